@@ -16,6 +16,9 @@ fused posterior/noise update -> advance] -- the unit the 1000-step sampler repea
 identical cost.  K steps are timed after W warm-up steps; one sampled patch = T = 1000 such steps, so
     value = n_gpus * batch_per_gpu / (T * seconds_per_step)       [patches/s, whole job].
 `--full` instead times complete 1000-step .sample() calls (K = number of calls).
+The W + K steps are the first steps of one sample (seed 1), started again should they run past its last step, so that the same
+arguments time the same steps; `--dump-outputs DIR` writes what the last of them returned -- x_t after it and the network output
+(`--full`: the last sample() call's result) -- as DIR/<name>.npy, float32, for comparing two builds output for output.
 
 Also on the JSON line: `roofline` for the dominant kernel family (conv3x3: exact-fp32 MFMA bound)
 measured with HIP events on the library's stream in a separate instrumented pass over the same
@@ -44,7 +47,9 @@ PEAK_HBM_GBS = 8000.0
 def parse():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=20)
+    ap.add_argument("--steps", type=int, default=20,
+                    help="timed sampler steps; should warm-up + steps run past the sampler's last step, the sample is started again inside the "
+                         "timed window (one host synchronisation each, counted as config.sample_restarts_timed on the JSON line)")
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--dim", type=int, default=64)
     ap.add_argument("--size", type=int, default=256)
@@ -66,7 +71,29 @@ def parse():
     ap.add_argument("--soak-s", type=float, default=3.0, help="seconds of untimed step replays before the W warm-up steps")
     ap.add_argument("--no-full-sample", action="store_true", help="skip the one complete sample() call timed behind the K-step leg (N = 1 only)")
     ap.add_argument("--no-alt", action="store_true", help="accepted and ignored (r4 timed a second product form here; there is one form since r5)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step (or, with --full, the last sample() call) returned as DIR/<name>.npy")
     return ap.parse_args()
+
+
+DUMP_BYTES = 64_000_000
+
+
+def dump_outputs(dirname, arrays, budget=DUMP_BYTES):
+    """Write every tensor of `arrays` as DIR/<name>.npy in float32, `budget` bytes in all at most (each of N ranks writing into the same DIR
+    gets DUMP_BYTES / N): a tensor larger than its share is written as the elements at fixed flat indices (drawn from a generator seeded
+    with 0, ascending), the same ones for every run of the same shapes.  Returns {name: {"shape", "elements_written"}} for the JSON line."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    share = (budget // len(arrays) - 4096) // 4              # elements per array; 4096 bytes left for each .npy header
+    info = {}
+    for name, t in arrays.items():
+        v = t.detach().to("cpu", torch.float32).numpy()
+        if v.size > share:
+            v = v.reshape(-1)[np.unique(np.random.default_rng(0).integers(0, v.size, share))]
+        np.save(os.path.join(dirname, name + ".npy"), v)
+        info[name] = {"shape": list(t.shape), "elements_written": int(v.size)}
+    return info
 
 
 def _pmc_profile(kind):
@@ -513,7 +540,7 @@ def main():
             dist.barrier()
         torch.cuda.synchronize(dev)
 
-    soak_steps = 0
+    soak_steps, timed_restarts, own_restarts = 0, None, None
     if a.full:
         kw = dict(batch_size=B, condition={k: v.to(dev) for k, v in cond.items()})
         for _ in range(a.warmup):
@@ -521,7 +548,7 @@ def main():
         barrier()
         t0 = time.perf_counter()
         for i in range(a.steps):
-            gd.sample(seed=2 + i, **kw)
+            last = gd.sample(seed=2 + i, **kw)
         plan.e.sync()
         barrier()
         dt = time.perf_counter() - t0
@@ -531,7 +558,8 @@ def main():
     else:
         from noisediff_amd.diffusion import _Loop
         loop = _Loop(gd, plan)
-        loop.start(None, None, seed=1, first_sample=rank * B, use_graph=not a.eager)
+        start = lambda: loop.start(None, None, seed=1, first_sample=rank * B, use_graph=not a.eager)
+        start()
         # untimed soak before the W warm-up steps: the chip reaches the clocks / temperature it holds over a 1000-step
         # sample() (fp32 MFMA load throttles to ~2.1 GHz after the first second), and an outside utilisation probe sees the job
         t_soak = time.perf_counter()
@@ -539,16 +567,38 @@ def main():
             loop.advance(10)
             plan.e.sync()
             soak_steps += 10
-        loop.advance(a.warmup)
+        # the soak is a time, not a number of steps: the warm-up and timed steps begin a fresh sample, so that they are the same steps on every run
+        start()
+        done = 0
+
+        def run_steps(n):
+            """n steps of the sampler; a sample that has taken its last step is started again (a step past the last one skips the update).
+            Returns the number of restarts: each synchronises the host with the device (Loop.start)."""
+            nonlocal done
+            restarts = 0
+            while n:
+                if done == loop.n_steps:
+                    start()
+                    done, restarts = 0, restarts + 1
+                k = min(n, loop.n_steps - done)
+                loop.advance(k)
+                done, n = done + k, n - k
+            return restarts
+
+        run_steps(a.warmup)
         plan.e.sync()
         barrier()
         t0 = time.perf_counter()
-        loop.advance(a.steps)
+        timed_restarts = run_steps(a.steps)
         plan.e.sync()
         barrier()
         dt = time.perf_counter() - t0
         per_step = dt / a.steps
         value = world * B / (n_sample_steps * per_step)
+    dumped = None
+    if a.dump_outputs:
+        outputs = {"sample": last} if a.full else {"x": plan.read_nchw(plan.x), "model_out": plan.read_nchw(plan.model_out)}
+        dumped = dump_outputs(a.dump_outputs, outputs if world == 1 else {f"{k}_rank{rank}": v for k, v in outputs.items()}, DUMP_BYTES // world)
     if world > 1:
         # every rank timed the same K steps between the same two barriers; its own GPU-side time for them (HIP events on the
         # library's stream around a second, untimed-by-the-metric replay of K steps) tells a slow rank from a slow barrier
@@ -557,7 +607,7 @@ def main():
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             ext = torch.cuda.ExternalStream(plan.e.stream.value, device=dev)
             e0.record(ext)
-            loop.advance(a.steps)
+            own_restarts = run_steps(a.steps)
             e1.record(ext)
             plan.e.sync()
             own_ms = e0.elapsed_time(e1) / a.steps
@@ -574,7 +624,7 @@ def main():
             except Exception as ex:          # noqa: BLE001 -- diagnostic field only
                 ver = f"unavailable ({type(ex).__name__})"
             bcast.update({"rccl_version": ver if a.backend == "nccl" else None,
-                          "ms_per_step_by_rank_wall": wall, "ms_per_step_by_rank_gpu_events": gpu,
+                          "ms_per_step_by_rank_wall": wall, "ms_per_step_by_rank_gpu_events": gpu, "sample_restarts_in_gpu_event_replay": own_restarts,
                           "ms_per_step_min_over_ranks": min(wall), "ms_per_step_max_over_ranks": max(wall)})
 
     sampler = f"{a.sampling_timesteps}-step DDIM of {T}" if a.sampling_timesteps else f"{T}-step DDPM"
@@ -592,7 +642,8 @@ def main():
                                 "one reverse-diffusion step (U-Net forward + fused posterior/noise update) over the per-GPU batch; "
                                 f"patches/s = n_gpus*{B}/({n_sample_steps}*s_per_step)"),
                    "global_batch": world * B, "launch": "eager" if a.eager else "hipGraph replay",
-                   "noise": "device Philox4x32-10", "untimed_soak_steps": soak_steps},
+                   "noise": "device Philox4x32-10", "untimed_soak_steps": soak_steps,
+                   "sample_restarts_timed": timed_restarts},
     }
     if rank == 0 and world == 1 and not a.full and not a.eager and not a.no_full_sample:
         # the metric itself, once: ONE complete sample() call (x_T, every reverse step, the final clamp and the NCHW read-back) on the same condition; the
@@ -611,6 +662,8 @@ def main():
                                       "defines -- when this call is more than 2 % slower (a box that throttles over 16 s of sustained load), read THIS figure"}
     if bcast:
         out["multi_gpu"] = bcast
+    if dumped:
+        out["dumped_outputs"] = {"dir": a.dump_outputs, "arrays": dumped}
     if rank == 0 and not a.no_roofline:
         out["roofline"] = roofline(a, loop, plan, L, per_step)
     if rank == 0 and world == 1 and not a.no_cpu:

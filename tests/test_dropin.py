@@ -1,19 +1,23 @@
 """The zero-edit overlay (noisediff_amd/dropin.py): the reference's import names resolve to this package's classes.
 
-Two checks, each in a fresh interpreter (the overlay patches the import system):
-  * a miniature tree with the reference's LAYOUT (models/modules.py-style registry scanning archs/*_arch.py by suffix,
-    a script importing `from models.denoising_diffusion_pytorch import GaussianDiffusion`) written by this test;
-  * the real reference tree when it is mounted (build container only; skipped on the GPU box).
+Two checks:
+  * in a fresh interpreter (the overlay patches the import system), a miniature tree with the reference's LAYOUT
+    (models/modules.py-style registry scanning archs/*_arch.py by suffix, a script importing
+    `from models.denoising_diffusion_pytorch import GaussianDiffusion`) written by this test;
+  * the classes the overlay rebinds, against the recorded shape of the reference's own classes (tests/golden/arch_meta.json).
 """
+import json
 import os
 import subprocess
 import sys
 import textwrap
+from types import SimpleNamespace
 
-import pytest
+import torch
+
+from noisediff_amd import dropin, train
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REF = "/root/reference"
 
 
 def _run(code, cwd, *args):
@@ -59,36 +63,21 @@ def test_overlay_on_a_tree_with_the_reference_layout(tmp_path):
     assert "RESULT models.archs.Diffusion_arch NoiseDiffNet noisediff_amd.diffusion ['train'] False" in out
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason="reference tree not mounted (GPU box)")
-def test_overlay_on_the_real_reference_registry():
-    """models/modules.py (the registry itself, unedited) hands out the HIP classes; training keeps the reference's."""
-    out = _run("""
-        import sys, types
-        sys.dont_write_bytecode = True
-        from types import SimpleNamespace
-        import torch
-        from noisediff_amd import dropin, train
-        dropin.install()
-        sys.path.insert(0, %r)
-        import models.modules as M
-        from models.denoising_diffusion_pytorch import GaussianDiffusion
-        for name in ('NoiseDiffNet', 'UNet_PosEmbV2', 'UNet_PosEmbV2_NoPosition', 'UNet_PosEmbV2_CameraCond'):
-            a = SimpleNamespace(net_name=name, dim=16, cond_dim=4, inp_dim=4, self_condition=False, normalize_condition=False, phase='test')
-            hip = M.define_network(a)
-            a.phase = 'train'
-            ref = M.define_network(a)
-            assert [(k, tuple(v.shape)) for k, v in hip.state_dict().items()] == [(k, tuple(v.shape)) for k, v in ref.state_dict().items()], name
-            hip.load_state_dict(ref.state_dict(), strict=True)        # a checkpoint trained on the reference class loads unchanged
-            n3 = sum(1 for m in ref.modules() if isinstance(m, torch.nn.Conv2d) and m.kernel_size == (3, 3))
-            acc = sum(1 for m in ref.modules() if getattr(getattr(m, 'forward', None), '__func__', None) is train._hip_conv_forward)
-            assert acc == n3 > 20, (name, acc, n3)                    # training: every 3x3 conv of the reference class goes through the HIP library
-            print('RESULT', name, type(hip).__module__, type(ref).__module__)
-        import torch
-        gd = GaussianDiffusion(torch.nn.DataParallel(ref), image_size=32, timesteps=20, beta_schedule='sigmoid2')
-        print('RESULT gd', type(gd).__module__, len(list(gd.buffers())))
-        a = SimpleNamespace(net_name='LSID', phase='test')
-        assert type(M.define_network(a)).__module__ == 'models.archs.SID_arch'       # other archs are untouched
-    """ % REF, REPO)
-    assert "RESULT NoiseDiffNet noisediff_amd.net models.archs.Diffusion_arch" in out
-    assert "RESULT UNet_PosEmbV2_CameraCond noisediff_amd.net models.archs.others_arch" in out
-    assert "RESULT gd noisediff_amd.diffusion 13" in out
+
+def test_overlay_classes_match_the_reference_classes_they_replace():
+    """Against the reference classes as tests/golden/capture_arch_meta.py recorded them at d=16, for every class the overlay rebinds: the HIP
+    network the registry hands out for inference has the reference class's state dict, name for name and shape for shape (a checkpoint trained
+    on the reference class loads unchanged), and the training path takes every 3x3 convolution the reference class holds."""
+    import noisediff_amd
+    with open(os.path.join(REPO, "tests", "golden", "arch_meta.json")) as f:
+        meta = json.load(f)
+    for name in dropin.HIP_CLASSES:
+        ref = meta[name]
+        net = getattr(noisediff_amd, name)(SimpleNamespace(dim=meta["dim"], cond_dim=4, inp_dim=4, self_condition=False, normalize_condition=False))
+        assert [[k, list(v.shape)] for k, v in net.state_dict().items()] == ref["state_dict"], name
+        shapes = dict((k, v) for k, v in ref["state_dict"])
+        convs = torch.nn.ModuleList()
+        for conv, cin, cout, stride, padding, dilation, groups, mode in ref["conv3x3"]:
+            assert shapes[conv + ".weight"] == [cout, cin // groups, 3, 3], (name, conv)
+            convs.append(torch.nn.Conv2d(cin, cout, 3, stride=stride, padding=padding, dilation=dilation, groups=groups, padding_mode=mode))
+        assert len(convs) > 20 and train.accelerate(convs) == len(convs), name

@@ -829,10 +829,11 @@ def test_n_rank_hip_sampler_equals_single_rank(mode, world, total):
     assert rel_err(got, ref.numpy()) < SAMPLE_TOL / 10
 
 
-def test_bench_self_launcher_two_ranks_on_one_device():
+def test_bench_self_launcher_two_ranks_on_one_device(tmp_path):
     """`python bench.py --gpus 2` as the driver starts it: a fresh child process that spawns the two rank processes itself (both on cuda:0 here, gloo
     rendezvous on 127.0.0.1), one weight broadcast, zero per-step collectives, one JSON line from rank 0; and a job size that contradicts WORLD_SIZE is
-    refused with exit code 2 instead of being reported as something it is not (reference entry: models/modules.py:73-83)."""
+    refused with exit code 2 instead of being reported as something it is not (reference entry: models/modules.py:73-83).
+    --dump-outputs: each rank writes its own shard into the one DIR."""
     import json
     import os
     import subprocess
@@ -842,7 +843,7 @@ def test_bench_self_launcher_two_ranks_on_one_device():
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
     cmd = [sys.executable, os.path.join(repo, "bench.py"), "--gpus", "2", "--one-device", "--backend", "gloo", "--steps", "2", "--warmup", "1", "--soak-s", "0",
-           "--no-cpu", "--no-roofline", "--size", "64", "--batch", "2", "--timesteps", "8"]
+           "--no-cpu", "--no-roofline", "--size", "64", "--batch", "2", "--timesteps", "8", "--dump-outputs", str(tmp_path)]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     line = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
@@ -851,10 +852,45 @@ def test_bench_self_launcher_two_ranks_on_one_device():
     assert mg["ranks_in_broadcast"] == 2 and mg["arena_checksum_equal_on_all_ranks"] is True and mg["per_step_collectives"] == 0
     assert len(mg["ms_per_step_by_rank_wall"]) == 2 and len(mg["ms_per_step_by_rank_gpu_events"]) == 2
     assert "bench.py started the ranks itself" in mg["launcher"]
+    assert line["config"]["sample_restarts_timed"] == 0 and mg["sample_restarts_in_gpu_event_replay"] == 0
+    assert sorted(os.listdir(tmp_path)) == ["model_out_rank0.npy", "model_out_rank1.npy", "x_rank0.npy", "x_rank1.npy"]
+    x0, x1 = np.load(tmp_path / "x_rank0.npy"), np.load(tmp_path / "x_rank1.npy")
+    assert x0.shape == x1.shape == (2, 4, 64, 64) and np.isfinite(x0).all() and not np.array_equal(x0, x1)     # rows 0..1 and 2..3 of the job
     bad = subprocess.run([sys.executable, os.path.join(repo, "bench.py"), "--gpus", "3", "--one-device", "--backend", "gloo", "--steps", "1", "--warmup", "0",
                           "--soak-s", "0", "--no-cpu", "--no-roofline"], env=dict(env, WORLD_SIZE="2", RANK="0", LOCAL_RANK="0"), capture_output=True, text=True,
                          timeout=300)
     assert bad.returncode == 2 and "WORLD_SIZE=2" in bad.stderr
+
+
+def test_bench_dump_outputs_are_the_same_steps_whatever_the_soak(tmp_path):
+    """`bench.py --dump-outputs DIR`: x_t and the network output of the last timed step.  The warm-up and timed steps begin a fresh sample whatever the
+    untimed soak did, and --steps counts real sampler steps: W + K beyond the sampler's length start the sample again, so W=3, K=7 on an 8-step sampler
+    ends where W=1, K=1 does -- bit for bit, with or without a soak -- and one step more does not."""
+    import json
+    import os
+    import subprocess
+    import sys
+    repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = dict(os.environ)
+    for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT"):
+        env.pop(k, None)
+
+    def run(tag, warmup, steps, soak):
+        d = tmp_path / tag
+        cmd = [sys.executable, os.path.join(repo, "bench.py"), "--no-cpu", "--no-roofline", "--no-full-sample", "--dim", "16", "--size", "32", "--batch", "2",
+               "--timesteps", "8", "--warmup", str(warmup), "--steps", str(steps), "--soak-s", str(soak), "--dump-outputs", str(d)]
+        r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-2000:]
+        line = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
+        assert line["steps"] == steps and line["dumped_outputs"]["arrays"]["x"] == {"shape": [2, 4, 32, 32], "elements_written": 2 * 4 * 32 * 32}
+        assert line["config"]["sample_restarts_timed"] == (1 if tag == "wrapped" else 0)
+        return {n: np.load(d / f"{n}.npy") for n in ("x", "model_out")}
+
+    one = run("one", 1, 1, 0)
+    for other in (run("soaked", 1, 1, 0.5), run("wrapped", 3, 7, 0)):
+        for n in one:
+            assert other[n].dtype == np.float32 and np.array_equal(other[n], one[n]), n
+    assert np.isfinite(one["x"]).all() and not np.array_equal(run("next", 1, 2, 0)["x"], one["x"])
 
 
 def test_split_chains_of_a_batch_cut_into_pieces_equal_the_whole_batch_bit_for_bit(monkeypatch):

@@ -275,6 +275,31 @@ def test_generated_npy_contract(tmp_path):
     assert io.psnr(torch.zeros(4), torch.full((4,), 0.1)) == pytest.approx(20.0, abs=1e-4)
 
 
+def test_bench_dump_outputs_are_float32_and_within_the_budget(tmp_path):
+    """bench.py --dump-outputs: DIR/<name>.npy in float32, DUMP_BYTES in all at most; an output larger than its share is written as the elements
+    at the same fixed, ascending flat indices on every call."""
+    import bench
+    small = torch.arange(24, dtype=torch.float64).reshape(2, 3, 4)
+    big = torch.arange(bench.DUMP_BYTES // 6, dtype=torch.float32)            # 2/3 of the budget on its own: more than its half
+    files = []
+    for run in ("a", "b"):
+        info = bench.dump_outputs(str(tmp_path / run), {"small": small, "big": big})
+        files.append({n: np.load(tmp_path / run / f"{n}.npy") for n in info})
+        assert sum(os.path.getsize(tmp_path / run / f"{n}.npy") for n in info) <= bench.DUMP_BYTES
+        assert info["small"] == {"shape": [2, 3, 4], "elements_written": 24} and info["big"]["shape"] == [big.numel()]
+    got = files[0]
+    assert got["small"].dtype == np.float32 and np.array_equal(got["small"], small.float().numpy())
+    assert got["big"].dtype == np.float32 and got["big"].ndim == 1 and got["big"].size > big.numel() // 3
+    assert np.all(np.diff(got["big"]) > 0) and got["big"][-1] < big.numel()        # distinct elements, ascending
+    assert np.array_equal(got["big"], files[1]["big"])
+    # --gpus N: every rank writes its own files into the same DIR with DUMP_BYTES / N; the run as a whole stays within DUMP_BYTES
+    world, shard = 4, torch.arange(bench.DUMP_BYTES // 8, dtype=torch.float32)     # two of them per rank: twice a rank's share
+    for rank in range(world):
+        bench.dump_outputs(str(tmp_path / "ranks"), {f"x_rank{rank}": shard, f"model_out_rank{rank}": shard}, bench.DUMP_BYTES // world)
+    assert len(os.listdir(tmp_path / "ranks")) == 2 * world
+    assert sum(os.path.getsize(tmp_path / "ranks" / f) for f in os.listdir(tmp_path / "ranks")) <= bench.DUMP_BYTES
+
+
 def test_blocked_map_row_permutation():
     """engine._blocked_map_rows: output row order of the ResnetBlock2 map Linear for nd_src.map_blocked (include/noisediff_hip.h):
     position 32 c + j holds scale channel 16 c + j (j < 16) or shift channel 16 c + j - 16."""
