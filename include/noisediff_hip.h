@@ -202,6 +202,24 @@ int nd_conv3x3_wgrad_cat_nhwc_f32(const float* x0, int ldx0, int c0, const float
 int nd_conv3x3_wgrad_form(int form);
 int nd_conv3x3_wgrad_nhwc_f32(const float* x, int ldx, const float* dy, int ldy, float* dw_oihw, float* dbias, float* workspace,
                               int B, int H, int W, int cin, int cout, void* stream);
+/* LSID training (models/archs/SID_arch.py:105-175; noisediff_amd/lsid_train.py): the same weight gradients for an input that is LeakyReLU(0.2) of the
+ * RAW tensor passed -- the activation is applied as the operand is staged, no activated copy.  Same forms, split and summation order as above.
+ * _leaky: x is raw, the layer's input is leaky(x) (every 3x3 convolution of LSID but conv1_1).  _cat_leaky_second: the input is
+ * cat((x0, leaky(x1)), channels) -- torch.cat((up(x), conv_k)) in front of conv6_1 .. conv9_1 (:135,142,150,158), as ND_PRO_LEAKY_SECOND reads it
+ * forward; any channel counts that are multiples of 4 (the Winograd-domain form where nd_conv3x3_wgrad_cat_nhwc_f32 takes the shape, else the nine-tap
+ * form per source into its columns of dw).  Workspace: nd_conv3x3_wgrad_cat_workspace_floats. */
+int nd_conv3x3_wgrad_leaky_nhwc_f32(const float* x, int ldx, const float* dy, int ldy, float* dw_oihw, float* dbias, float* workspace,
+                                    int B, int H, int W, int cin, int cout, void* stream);
+int64_t nd_conv3x3_wgrad_cat_workspace_floats(int B, int H, int W, int c0, int c1, int cout);
+int nd_conv3x3_wgrad_cat_leaky_second_nhwc_f32(const float* x0, int ldx0, int c0, const float* x1, int ldx1, int c1, const float* dy, int ldy,
+                                               float* dw_oihw, float* dbias, float* workspace, int B, int H, int W, int cout, void* stream);
+/* The gradient join at every LeakyReLU of the LSID training backward: dz = (d_direct + pool_scatter(d_pool)) * (z > 0 ? 1 : 0.2), one streaming pass.
+ * z, dz: [B][H][W][C] dense (z = the convolution's RAW output); d_direct (may be NULL): [B][H][W] x ld_direct, the gradient of leaky(z) through
+ * its direct consumers (e.g. the skip half of a concat convolution's data gradient); d_pool (may be NULL): [B][ceil(H/2)][ceil(W/2)][C], the gradient
+ * of nn.MaxPool2d(2, 2, ceil_mode=True)(leaky(z)), routed to the first maximum of each window in row-major order (torch's max_pool2d backward, ties
+ * and partial border windows included).  dz may alias d_direct when ld_direct == C. */
+int nd_leaky_grad_join_f32(const float* z, float* dz, const float* d_direct, int ld_direct, const float* d_pool, int B, int H, int W, int C,
+                           void* stream);
 
 /* nn.GroupNorm(groups, C) forward and backward on NHWC fp32 for training: Block.norm (Diffusion_arch.py:132,138) under
  * GaussianDiffusion.p_losses -> loss.backward().  Statistics per (sample, group) over (C / groups) x HW values, eps inside the
@@ -261,6 +279,16 @@ int nd_layernorm_train_backward_f32(const float* dy, int lddy, const float* x, i
 int64_t nd_linear_wgrad_workspace_floats(int64_t N, int cin, int cout);
 int nd_linear_wgrad_f32(const float* x, int ldx, const float* dy, int ldy, float* dw, float* dbias, float* workspace,
                         int64_t N, int cin, int cout, void* stream);
+/* The same with LeakyReLU(0.2) applied to x as it is staged (LSID's conv10 on the raw conv9_2 output, SID_arch.py:168-172). */
+int nd_linear_wgrad_leaky_f32(const float* x, int ldx, const float* dy, int ldy, float* dw, float* dbias, float* workspace,
+                              int64_t N, int cin, int cout, void* stream);
+/* Weight gradient of nn.ConvTranspose2d(cin, cout, 2, stride=2, bias=False) on leaky(x) followed by the crop to (up_h, up_w) (SID_arch.py:134-158):
+ * dw[ci][c][p1][p2] = sum over (b, y, x) of leaky(x[b][y][x][ci]) * d_up[b][2y + p1][2x + p2][c], terms past the crop absent; x [B][h][w] x ldx raw,
+ * d_up [B][up_h][up_w] x ld_up (may be a channel slice), dw in torch's (cin, cout, 2, 2) layout.  Fixed split and order, as nd_linear_wgrad_f32.
+ * Workspace: nd_convt2x2_wgrad_workspace_floats(B, h, w, cin, cout). */
+int64_t nd_convt2x2_wgrad_workspace_floats(int B, int h, int w, int cin, int cout);
+int nd_convt2x2_wgrad_leaky_f32(const float* x, int ldx, const float* d_up, int ld_up, float* dw, float* workspace, int B, int h, int w,
+                                int cin, int cout, int up_h, int up_w, void* stream);
 
 /* ------------------------------------------------------------------ pointwise GEMM */
 
@@ -289,6 +317,10 @@ typedef struct nd_pointwise {
 } nd_pointwise;
 
 int nd_pointwise_gemm_nhwc_f32(const nd_pointwise* d, void* stream);
+/* The data gradient of ConvTranspose2d(k=2, s=2) + crop (SID_arch.py:134-158): d->src.unshuffle = 1 with p0 = d_up, an image of (src_h, src_w)
+ * <= (2 H, 2 W) pixels (H = HW / W), read as its pixel unshuffle with zeros for the rows / columns the forward cropped away; weight packed by
+ * nd_pack_pointwise_weight(w.reshape(cin, 4 c) of the ConvTranspose weight (cin, c, 2, 2), ..., cin = 4 c, cout = cin, unshuffle_c = c). */
+int nd_pointwise_gemm_unshuffle_crop_nhwc_f32(const nd_pointwise* d, int src_h, int src_w, void* stream);
 /* (cout, cin) row-major (Linear / 1x1 conv weight) -> [cinP/4][coutP][4]; `unshuffle_c` > 0
  * permutes K from (c p1 p2) to (p1 p2 c) for a pixel-unshuffled input with c = unshuffle_c. */
 int64_t nd_pack_pointwise_weight_floats(int cin, int cout);

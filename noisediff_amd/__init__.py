@@ -2,7 +2,7 @@
 __version__ = "0.1.0"
 
 __all__ = ["GaussianDiffusion", "NoiseDiffNet", "UNet_PosEmbV2", "UNet_PosEmbV2_NoPosition", "UNet_PosEmbV2_CameraCond", "LSID",
-           "TrainableNoiseDiffNet", "__version__"]
+           "TrainableNoiseDiffNet", "TrainableLSID", "__version__"]
 
 
 def __getattr__(name):
@@ -19,4 +19,7 @@ def __getattr__(name):
     if name == "TrainableNoiseDiffNet":
         from .trainable import TrainableNoiseDiffNet
         return TrainableNoiseDiffNet
+    if name == "TrainableLSID":
+        from .lsid_train import TrainableLSID
+        return TrainableLSID
     raise AttributeError(name)

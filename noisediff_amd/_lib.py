@@ -186,13 +186,22 @@ SIGNATURES = {
     "nd_event_create_untimed": (i32, [C.POINTER(vp)]),
     "nd_stream_wait_event": (i32, [vp, vp]),
     "nd_stream_device": (i32, [vp]),
+    "nd_conv3x3_wgrad_leaky_nhwc_f32": (i32, [vp, i32, vp, i32, vp, vp, vp, i32, i32, i32, i32, i32, vp]),
+    "nd_conv3x3_wgrad_cat_workspace_floats": (i64, [i32, i32, i32, i32, i32, i32]),
+    "nd_conv3x3_wgrad_cat_leaky_second_nhwc_f32": (i32, [vp, i32, i32, vp, i32, i32, vp, i32, vp, vp, vp, i32, i32, i32, i32, vp]),
+    "nd_leaky_grad_join_f32": (i32, [vp, vp, vp, i32, vp, i32, i32, i32, i32, vp]),
+    "nd_linear_wgrad_leaky_f32": (i32, [vp, i32, vp, i32, vp, vp, vp, i64, i32, i32, vp]),
+    "nd_convt2x2_wgrad_workspace_floats": (i64, [i32, i32, i32, i32, i32]),
+    "nd_convt2x2_wgrad_leaky_f32": (i32, [vp, i32, vp, i32, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp]),
+    "nd_pointwise_gemm_unshuffle_crop_nhwc_f32": (i32, [C.POINTER(Pointwise), i32, i32, vp]),
 }
 
 _UNCHECKED = {"nd_version", "nd_last_error", "nd_stream_device", "nd_conv3x3_wgrad_form", "nd_adam_chunk_elements", "nd_conv7x7_c4_wgrad_workspace_floats", "nd_conv3x3_stat_slots", "nd_conv3x3_tiling_id", "nd_pack_conv3x3_weight_floats",
               "nd_pack_pointwise_weight_floats", "nd_linear_attention_workspace_floats", "nd_conv3x3_wino_stat_slots", "nd_conv3x3_wino4_stat_slots",
               "nd_pack_conv3x3_wino_weight_floats", "nd_pack_conv3x3_wino4_weight_floats", "nd_conv3x3_wino4_splitk_plan", "nd_conv3x3_wino4_16_splitk_plan", "nd_conv3x3_wino4_splitk_workspace_floats", "nd_token_sum_workspace_floats", "nd_cond_step_lds_bytes", "nd_conv3x3_wgrad_workspace_floats",
               "nd_groupnorm_train_workspace_floats", "nd_linear_wgrad_workspace_floats",
-              "nd_layernorm_train_workspace_floats", "nd_groupnorm_silu_train_workspace_floats"}
+              "nd_layernorm_train_workspace_floats", "nd_groupnorm_silu_train_workspace_floats", "nd_conv3x3_wgrad_cat_workspace_floats",
+              "nd_convt2x2_wgrad_workspace_floats"}
 
 _lib: Optional[C.CDLL] = None
 

@@ -33,6 +33,8 @@ struct WgradArgs {
     unsigned dy_bytes, x_bytes;
 };
 
+// LK: LeakyReLU(0.2) applied to X as it is staged (LSID: the convolution's input is the activation of a raw pre-activation, SID_arch.py:105-168)
+template <bool LK>
 __global__ __launch_bounds__(256, (WG_TILE_ROWS <= 8 ? 2 : 1)) void wgrad_kernel(const WgradArgs a) {
     extern __shared__ __attribute__((aligned(16))) float sm[];
     float* dYs = sm;                                                 // [256 pixels][64 couts]
@@ -104,7 +106,7 @@ __global__ __launch_bounds__(256, (WG_TILE_ROWS <= 8 ? 2 : 1)) void wgrad_kernel
 #pragma unroll
                 for (int i = 0; i < DY_IT; ++i) nd_st4(dYs + (tr + 16 * i) * CB + 4 * q, vy[i]);
 #pragma unroll
-                for (int i = 0; i < XA; ++i) nd_st4(xdst + i * HALO * CB, vx[i]);
+                for (int i = 0; i < XA; ++i) nd_st4(xdst + i * HALO * CB, LK ? nd_leaky4(vx[i]) : vx[i]);
             }
             {
                 constexpr int XA = HALO_H / 2, XB = HALO_H - XA;
@@ -115,9 +117,9 @@ __global__ __launch_bounds__(256, (WG_TILE_ROWS <= 8 ? 2 : 1)) void wgrad_kernel
                 ve0 = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs_x, xe0_voff, x_base, 0));
                 ve1 = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs_x, xe1_voff, x_base, 0));
 #pragma unroll
-                for (int i = 0; i < XB; ++i) nd_st4(xdst + (XA + i) * HALO * CB, vx[i]);
-                nd_st4(Xs + ((tr >> 1) * HALO + 16 + (tr & 1)) * CB + 4 * q, ve0);
-                if (16 + tr < 2 * HALO_H) nd_st4(Xs + ((e1 >> 1) * HALO + 16 + (e1 & 1)) * CB + 4 * q, ve1);
+                for (int i = 0; i < XB; ++i) nd_st4(xdst + (XA + i) * HALO * CB, LK ? nd_leaky4(vx[i]) : vx[i]);
+                nd_st4(Xs + ((tr >> 1) * HALO + 16 + (tr & 1)) * CB + 4 * q, LK ? nd_leaky4(ve0) : ve0);
+                if (16 + tr < 2 * HALO_H) nd_st4(Xs + ((e1 >> 1) * HALO + 16 + (e1 & 1)) * CB + 4 * q, LK ? nd_leaky4(ve1) : ve1);
             }
         } else
 #ifdef WG_ABLATE_STAGE
@@ -168,7 +170,7 @@ __global__ __launch_bounds__(256, (WG_TILE_ROWS <= 8 ? 2 : 1)) void wgrad_kernel
                         const int p = (tid >> 4) + 16 * (i0 + j), py = p / HALO, px = p - py * HALO;
                         const int gy = y0 + py - 1, gx = x0 + px - 1;
                         const bool ok = cx_ok && (unsigned)gy < (unsigned)a.H && (unsigned)gx < (unsigned)a.W;
-                        if (p < HALO * HALO_H) nd_st4(Xs + p * CB + 4 * q, ok ? v[j] : zero);
+                        if (p < HALO * HALO_H) nd_st4(Xs + p * CB + 4 * q, ok ? (LK ? nd_leaky4(v[j]) : v[j]) : zero);
                     }
                 }
             }
@@ -216,7 +218,8 @@ __global__ __launch_bounds__(256, (WG_TILE_ROWS <= 8 ? 2 : 1)) void wgrad_kernel
 // dW (OIHW, torch layout) = sum over the S partials in a fixed order.  A thread owns one element (tap, co, ci) of the partial
 // blocks -- consecutive threads read consecutive cins, every load of the S-deep sum is coalesced -- and scatters its one result.
 __global__ __launch_bounds__(256) void wgrad_reduce_kernel(const float* __restrict__ ws, const float* __restrict__ wsb, float* __restrict__ dw,
-                                                           float* __restrict__ db, int S, int cin, int cout, int coP, int ciP) {
+                                                           float* __restrict__ db, int S, int cin, int cout, int coP, int ciP, int dw_cin = 0, int dw_ci0 = 0) {
+    if (dw_cin == 0) dw_cin = cin;                                   // dw_cin / dw_ci0: dw has dw_cin input channels, this gradient fills dw_ci0 .. + cin - 1
     const size_t block = (size_t)9 * coP * ciP, total = block + (db ? coP : 0);     // the bias partials follow the weight partials element-wise
     for (size_t j = blockIdx.x * (size_t)blockDim.x + threadIdx.x; j < total; j += (size_t)gridDim.x * blockDim.x) {
         const bool bias = j >= block;
@@ -237,7 +240,7 @@ __global__ __launch_bounds__(256) void wgrad_reduce_kernel(const float* __restri
         }
         for (; s < S; ++s) sum += p[(size_t)s * stride];
         if (bias) db[co] = sum;
-        else dw[((size_t)co * cin + ci) * 9 + t] = sum;
+        else dw[((size_t)co * dw_cin + dw_ci0 + ci) * 9 + t] = sum;
     }
 }
 
@@ -292,6 +295,7 @@ struct WwArgs {
     int ldx1, c0;
     int ldx, ldy, B, H, W, cin, cout;
     int n_co, n_ci, S, gx, gy, n_groups, wide, coP, ciP;
+    int lk0, lk1;                                                    // LeakyReLU(0.2) on the staged input of source 0 / 1 (kernels instantiated with LK only)
 };
 
 typedef float ww_f2 __attribute__((ext_vector_type(2)));
@@ -360,7 +364,7 @@ __device__ __forceinline__ void ww_a6(const ww_f2 (&y)[4], ww_f2 (&o)[6]) {
 //     L(p+3)  the requests for group p + 3 into staging set (p + 1) & 1 (a whole phase in flight)
 // Everything indexed by the parity of p is a compile-time constant of the two copies of the phase (register sets, LDS offsets as immediates).
 // Phases -2 and -1 fill the pipeline (no MFMAs); past the last group X / W / L run on clamped, unused data.
-template <bool ISV, int RH>
+template <bool ISV, int RH, bool LK>
 __device__ __forceinline__ void ww_wave(const WwArgs& a, float* sm, const int wave, const int lane) {
     constexpr int NIT = ISV ? WW_Y_IT : WW_X_IT;
     const int col = lane & 31, half = lane >> 5;
@@ -386,6 +390,7 @@ __device__ __forceinline__ void ww_wave(const WwArgs& a, float* sm, const int wa
     const bool second = !ISV && ci0 >= a.c0;                         // the workgroup's cin block lies in the second source (blocks never straddle: c0 % 32 == 0)
     const int ld = ISV ? a.ldy : second ? a.ldx1 : a.ldx;
     const float* const src = ISV ? a.dy : second ? a.x1 : a.x;
+    const bool lk = LK && !ISV && (second ? a.lk1 : a.lk0) != 0;     // workgroup-uniform
     const int cs0 = ISV ? co0 : second ? ci0 - a.c0 : ci0;           // first channel of the block within its source
     const int sc = u >> 3, sq = u & 7;
     const int OOB = (int)0x80000000;
@@ -460,7 +465,8 @@ __device__ __forceinline__ void ww_wave(const WwArgs& a, float* sm, const int wa
         float* const vdw = sm + 2 * WW_RAWF + Q * (2 * WW_VDF) + wr_off + (3 * RH * 6) * 128;        // X(p+1) writes its rows of VD[(p+1) & 1]
         auto commit = [&](auto ii, auto hh) {                        // W: half of one staged float4 -> the raw buffer.  8-byte writes: behind an MFMA a ds_write_b64
             constexpr int it = decltype(ii)::value, h = decltype(hh)::value;      // costs the wave ~2 cycles, a ds_write_b128 ~80 (tools/wgrad_clock.py)
-            const ww_f2 v = h ? ww_f2{sr[P][it][2], sr[P][it][3]} : ww_f2{sr[P][it][0], sr[P][it][1]};
+            ww_f2 v = h ? ww_f2{sr[P][it][2], sr[P][it][3]} : ww_f2{sr[P][it][0], sr[P][it][1]};
+            if constexpr (LK && !ISV) { if (lk) v = ww_f2{fmaxf(v[0], 0.2f * v[0]), fmaxf(v[1], 0.2f * v[1])}; }
             float* d;
             if constexpr (ISV) d = wbuf + lds_c + it * WW_GW * WW_PS;
             else if constexpr (it < 6) d = wbuf + lds_c + it * WW_HC * WW_PS;
@@ -603,13 +609,14 @@ __device__ __forceinline__ void ww_wave(const WwArgs& a, float* sm, const int wa
     }
 }
 
+template <bool LK>
 __global__ __launch_bounds__(256, 1) void wgrad_wino_kernel(const WwArgs a) {
     extern __shared__ __attribute__((aligned(16))) float sm[];
     const int wave = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6), lane = threadIdx.x & 63;     // scalar: the four roles are wave-uniform branches
-    if (wave == 0) ww_wave<true, 0>(a, sm, wave, lane);
-    else if (wave == 1) ww_wave<true, 1>(a, sm, wave, lane);
-    else if (wave == 2) ww_wave<false, 0>(a, sm, wave, lane);
-    else ww_wave<false, 1>(a, sm, wave, lane);
+    if (wave == 0) ww_wave<true, 0, LK>(a, sm, wave, lane);
+    else if (wave == 1) ww_wave<true, 1, LK>(a, sm, wave, lane);
+    else if (wave == 2) ww_wave<false, 0, LK>(a, sm, wave, lane);
+    else ww_wave<false, 1, LK>(a, sm, wave, lane);
 }
 
 // ---- the same pipeline for a (64 couts x 32 cins) block on EIGHT waves, two per SIMD (taken when cout % 64 == 0).  What bounds the four-wave form
@@ -631,7 +638,7 @@ constexpr size_t W8_LDS = (size_t)(2 * W8_RAWF + W8_VDF) * sizeof(float);
 
 enum { W8_V = 0, W8_D = 1, W8_S = 2 };
 
-template <int ROLE, int RH>
+template <int ROLE, int RH, bool LK>
 __device__ __forceinline__ void ww8_wave(const WwArgs& a, float* sm, const int wave, const int lane) {
     constexpr int NIT = ROLE == W8_S ? WW_X_IT : ROLE == W8_D ? WW_Y_IT : 1;
     const int col = lane & 31, half = lane >> 5;
@@ -655,6 +662,7 @@ __device__ __forceinline__ void ww8_wave(const WwArgs& a, float* sm, const int w
     const bool second = ROLE != W8_D && ci0 >= a.c0;                 // (see ww_wave)
     const int ld = ROLE == W8_D ? a.ldy : second ? a.ldx1 : a.ldx;
     const float* const src = ROLE == W8_D ? a.dy : second ? a.x1 : a.x;
+    const bool lk = LK && ROLE == W8_S && (second ? a.lk1 : a.lk0) != 0;      // workgroup-uniform
     const int cs0 = ROLE == W8_D ? co0 : second ? ci0 - a.c0 : ci0;
     const int sc = ROLE == W8_D ? u >> 4 : u >> 3, sq = ROLE == W8_D ? u & 15 : u & 7;
     const int vl = (sc * ld + cs0 + 4 * sq) * 4;
@@ -738,8 +746,8 @@ __device__ __forceinline__ void ww8_wave(const WwArgs& a, float* sm, const int w
         auto commit = [&](auto ii) {                                 // one staged float4 -> the raw buffer
             constexpr int it = decltype(ii)::value;
             if constexpr (ROLE == W8_D) nd_st4(wbuf + st_c + it * WW_GW * W8_PSY, sr[it]);
-            else if constexpr (ROLE == W8_S && it < 6) nd_st4(wbuf + st_c + it * WW_HC * WW_PS, sr[it]);
-            else if constexpr (ROLE == W8_S) { if (u < 96) nd_st4(wbuf + st_6, sr[6]); }
+            else if constexpr (ROLE == W8_S && it < 6) nd_st4(wbuf + st_c + it * WW_HC * WW_PS, LK && lk ? nd_leaky4(sr[it]) : sr[it]);
+            else if constexpr (ROLE == W8_S) { if (u < 96) nd_st4(wbuf + st_6, LK && lk ? nd_leaky4(sr[6]) : sr[6]); }
         };
         // ================= segment 1 (behind barrier A): positions 7, 8 of the previous group, then this group's operands
         W8_MFMA(7, 0)  W8_MFMA(8, 0)  W8_MFMA(7, 1)  W8_MFMA(8, 1)
@@ -869,15 +877,16 @@ __device__ __forceinline__ void ww8_wave(const WwArgs& a, float* sm, const int w
     }
 }
 
+template <bool LK>
 __global__ __launch_bounds__(512, 1) void wgrad_wino8_kernel(const WwArgs a) {
     extern __shared__ __attribute__((aligned(16))) float sm[];
     const int wave = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6), lane = threadIdx.x & 63;
     switch (wave) {
-        case 0: ww8_wave<W8_V, 0>(a, sm, wave, lane); break;
-        case 1: ww8_wave<W8_V, 1>(a, sm, wave, lane); break;
-        case 4: case 5: ww8_wave<W8_S, 0>(a, sm, wave, lane); break;
-        case 2: case 6: ww8_wave<W8_D, 0>(a, sm, wave, lane); break;
-        default: ww8_wave<W8_D, 1>(a, sm, wave, lane); break;
+        case 0: ww8_wave<W8_V, 0, LK>(a, sm, wave, lane); break;
+        case 1: ww8_wave<W8_V, 1, LK>(a, sm, wave, lane); break;
+        case 4: case 5: ww8_wave<W8_S, 0, LK>(a, sm, wave, lane); break;
+        case 2: case 6: ww8_wave<W8_D, 0, LK>(a, sm, wave, lane); break;
+        default: ww8_wave<W8_D, 1, LK>(a, sm, wave, lane); break;
     }
 }
 
@@ -1044,28 +1053,32 @@ extern "C" int64_t nd_conv3x3_wgrad_workspace_floats(int B, int H, int W, int ci
     return n;
 }
 
-static int wgrad_run(const float* x, int ldx, int c0, const float* x1, int ldx1, const float* dy, int ldy, float* dw_oihw, float* dbias, float* workspace,
-                     int B, int H, int W, int cin, int cout, void* stream) {
+// lk0 / lk1: LeakyReLU(0.2) on the input of source 0 / 1 as it is staged (the nd_conv3x3_wgrad_*leaky* entries).  dw_cin / dw_ci0 (nine taps only): dw has
+// dw_cin input channels and this gradient fills dw_ci0 .. dw_ci0 + cin - 1 (0, 0: dw is (cout, cin, 3, 3)).
+template <bool LK>
+static int wgrad_run_t(const float* x, int ldx, int c0, const float* x1, int ldx1, const float* dy, int ldy, float* dw_oihw, float* dbias, float* workspace,
+                       int B, int H, int W, int cin, int cout, void* stream, int lk0, int lk1, int dw_cin, int dw_ci0) {
     ND_REQUIRE(x && dy && dw_oihw && workspace, ND_E_BADARG, "nd_conv3x3_wgrad: null pointer");
     ND_REQUIRE(B > 0 && H > 0 && W > 0 && cin > 0 && cout > 0, ND_E_BADARG, "nd_conv3x3_wgrad: non-positive size");
     ND_REQUIRE(cin % 4 == 0 && cout % 4 == 0 && ldx >= c0 && ldy >= cout && ldx % 4 == 0 && ldy % 4 == 0, ND_E_SHAPE,
                "nd_conv3x3_wgrad: cin=%d, cout=%d and the pixel strides must be multiples of 4", cin, cout);
     ND_REQUIRE(nd_aligned16(x) && nd_aligned16(dy), ND_E_ALIGN, "nd_conv3x3_wgrad: x and dy must be 16-byte aligned");
-    if (ww_takes(B, H, W, cin, cout) && (long)H * W * ldx * 4 < (1L << 30) && (long)H * W * ldy * 4 < (1L << 30)) {     // F(4x4) Winograd-domain form (a quarter of the MFMAs); 32-bit offsets within a sample
+    if (dw_cin == 0 && ww_takes(B, H, W, cin, cout) && (long)H * W * ldx * 4 < (1L << 30) && (long)H * W * ldy * 4 < (1L << 30)) {     // F(4x4) Winograd-domain form (a quarter of the MFMAs); 32-bit offsets within a sample
         WwArgs w;
         ww_plan(B, H, W, cin, cout, w);
         w.x = x; w.dy = dy; w.ws = workspace; w.ldx = ldx; w.ldy = ldy;
         w.x1 = x1; w.ldx1 = ldx1; w.c0 = c0;
+        w.lk0 = lk0; w.lk1 = lk1;
         w.wsb = dbias ? workspace + (size_t)w.S * 36 * w.coP * w.ciP : nullptr;
         static nd_device_once configured_w;
-        if (int e = nd_reserve_lds(configured_w, reinterpret_cast<const void*>(wgrad_wino_kernel), WW_LDS, "nd_conv3x3_wgrad (Winograd domain)")) return e;
+        if (int e = nd_reserve_lds(configured_w, reinterpret_cast<const void*>(wgrad_wino_kernel<LK>), WW_LDS, "nd_conv3x3_wgrad (Winograd domain)")) return e;
         hipStream_t st = (hipStream_t)stream;
         if (w.wide) {
             static nd_device_once configured_w8;
-            if (int e = nd_reserve_lds(configured_w8, reinterpret_cast<const void*>(wgrad_wino8_kernel), W8_LDS, "nd_conv3x3_wgrad (Winograd domain, eight waves)")) return e;
-            hipLaunchKernelGGL(wgrad_wino8_kernel, dim3((unsigned)(w.n_co * w.n_ci * w.S)), dim3(512), W8_LDS, st, w);
+            if (int e = nd_reserve_lds(configured_w8, reinterpret_cast<const void*>(wgrad_wino8_kernel<LK>), W8_LDS, "nd_conv3x3_wgrad (Winograd domain, eight waves)")) return e;
+            hipLaunchKernelGGL(wgrad_wino8_kernel<LK>, dim3((unsigned)(w.n_co * w.n_ci * w.S)), dim3(512), W8_LDS, st, w);
         } else
-        hipLaunchKernelGGL(wgrad_wino_kernel, dim3((unsigned)(w.n_co * w.n_ci * w.S)), dim3(256), WW_LDS, st, w);
+        hipLaunchKernelGGL(wgrad_wino_kernel<LK>, dim3((unsigned)(w.n_co * w.n_ci * w.S)), dim3(256), WW_LDS, st, w);
         if (int e = nd_launch_status("nd_conv3x3_wgrad_nhwc_f32 (Winograd domain)")) return e;
         const int n_main = cout * (w.ciP / 32), n_bias = dbias ? (cout + 383) / 384 : 0;
         if (w.S > 1 && n_main >= 512) {
@@ -1085,6 +1098,7 @@ static int wgrad_run(const float* x, int ldx, int c0, const float* x1, int ldx1,
     WgradArgs a;
     plan(B, H, W, cin, cout, a);
     a.x = x; a.dy = dy; a.ws = workspace; a.ldx = ldx; a.ldy = ldy;
+    ND_REQUIRE(LK == (lk0 != 0), ND_E_STATE, "nd_conv3x3_wgrad: internal: the nine-tap instance applies LeakyReLU iff it is the LK one");
     a.wsb = dbias ? workspace + (size_t)a.S * 9 * a.n_co * CB * a.n_ci * CB : nullptr;
     {   // the interior-tile path addresses both tensors with 32-bit byte offsets
         const long xb = (long)B * H * W * ldx * 4, dyb = (long)B * H * W * ldy * 4;
@@ -1096,14 +1110,20 @@ static int wgrad_run(const float* x, int ldx, int c0, const float* x1, int ldx1,
     ND_REQUIRE(wgs < (1L << 31), ND_E_SHAPE, "nd_conv3x3_wgrad: grid too large");
     const size_t lds = (size_t)(WG_TILE * TILE_H + HALO * HALO_H) * CB * sizeof(float);
     static nd_device_once configured;
-    if (int e = nd_reserve_lds(configured, reinterpret_cast<const void*>(wgrad_kernel), lds, "nd_conv3x3_wgrad")) return e;
+    if (int e = nd_reserve_lds(configured, reinterpret_cast<const void*>(wgrad_kernel<LK>), lds, "nd_conv3x3_wgrad")) return e;
     hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(wgrad_kernel, dim3((unsigned)wgs), dim3(256), lds, st, a);
+    hipLaunchKernelGGL(wgrad_kernel<LK>, dim3((unsigned)wgs), dim3(256), lds, st, a);
     if (int e = nd_launch_status("nd_conv3x3_wgrad_nhwc_f32")) return e;
     const size_t total = (size_t)a.n_co * CB * (9 * a.n_ci * CB + 1);
     const int blocks = (int)((total + 255) / 256 < 4096 ? (total + 255) / 256 : 4096);
-    hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(blocks), dim3(256), 0, st, workspace, a.wsb, dw_oihw, dbias, a.S, cin, cout, a.n_co * CB, a.n_ci * CB);
+    hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(blocks), dim3(256), 0, st, workspace, a.wsb, dw_oihw, dbias, a.S, cin, cout, a.n_co * CB, a.n_ci * CB,
+                       dw_cin, dw_ci0);
     return nd_launch_status("nd_conv3x3_wgrad_nhwc_f32 (reduce)");
+}
+
+static int wgrad_run(const float* x, int ldx, int c0, const float* x1, int ldx1, const float* dy, int ldy, float* dw_oihw, float* dbias, float* workspace,
+                     int B, int H, int W, int cin, int cout, void* stream) {
+    return wgrad_run_t<false>(x, ldx, c0, x1, ldx1, dy, ldy, dw_oihw, dbias, workspace, B, H, W, cin, cout, stream, 0, 0, 0, 0);
 }
 
 extern "C" int nd_conv3x3_wgrad_nhwc_f32(const float* x, int ldx, const float* dy, int ldy, float* dw_oihw, float* dbias, float* workspace,
@@ -1117,4 +1137,31 @@ extern "C" int nd_conv3x3_wgrad_cat_nhwc_f32(const float* x0, int ldx0, int c0, 
                "nd_conv3x3_wgrad_cat_nhwc_f32: two sources of whole 32-channel blocks (c0=%d, c1=%d)", c0, c1);
     ND_REQUIRE((long)H * W * ldx1 * 4 < (1L << 30), ND_E_SHAPE, "nd_conv3x3_wgrad_cat_nhwc_f32: second source too large for 32-bit offsets within a sample");
     return wgrad_run(x0, ldx0, c0, x1, ldx1, dy, ldy, dw_oihw, dbias, workspace, B, H, W, c0 + c1, cout, stream);
+}
+
+// LSID (SID_arch.py:105-175): the input of every 3x3 convolution but conv1_1 is LeakyReLU(0.2) of a raw pre-activation that the training forward keeps
+// (noisediff_amd/lsid_train.py); these read the raw tensor and apply the activation while staging it -- no activated copy.  Same forms, same split,
+// same summation order as the plain entries.
+extern "C" int nd_conv3x3_wgrad_leaky_nhwc_f32(const float* x, int ldx, const float* dy, int ldy, float* dw_oihw, float* dbias, float* workspace,
+                                               int B, int H, int W, int cin, int cout, void* stream) {
+    return wgrad_run_t<true>(x, ldx, cin, nullptr, 0, dy, ldy, dw_oihw, dbias, workspace, B, H, W, cin, cout, stream, 1, 0, 0, 0);
+}
+
+extern "C" int nd_conv3x3_wgrad_cat_leaky_second_nhwc_f32(const float* x0, int ldx0, int c0, const float* x1, int ldx1, int c1, const float* dy, int ldy,
+                                                          float* dw_oihw, float* dbias, float* workspace, int B, int H, int W, int cout, void* stream) {
+    ND_REQUIRE(x0 && x1 && c0 > 0 && c1 > 0 && c0 % 4 == 0 && c1 % 4 == 0 && ldx0 >= c0 && ldx1 >= c1 && ldx1 % 4 == 0 && nd_aligned16(x1), ND_E_SHAPE,
+               "nd_conv3x3_wgrad_cat_leaky_second_nhwc_f32: c0=%d, c1=%d must be multiples of 4", c0, c1);
+    const int cin = c0 + c1;
+    if (c0 % 32 == 0 && c1 % 32 == 0 && ww_takes(B, H, W, cin, cout) && (long)H * W * ldx0 * 4 < (1L << 30) && (long)H * W * ldx1 * 4 < (1L << 30) &&
+        (long)H * W * ldy * 4 < (1L << 30))                             // one Winograd-domain gradient over both sources (a cin block never straddles them)
+        return wgrad_run_t<true>(x0, ldx0, c0, x1, ldx1, dy, ldy, dw_oihw, dbias, workspace, B, H, W, cin, cout, stream, 0, 1, 0, 0);
+    // nine taps: one gradient per source into its columns of dw; the bias gradient with the first
+    if (int e = wgrad_run_t<false>(x0, ldx0, c0, nullptr, 0, dy, ldy, dw_oihw, dbias, workspace, B, H, W, c0, cout, stream, 0, 0, cin, 0)) return e;
+    return wgrad_run_t<true>(x1, ldx1, c1, nullptr, 0, dy, ldy, dw_oihw, nullptr, workspace, B, H, W, c1, cout, stream, 1, 0, cin, c0);
+}
+
+extern "C" int64_t nd_conv3x3_wgrad_cat_workspace_floats(int B, int H, int W, int c0, int c1, int cout) {
+    const int64_t a = nd_conv3x3_wgrad_workspace_floats(B, H, W, c0 + c1, cout), b = nd_conv3x3_wgrad_workspace_floats(B, H, W, c0, cout),
+                  c = nd_conv3x3_wgrad_workspace_floats(B, H, W, c1, cout);
+    return a > b ? (a > c ? a : c) : (b > c ? b : c);
 }

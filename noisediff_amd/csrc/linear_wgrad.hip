@@ -20,8 +20,12 @@ struct LwArgs {
     const float* x; const float* dy; float* ws; float* wsb;
     int ldx, ldy, cin, cout, n_co, n_ci, S, want_bias;
     long N, chunks;
+    int uh, uw, sh, sw, uc;          // UNS: dY is d_up (B, sh, sw, uc) read as the pixel unshuffle of a (uh, uw) token grid, K order (p1 p2 c), zero past the crop
 };
 
+// LKX: LeakyReLU(0.2) on X as it is staged (LSID's conv10 and ConvTranspose2d inputs are activations of raw pre-activations, SID_arch.py:134-172).
+// UNS: the ConvTranspose2d(2, s=2) weight gradient -- dY[p][(p1 p2 c)] = d_up[b][2y + p1][2x + p2][c], 0 where the forward cropped (:135).
+template <bool LKX, bool UNS>
 __global__ __launch_bounds__(256, 2) void linear_wgrad_kernel(const LwArgs a) {
     __shared__ __attribute__((aligned(16))) float dYs[LW_PK * LW_CB];
     __shared__ __attribute__((aligned(16))) float Xs[LW_PK * LW_CB];
@@ -42,24 +46,40 @@ __global__ __launch_bounds__(256, 2) void linear_wgrad_kernel(const LwArgs a) {
     const float* dyb = a.dy + (cy_ok ? cy : 0);
     const float* xb = a.x + (cx_ok ? cx : 0);
     const f32x4 zero = {0, 0, 0, 0};
+    int u_py = 0, u_px = 0;                                              // UNS: this thread's quad of (p1 p2 c) lies in one (p1, p2) slot
+    if constexpr (UNS) {
+        const int pp = cy_ok ? cy / a.uc : 0;
+        u_py = pp >> 1;  u_px = pp & 1;
+        dyb = a.dy + (cy_ok ? cy - pp * a.uc : 0);
+    }
 
     for (long chunk = s; chunk < a.chunks; chunk += a.S) {
         const long p0 = chunk * LW_PK;
         __syncthreads();                                                 // the previous chunk's operands have been consumed
         {   // every load unconditional (clamped row, select afterwards), all 16 in flight before the first LDS write
             f32x4 vy[8], vx[8];
+            bool uin[8];
 #pragma unroll
             for (int j = 0; j < 8; ++j) {
                 const long p = min(p0 + r0 + 16 * j, a.N - 1);
-                vy[j] = nd_ld4(dyb + (size_t)p * a.ldy);
+                if constexpr (UNS) {
+                    const long hw = (long)a.uh * a.uw, b = p / hw;
+                    const int rem = (int)(p - b * hw), y = rem / a.uw, x = rem - y * a.uw;
+                    const int Y = 2 * y + u_py, X = 2 * x + u_px;
+                    uin[j] = Y < a.sh && X < a.sw;
+                    vy[j] = nd_ld4(dyb + (size_t)((b * a.sh + (uin[j] ? Y : 0)) * a.sw + (uin[j] ? X : 0)) * a.ldy);
+                } else {
+                    uin[j] = true;
+                    vy[j] = nd_ld4(dyb + (size_t)p * a.ldy);
+                }
                 vx[j] = nd_ld4(xb + (size_t)p * a.ldx);
             }
 #pragma unroll
             for (int j = 0; j < 8; ++j) {
                 const int r = r0 + 16 * j;
                 const bool in = p0 + r < a.N;
-                nd_st4(dYs + r * LW_CB + 4 * q, in && cy_ok ? vy[j] : zero);
-                nd_st4(Xs + r * LW_CB + 4 * q, in && cx_ok ? vx[j] : zero);
+                nd_st4(dYs + r * LW_CB + 4 * q, in && cy_ok && uin[j] ? vy[j] : zero);
+                nd_st4(Xs + r * LW_CB + 4 * q, in && cx_ok ? (LKX ? nd_leaky4(vx[j]) : vx[j]) : zero);
             }
         }
         __syncthreads();
@@ -90,7 +110,7 @@ __global__ __launch_bounds__(256, 2) void linear_wgrad_kernel(const LwArgs a) {
 // 32-thread stripes add the slots s = stripe, stripe + 8, ... (eight loads in flight each) and the stripes then meet in stripe order:
 // a fixed order, eight times shallower than one thread per element (which made this pass slower than the gradient kernel itself).
 __global__ __launch_bounds__(256) void linear_wgrad_reduce_kernel(const float* __restrict__ ws, const float* __restrict__ wsb, float* __restrict__ dw,
-                                                                  float* __restrict__ db, int S, int cin, int cout, int coP, int ciP) {
+                                                                  float* __restrict__ db, int S, int cin, int cout, int coP, int ciP, int uc = 0) {
     __shared__ float red[8][32];
     const size_t block = (size_t)coP * ciP, total = block + coP;         // the bias partials follow the weight partials element-wise
     const int o = threadIdx.x & 31, stripe = threadIdx.x >> 5;
@@ -122,7 +142,12 @@ __global__ __launch_bounds__(256) void linear_wgrad_reduce_kernel(const float* _
                 if (db && co < cout) db[co] = sum;
             } else {
                 const int ci = (int)(j % ciP), co = (int)(j / ciP);
-                if (co < cout && ci < cin) dw[(size_t)co * cin + ci] = sum;
+                if (co < cout && ci < cin) {
+                    if (uc > 0) {                                        // ConvTranspose2d: row co = (p1 p2 c) -> torch's (cin, cout, 2, 2)
+                        const int pp = co / uc, c = co - pp * uc;
+                        dw[((size_t)ci * uc + c) * 4 + pp] = sum;
+                    } else dw[(size_t)co * cin + ci] = sum;
+                }
             }
         }
     }
@@ -148,25 +173,57 @@ extern "C" int64_t nd_linear_wgrad_workspace_floats(int64_t N, int cin, int cout
     return (int64_t)a.S * a.n_co * LW_CB * (a.n_ci * LW_CB + 1);
 }
 
-extern "C" int nd_linear_wgrad_f32(const float* x, int ldx, const float* dy, int ldy, float* dw, float* dbias, float* workspace,
-                                   int64_t N, int cin, int cout, void* stream) {
+template <bool LKX, bool UNS>
+static int lw_run(const float* x, int ldx, const float* dy, int ldy, float* dw, float* dbias, float* workspace, int64_t N, int cin, int cout, void* stream,
+                  const LwArgs* uns) {
     ND_REQUIRE(x && dy && dw && workspace, ND_E_BADARG, "nd_linear_wgrad: null pointer");
     ND_REQUIRE(N > 0 && cin > 0 && cout > 0, ND_E_BADARG, "nd_linear_wgrad: non-positive size");
-    ND_REQUIRE(cin % 4 == 0 && cout % 4 == 0 && ldx >= cin && ldy >= cout && ldx % 4 == 0 && ldy % 4 == 0, ND_E_SHAPE,
+    ND_REQUIRE(cin % 4 == 0 && cout % 4 == 0 && ldx >= cin && ldy >= (UNS ? uns->uc : cout) && ldx % 4 == 0 && ldy % 4 == 0, ND_E_SHAPE,
                "nd_linear_wgrad: cin=%d, cout=%d and the token strides must be multiples of 4", cin, cout);
     ND_REQUIRE(nd_aligned16(x) && nd_aligned16(dy) && nd_aligned16(workspace), ND_E_ALIGN, "nd_linear_wgrad: x, dy and the workspace must be 16-byte aligned");
     LwArgs a;
     lw_plan(N, cin, cout, a);
     a.x = x; a.dy = dy; a.ldx = ldx; a.ldy = ldy; a.want_bias = dbias != nullptr;
+    a.uh = a.uw = a.sh = a.sw = a.uc = 0;
+    if (uns) { a.uh = uns->uh; a.uw = uns->uw; a.sh = uns->sh; a.sw = uns->sw; a.uc = uns->uc; }
     a.ws = workspace;
     a.wsb = workspace + (size_t)a.S * a.n_co * LW_CB * a.n_ci * LW_CB;
     const long wgs = (long)a.n_co * a.n_ci * a.S;
     ND_REQUIRE(wgs < (1L << 31), ND_E_SHAPE, "nd_linear_wgrad: grid too large");
     hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(linear_wgrad_kernel, dim3((unsigned)wgs), dim3(256), 0, st, a);
+    hipLaunchKernelGGL((linear_wgrad_kernel<LKX, UNS>), dim3((unsigned)wgs), dim3(256), 0, st, a);
     if (int e = nd_launch_status("nd_linear_wgrad_f32")) return e;
     const size_t total = (size_t)a.n_co * LW_CB * (a.n_ci * LW_CB + 1);
     const int blocks = (int)((total + 31) / 32 < 8192 ? (total + 31) / 32 : 8192);
-    hipLaunchKernelGGL(linear_wgrad_reduce_kernel, dim3(blocks), dim3(256), 0, st, a.ws, a.wsb, dw, dbias, a.S, cin, cout, a.n_co * LW_CB, a.n_ci * LW_CB);
+    hipLaunchKernelGGL(linear_wgrad_reduce_kernel, dim3(blocks), dim3(256), 0, st, a.ws, a.wsb, dw, dbias, a.S, cin, cout, a.n_co * LW_CB, a.n_ci * LW_CB,
+                       a.uc);
     return nd_launch_status("nd_linear_wgrad_f32 (reduce)");
+}
+
+extern "C" int nd_linear_wgrad_f32(const float* x, int ldx, const float* dy, int ldy, float* dw, float* dbias, float* workspace,
+                                   int64_t N, int cin, int cout, void* stream) {
+    return lw_run<false, false>(x, ldx, dy, ldy, dw, dbias, workspace, N, cin, cout, stream, nullptr);
+}
+
+extern "C" int nd_linear_wgrad_leaky_f32(const float* x, int ldx, const float* dy, int ldy, float* dw, float* dbias, float* workspace,
+                                         int64_t N, int cin, int cout, void* stream) {
+    return lw_run<true, false>(x, ldx, dy, ldy, dw, dbias, workspace, N, cin, cout, stream, nullptr);
+}
+
+extern "C" int64_t nd_convt2x2_wgrad_workspace_floats(int B, int h, int w, int cin, int cout) {
+    if (B <= 0 || h <= 0 || w <= 0) return -1;
+    return nd_linear_wgrad_workspace_floats((int64_t)B * h * w, cin, 4 * cout);
+}
+
+extern "C" int nd_convt2x2_wgrad_leaky_f32(const float* x, int ldx, const float* d_up, int ld_up, float* dw, float* workspace, int B, int h, int w,
+                                           int cin, int cout, int up_h, int up_w, void* stream) {
+    ND_REQUIRE(B > 0 && h > 0 && w > 0 && up_h > 0 && up_w > 0 && up_h <= 2 * h && up_w <= 2 * w, ND_E_SHAPE,
+               "nd_convt2x2_wgrad: the (%d, %d) output must lie within twice the (%d, %d) input", up_h, up_w, h, w);
+    ND_REQUIRE(cout > 0 && cout % 4 == 0 && ld_up >= cout && ld_up % 4 == 0 && nd_aligned16(d_up), ND_E_SHAPE,
+               "nd_convt2x2_wgrad: cout=%d and the d_up pixel stride must be multiples of 4", cout);
+    ND_REQUIRE((long)B * up_h * up_w * ld_up < (1L << 31), ND_E_SHAPE, "nd_convt2x2_wgrad: d_up too large");
+    LwArgs u;
+    u.uh = h; u.uw = w; u.sh = up_h; u.sw = up_w; u.uc = cout;
+    // the GEMM's rows are the 4 cout (p1 p2 c) unshuffled gradient columns, its columns the cin input channels
+    return lw_run<true, true>(x, ldx, d_up, ld_up, dw, nullptr, workspace, (int64_t)B * h * w, cin, 4 * cout, stream, &u);
 }

@@ -23,6 +23,7 @@ constexpr int LDA = KC + 4;
 struct PwArgs {
     nd_pointwise d;
     int m_tiles, n_tiles, coutP, cinP, total_wg;
+    int uns_h, uns_w;      // unshuffle: the source image's size when it is smaller than (2 H, 2 W) -- rows / columns past it read as zeros (0: none cropped)
 };
 
 // Epilogue shared by both kernels: accumulators -> LDS -> (bias, activation, residuals, fused ResnetBlock tail) -> global.
@@ -758,7 +759,8 @@ __global__ __launch_bounds__(256) void pointwise_kernel(const PwArgs a) {
 
     const int quad = tid & 15, prow = tid >> 4;
     const int Cs = s.unshuffle ? (s.c0 >> 2) : 1;
-    const int Hs2 = 2 * (HW / max(W, 1));                 // source height for the unshuffle addressing
+    const int Hs2 = a.uns_h > 0 ? a.uns_h : 2 * (HW / max(W, 1));     // source height / width for the unshuffle addressing
+    const int Ws2 = a.uns_w > 0 ? a.uns_w : 2 * W;
 
     for (int cb = 0; cb < a.cinP; cb += KC) {
         const int ng = min(8, (a.cinP - cb) >> 3);
@@ -794,13 +796,17 @@ __global__ __launch_bounds__(256) void pointwise_kernel(const PwArgs a) {
             }
             f32x4 raw[STAGE_IT];
             float rmean[STAGE_IT], rrstd[STAGE_IT];
+            bool uin[STAGE_IT];
 #pragma unroll
             for (int it = 0; it < STAGE_IT; ++it) {
                 const int p = min(p0 + prow + it * 16, HW - 1);
                 size_t pix = (size_t)b * HW + p;
+                uin[it] = true;
                 if (s.unshuffle) {
                     const int y = p / W, x = p - y * W;
-                    pix = ((size_t)b * Hs2 + 2 * y + py) * (2 * W) + 2 * x + px;
+                    const int sy = 2 * y + py, sx = 2 * x + px;
+                    uin[it] = sy < Hs2 && sx < Ws2;
+                    pix = ((size_t)b * Hs2 + (uin[it] ? sy : 0)) * Ws2 + (uin[it] ? sx : 0);
                 }
                 raw[it] = nd_ld4(base + pix * ld + cc);
                 if (MODE == ND_PRO_LAYERNORM && s.rowstats) {
@@ -832,7 +838,7 @@ __global__ __launch_bounds__(256) void pointwise_kernel(const PwArgs a) {
                 else if (MODE == ND_PRO_AFFINE_SILU) v = nd_silu4((v - tM) * tA + tD);
                 else if (MODE == ND_PRO_LEAKY) v = nd_leaky4(v);
                 const f32x4 zero = {0, 0, 0, 0};
-                v = (cvalid && p0 + r < HW) ? v : zero;
+                v = (cvalid && p0 + r < HW && uin[it]) ? v : zero;
                 nd_st4(&As[r * LDA + quad * 4], v);
             }
         }
@@ -1113,7 +1119,7 @@ bool pw_split_takes(const nd_pointwise* d) {
            (s.c1 == 0 || (s.c0 % SKC == 0 && nd_aligned16(s.p1)));
 }
 
-int pw_run(const nd_pointwise* d, void* stream, bool split = false) {
+int pw_run(const nd_pointwise* d, void* stream, bool split = false, int uns_h = 0, int uns_w = 0) {
     ND_REQUIRE(d, ND_E_BADARG, "nd_pointwise: null descriptor");
     const nd_src& s = d->src;
     ND_REQUIRE(s.p0 && d->weight && d->out, ND_E_BADARG, "nd_pointwise: null tensor pointer");
@@ -1154,8 +1160,12 @@ int pw_run(const nd_pointwise* d, void* stream, bool split = false) {
     ND_REQUIRE(!d->gn_t || (d->gn_mad && d->ldt >= d->cout), ND_E_BADARG, "nd_pointwise: gn_t needs gn_mad and ldt >= cout");
     ND_REQUIRE(d->act >= ND_ACT_NONE && d->act <= ND_ACT_SILU, ND_E_BADARG, "nd_pointwise: bad act");
 
+    if (uns_h > 0 || uns_w > 0)
+        ND_REQUIRE(s.unshuffle && uns_h > 0 && uns_w > 0 && uns_h <= 2 * (d->HW / d->W) && uns_w <= 2 * d->W, ND_E_SHAPE,
+                   "nd_pointwise_gemm_unshuffle_crop: source (%d, %d) must lie within twice the (%d, %d) output", uns_h, uns_w, d->HW / d->W, d->W);
     PwArgs a;
     a.d = *d;
+    a.uns_h = uns_h;  a.uns_w = uns_w;
     if (split) {
         ND_REQUIRE(pw_split_takes(d), ND_E_SHAPE, "nd_pointwise_gemm_split: %d -> %d is not a layer of the split kernel (cin %% 32, cin >= 64, cout %% 128, plain "
                    "addressing, LayerNorm with rowstats, concat on a 32-channel boundary: nd_pointwise_gemm_split_takes)", d->cin, d->cout);
@@ -1219,6 +1229,13 @@ int pw_run(const nd_pointwise* d, void* stream, bool split = false) {
 }  // namespace
 
 extern "C" int nd_pointwise_gemm_nhwc_f32(const nd_pointwise* d, void* stream) { return pw_run(d, stream); }
+
+// The data gradient of ConvTranspose2d(2, s=2) followed by the crop (SID_arch.py:134-158): d->src.unshuffle = 1 reads d_up (src_h, src_w, c0/4) as the
+// pixel unshuffle of a (HW / W, W) grid, and the rows / columns the forward cropped away (src_h < 2 H, src_w < 2 W) read as zeros.
+extern "C" int nd_pointwise_gemm_unshuffle_crop_nhwc_f32(const nd_pointwise* d, int src_h, int src_w, void* stream) {
+    ND_REQUIRE(d && d->W > 0 && d->src.unshuffle && src_h > 0 && src_w > 0, ND_E_BADARG, "nd_pointwise_gemm_unshuffle_crop: needs src.unshuffle and a source size");
+    return pw_run(d, stream, false, src_h, src_w);
+}
 
 // The same operator with the products on the bf16 matrix pipe at full fp32 significand (pointwise_split_kernel above); `weight` is an
 // nd_pack_pointwise_weight_split packing.  Same prologues, epilogues and errors; takes the layers nd_pointwise_gemm_split_takes names.

@@ -1,0 +1,376 @@
+"""``TrainableLSID``: the reference's denoiser (models/archs/SID_arch.py:49-175) trained on MI355X -- the fourth workflow of the reference
+(train_denoising.py, script.sh:17: LSID, L1 loss, Adam) without the reference tree.
+
+    net = noisediff_amd.TrainableLSID().cuda().hip()
+    opt = noisediff_amd.train.Adam(net.parameters(), lr=1e-4)
+    loss = torch.nn.functional.l1_loss(net(noisy), clean); loss.backward(); opt.step()
+    noisediff_amd.LSID(None).load_state_dict(net.state_dict())        # the HIP inference path takes the trained weights as they are
+
+Parameters are registered under the reference's names and shapes (spec.lsid_param_spec) with its init, so ``state_dict()`` loads strictly into
+``noisediff_amd.LSID`` and into the reference class.  Without ``.hip()`` the forward is plain differentiable PyTorch (CPU or GPU): the restatement
+tests/test_lsid_train.py pins against the reference's loss and gradients.  With ``.hip()`` the whole network is ONE torch.autograd.Function
+(``_LsidFunction``) over the HIP library, forward and backward:
+
+  forward   the launches of lsid._LsidPlan._record: every convolution stores its RAW pre-activation, the consumers apply LeakyReLU(0.2) in their
+            prologue (ND_PRO_LEAKY / ND_PRO_LEAKY_SECOND), the ceil-mode max-pools run on raw values (max commutes with the activation), each
+            ConvTranspose2d(2, s=2) is one pointwise GEMM with a pixel-shuffle store that also crops.  Saved: the raw tensors below, nothing activated.
+  backward  in reverse: conv10's weight gradient (nd_linear_wgrad_leaky_f32) and data gradient (pointwise GEMM); per LeakyReLU the gradient join
+            nd_leaky_grad_join_f32 (direct gradient + max-pool scatter, times the slope); per 3x3 convolution the weight gradient with the activation
+            applied on load (nd_conv3x3_wgrad_leaky / _cat_leaky_second) and the data gradient as the forward kernels on dgrad-packed weights; per
+            ConvTranspose the weight gradient nd_convt2x2_wgrad_leaky_f32 and the data gradient as a pointwise GEMM reading d_up through a cropped
+            pixel unshuffle (nd_pointwise_gemm_unshuffle_crop_nhwc_f32).  The input gradient is not built (out of scope: nothing trains the image).
+
+Every launch goes on torch's CURRENT stream, every buffer (packed weights, saved tensors, workspaces) comes from torch's caching allocator on that
+stream and is owned by the autograd context: nothing is freed while a queued launch may still read it, and a whole step (forward, loss, backward,
+train.Adam) captures into one torch.cuda.graph without parallel branches.  The weights are packed per forward (and per backward for the data
+gradients) from the parameters as they are: no cache that an optimizer step could leave stale.
+"""
+from __future__ import annotations
+
+import ctypes as C
+from typing import Dict, List, Optional, Tuple
+
+import torch
+import torch.nn.functional as F
+from torch import nn
+from torch.autograd.function import once_differentiable
+
+from . import _lib as L
+from . import synth
+from .spec import LSID_STAGES, lsid_param_spec
+
+SLOPE = 0.2
+# F(4x4,3x3) Winograd kernels where they take the layer (lsid.py's rule), for the forward / the data-gradient convolutions; False: F(2x2,3x3) there.
+# Measured at B = 4, 256 x 256 against float64 (max |g - g64| / max |g64| over the parameters): F(4x4) forward 1.8e-4, F(2x2) forward 5.2e-5 --
+# PyTorch's own fp32 path 6.3e-5; the data-gradient form changes none of these figures.  The forward is what the saved activations carry into
+# every weight gradient, so training keeps it on F(2x2).
+WINO4_FORWARD, WINO4_DGRAD = False, True
+PARAM_NAMES: Tuple[str, ...] = tuple(p.name for p in lsid_param_spec())
+
+
+# --------------------------------------------------------------------------------------------------------- the PyTorch restatement
+def lsid_forward_torch(p: Dict[str, torch.Tensor], x: torch.Tensor) -> torch.Tensor:
+    """LSID.forward (SID_arch.py:105-175) as functional PyTorch over the parameter table."""
+    act = lambda t: F.leaky_relu(t, SLOPE)
+    conv = lambda n, t, pad=1: F.conv2d(t, p[n + ".weight"], p[n + ".bias"], padding=pad)
+    skips = []
+    for i in range(1, 6):
+        x = act(conv(f"conv{i}_2", act(conv(f"conv{i}_1", x))))
+        if i < 5:
+            skips.append(x)
+            x = F.max_pool2d(x, 2, 2, ceil_mode=True)
+    for i in range(6, 10):
+        skip = skips.pop()
+        x = F.conv_transpose2d(x, p[f"up{i}.weight"], stride=2)
+        x = torch.cat((x[:, :, :skip.shape[2], :skip.shape[3]], skip), 1)
+        x = act(conv(f"conv{i}_2", act(conv(f"conv{i}_1", x))))
+    return conv("conv10", x, 0)
+
+
+# --------------------------------------------------------------------------------------------------------- HIP launches
+def _stream(dev: torch.device) -> C.c_void_p:
+    return C.c_void_p(torch._C._cuda_getCurrentRawStream(dev.index if dev.index is not None else torch.cuda.current_device()))
+
+
+class _Launcher:
+    """Buffers and launches of one forward or backward pass on the current stream; ``keep`` owns every buffer a launch reads or writes."""
+
+    def __init__(self, dev: torch.device):
+        self.lib = L.load()
+        self.dev = dev
+        self.st = _stream(dev)
+        self.keep: List[object] = []
+
+    def empty(self, *shape) -> torch.Tensor:
+        t = torch.empty(*shape, dtype=torch.float32, device=self.dev)
+        self.keep.append(t)
+        return t
+
+    # ---- weight packings
+    def pack_pw(self, m: torch.Tensor, cin: int, cout: int, unshuffle_c: int = 0) -> torch.Tensor:
+        out = self.empty(int(self.lib.nd_pack_pointwise_weight_floats(cin, cout)))
+        self.keep.append(m)
+        L.call("nd_pack_pointwise_weight", m.data_ptr(), out.data_ptr(), cin, cout, unshuffle_c, self.st)
+        return out
+
+    def pack_pw_t(self, w: torch.Tensor, cin: int, cout: int) -> torch.Tensor:
+        out = self.empty(int(self.lib.nd_pack_pointwise_weight_floats(cin, cout)))
+        L.call("nd_pack_pointwise_weight_t", w.data_ptr(), out.data_ptr(), cin, cout, self.st)
+        return out
+
+    @staticmethod
+    def conv_kind(B: int, h: int, w: int, cin: int, cout: int, c0: int, c1: int, ld: int, wino4: bool = True) -> str:
+        """The forward kernel of a 3x3 layer (lsid._LsidPlan._conv's rule): 'wino4', 'wino2', 'wino' or 'direct'."""
+        wino = h >= 16 and w >= 16
+        if (wino4 and wino and cin > 16 and cin % 4 == 0 and cout % 4 == 0 and w >= 32 and (w % 32 == 0 or w >= 96) and w <= 2048
+                and (c1 == 0 or c0 % 16 == 0) and B * h * w + w + 2 < (1 << 24) and (B * h * w + w + 2) * 4 * ld < (1 << 30) - (1 << 16)):
+            return "wino4"
+        if wino and (c1 == 0 or c0 % 32 == 0) and B * h * w < (1 << 24) and B * h * w * 4 * ld < (1 << 31):
+            return "wino2"
+        return "wino" if wino else "direct"
+
+    _PACK = {"wino4": "nd_pack_conv3x3_wino4_weight", "wino2": "nd_pack_conv3x3_wino_weight", "wino": "nd_pack_conv3x3_wino_weight",
+             "direct": "nd_pack_conv3x3_weight"}
+    _ENTRY = {"wino4": "nd_conv3x3_wino4_nhwc_f32", "wino2": "nd_conv3x3_wino2_nhwc_f32", "wino": "nd_conv3x3_wino_nhwc_f32",
+              "direct": "nd_conv3x3_nhwc_f32"}
+
+    def conv3x3(self, w_oihw: torch.Tensor, bias: Optional[torch.Tensor], src: L.Src, B: int, h: int, w: int, cin: int, cout: int,
+                dgrad: bool = False, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """One 3x3 convolution (``dgrad``: the data gradient of the layer whose forward weight is ``w_oihw``; cin / cout are the operator's)."""
+        kind = self.conv_kind(B, h, w, cin, cout, src.c0, src.c1, max(src.ld0, src.ld1), WINO4_DGRAD if dgrad else WINO4_FORWARD)
+        pack = self._PACK[kind]
+        wp = self.empty(int(getattr(self.lib, pack + "_floats")(cin, cout)))
+        L.call(pack + ("_dgrad" if dgrad else ""), w_oihw.data_ptr(), wp.data_ptr(), cin, cout, self.st)
+        if out is None:
+            out = self.empty(B, h, w, cout)
+        d = L.Conv3x3()
+        d.src, d.weight, d.out = src, wp.data_ptr(), out.data_ptr()
+        d.bias = bias.data_ptr() if bias is not None else None
+        d.B, d.H, d.W, d.cin, d.cout, d.ldo = B, h, w, cin, cout, cout
+        self.keep.append(d)
+        L.call(self._ENTRY[kind], C.byref(d), self.st)
+        return out
+
+    @staticmethod
+    def src(t: torch.Tensor, c: Optional[int] = None, ld: Optional[int] = None, t2: Optional[torch.Tensor] = None, mode: int = L.PRO_NONE,
+            offset: int = 0) -> L.Src:
+        s = L.Src()
+        s.p0, s.c0, s.ld0 = t.data_ptr() + 4 * offset, c or t.shape[-1], ld or t.shape[-1]
+        if t2 is not None:
+            s.p1, s.c1, s.ld1 = t2.data_ptr(), t2.shape[-1], t2.shape[-1]
+        s.mode = mode
+        return s
+
+    def pointwise(self, src: L.Src, wp: torch.Tensor, bias: Optional[torch.Tensor], out: torch.Tensor, B: int, HW: int, W: int, cin: int, cout: int,
+                  ldo: int, shuffle: Optional[Tuple[int, int, int]] = None, crop_src: Optional[Tuple[int, int]] = None) -> None:
+        d = L.Pointwise()
+        d.src, d.weight, d.out = src, wp.data_ptr(), out.data_ptr()
+        d.bias = bias.data_ptr() if bias is not None else None
+        d.B, d.HW, d.W, d.cin, d.cout, d.ldo = B, HW, W, cin, cout, ldo
+        if shuffle is not None:
+            d.shuffle_c, d.shuffle_h, d.shuffle_w = shuffle
+        self.keep.append(d)
+        if crop_src is not None:
+            L.call("nd_pointwise_gemm_unshuffle_crop_nhwc_f32", C.byref(d), crop_src[0], crop_src[1], self.st)
+        else:
+            L.call("nd_pointwise_gemm_nhwc_f32", C.byref(d), self.st)
+
+    def join(self, z: torch.Tensor, dz: torch.Tensor, d_direct: Optional[torch.Tensor], ld_direct: int, d_pool: Optional[torch.Tensor],
+             direct_offset: int = 0) -> torch.Tensor:
+        B, h, w, c = z.shape
+        L.call("nd_leaky_grad_join_f32", z.data_ptr(), dz.data_ptr(), d_direct.data_ptr() + 4 * direct_offset if d_direct is not None else None,
+               ld_direct, d_pool.data_ptr() if d_pool is not None else None, B, h, w, c, self.st)
+        return dz
+
+
+def _sizes(H: int, W: int) -> List[Tuple[int, int]]:
+    """Spatial size of each encoder stage: ceil-mode pooling halves with rounding up."""
+    out = [(H, W)]
+    for _ in range(4):
+        h, w = out[-1]
+        out.append(((h + 1) // 2, (w + 1) // 2))
+    return out
+
+
+def _lsid_hip_forward(P: Dict[str, torch.Tensor], x: torch.Tensor, saved: Dict[str, torch.Tensor], run: _Launcher) -> torch.Tensor:
+    """The forward launches (lsid._LsidPlan._record) on the current stream; fills ``saved`` with the raw tensors the backward reads."""
+    B, _, H, W = x.shape
+    sizes = _sizes(H, W)
+    xn = x.detach().to(torch.float32).contiguous()
+    run.keep.append(xn)
+    x8 = run.empty(B, H, W, 8)
+    L.call("nd_nchw_to_nhwc_pad_f32", xn.data_ptr(), x8.data_ptr(), B, 4, H, W, 8, run.st)
+    saved["x8"] = x8
+    w11 = P["conv1_1.weight"]
+    w11 = torch.cat((w11, torch.zeros(w11.shape[0], 4, 3, 3, dtype=w11.dtype, device=w11.device)), 1).contiguous()   # conv1_1: 4 input channels padded to 8
+    run.keep.append(w11)
+    cur, mode, cin = x8, L.PRO_NONE, 8
+    for i, c in enumerate(LSID_STAGES, start=1):
+        h, w = sizes[i - 1]
+        wi1 = w11 if i == 1 else P[f"conv{i}_1.weight"]
+        a = run.conv3x3(wi1, P[f"conv{i}_1.bias"], run.src(cur, mode=mode), B, h, w, cin, c)
+        z = run.conv3x3(P[f"conv{i}_2.weight"], P[f"conv{i}_2.bias"], run.src(a, mode=L.PRO_LEAKY), B, h, w, c, c)
+        saved[f"a{i}"], saved[f"z{i}"] = a, z
+        cur, mode, cin = z, L.PRO_LEAKY, c
+        if i < 5:
+            ph, pw = sizes[i]
+            p = run.empty(B, ph, pw, c)
+            L.call("nd_maxpool2x2_nhwc_f32", z.data_ptr(), p.data_ptr(), B, h, w, c, run.st)
+            saved[f"p{i}"] = p
+            cur = p
+    for j, c in zip(range(6, 10), reversed(LSID_STAGES[:-1])):
+        i = 10 - j                                           # the encoder stage of the skip
+        sh, sw = sizes[i - 1]
+        hp, wp_ = sizes[i]
+        wt = P[f"up{j}.weight"]                              # (cin, c, 2, 2) -> rows (p1 p2 c'), columns cin
+        m = wt.permute(2, 3, 1, 0).reshape(4 * c, cin).contiguous()
+        up = run.empty(B, sh, sw, c)
+        run.pointwise(run.src(cur, mode=L.PRO_LEAKY), run.pack_pw(m, cin, 4 * c), None, up, B, hp * wp_, wp_, cin, 4 * c, c, shuffle=(c, sh, sw))
+        a = run.conv3x3(P[f"conv{j}_1.weight"], P[f"conv{j}_1.bias"], run.src(up, t2=saved[f"z{i}"], mode=L.PRO_LEAKY_SECOND), B, sh, sw, 2 * c, c)
+        z = run.conv3x3(P[f"conv{j}_2.weight"], P[f"conv{j}_2.bias"], run.src(a, mode=L.PRO_LEAKY), B, sh, sw, c, c)
+        saved[f"u{j}"], saved[f"a{j}"], saved[f"z{j}"] = up, a, z
+        cur, cin = z, c
+    y = run.empty(B, H, W, 4)
+    w10 = P["conv10.weight"].reshape(4, cin).contiguous()
+    run.pointwise(run.src(cur, mode=L.PRO_LEAKY), run.pack_pw(w10, cin, 4), P["conv10.bias"], y, B, H * W, W, cin, 4, 4)
+    out = torch.empty(B, 4, H, W, dtype=torch.float32, device=x.device)
+    L.call("nd_nhwc_to_nchw_f32", y.data_ptr(), out.data_ptr(), B, 4, H, W, run.st)
+    return out
+
+
+def _lsid_hip_backward(P: Dict[str, torch.Tensor], saved: Dict[str, torch.Tensor], grad_out: torch.Tensor, run: _Launcher) -> Dict[str, torch.Tensor]:
+    """Weight and bias gradients of every parameter from the raw tensors of the forward, in reverse launch order."""
+    lib = run.lib
+    x8 = saved["x8"]
+    B, H, W, _ = x8.shape
+    sizes = _sizes(H, W)
+    G: Dict[str, torch.Tensor] = {}
+    g = grad_out.detach().to(torch.float32).contiguous()
+    run.keep.append(g)
+    dy = run.empty(B, H, W, 4)
+    L.call("nd_nchw_to_nhwc_f32", g.data_ptr(), dy.data_ptr(), B, 4, H, W, run.st)
+
+    def ws(n: int) -> torch.Tensor:
+        return run.empty(int(n))
+
+    def wgrad3(name: str, x: torch.Tensor, dz: torch.Tensor, cin: int, ldx: int, leaky: bool) -> None:
+        h, w, cout = dz.shape[1], dz.shape[2], dz.shape[3]
+        gw, gb = run.empty(cout, cin, 3, 3), run.empty(cout)
+        L.call("nd_conv3x3_wgrad_leaky_nhwc_f32" if leaky else "nd_conv3x3_wgrad_nhwc_f32", x.data_ptr(), ldx, dz.data_ptr(), cout, gw.data_ptr(),
+               gb.data_ptr(), ws(lib.nd_conv3x3_wgrad_workspace_floats(B, h, w, cin, cout)).data_ptr(), B, h, w, cin, cout, run.st)
+        G[name + ".weight"], G[name + ".bias"] = gw, gb
+
+    # ---- conv10 (1x1 on leaky(z9)): weight / bias gradient, then the gradient of leaky(z9)
+    c = LSID_STAGES[0]
+    N = B * H * W
+    gw, gb = run.empty(4, c), run.empty(4)
+    L.call("nd_linear_wgrad_leaky_f32", saved["z9"].data_ptr(), c, dy.data_ptr(), 4, gw.data_ptr(), gb.data_ptr(),
+           ws(lib.nd_linear_wgrad_workspace_floats(N, c, 4)).data_ptr(), N, c, 4, run.st)
+    G["conv10.weight"], G["conv10.bias"] = gw.reshape(4, c, 1, 1), gb
+    t = run.empty(B, H, W, c)
+    run.pointwise(run.src(dy), run.pack_pw_t(P["conv10.weight"].reshape(4, c).contiguous(), 4, c), None, t, B, H * W, W, 4, c, c)
+    dz = run.join(saved["z9"], t, t, c, None)
+    # ---- up path, last stage first
+    dcat: Dict[int, torch.Tensor] = {}
+    for j in range(9, 5, -1):
+        i = 10 - j
+        c = LSID_STAGES[i - 1]
+        cin = LSID_STAGES[i]
+        h, w = sizes[i - 1]
+        hp, wp_ = sizes[i]
+        a = saved[f"a{j}"]
+        wgrad3(f"conv{j}_2", a, dz, c, c, True)
+        t = run.conv3x3(P[f"conv{j}_2.weight"], None, run.src(dz), B, h, w, c, c, dgrad=True)
+        da = run.join(a, t, t, c, None)
+        gw, gb = run.empty(c, 2 * c, 3, 3), run.empty(c)
+        L.call("nd_conv3x3_wgrad_cat_leaky_second_nhwc_f32", saved[f"u{j}"].data_ptr(), c, c, saved[f"z{i}"].data_ptr(), c, c, da.data_ptr(), c,
+               gw.data_ptr(), gb.data_ptr(), ws(lib.nd_conv3x3_wgrad_cat_workspace_floats(B, h, w, c, c, c)).data_ptr(), B, h, w, c, run.st)
+        G[f"conv{j}_1.weight"], G[f"conv{j}_1.bias"] = gw, gb
+        dc = run.conv3x3(P[f"conv{j}_1.weight"], None, run.src(da), B, h, w, c, 2 * c, dgrad=True)     # [d up | d leaky(skip)]
+        dcat[i] = dc
+        # ConvTranspose2d(cin -> c) on leaky(z_prev) + crop: weight gradient, then the gradient of leaky(z_prev)
+        zp = saved[f"z{j - 1}"] if j > 6 else saved["z5"]
+        gw = run.empty(cin, c, 2, 2)
+        L.call("nd_convt2x2_wgrad_leaky_f32", zp.data_ptr(), cin, dc.data_ptr(), 2 * c, gw.data_ptr(),
+               ws(lib.nd_convt2x2_wgrad_workspace_floats(B, hp, wp_, cin, c)).data_ptr(), B, hp, wp_, cin, c, h, w, run.st)
+        G[f"up{j}.weight"] = gw
+        wt = P[f"up{j}.weight"].reshape(cin, 4 * c).contiguous()
+        t = run.empty(B, hp, wp_, cin)
+        src = run.src(dc, c=4 * c, ld=2 * c)
+        src.unshuffle = 1
+        run.pointwise(src, run.pack_pw(wt, 4 * c, cin, unshuffle_c=c), None, t, B, hp * wp_, wp_, 4 * c, cin, cin, crop_src=(h, w))
+        dz = run.join(zp, t, t, cin, None)
+    # ---- down path, deepest stage first; dz is the gradient of z5
+    d_pool: Optional[torch.Tensor] = None
+    for i in range(5, 0, -1):
+        c = LSID_STAGES[i - 1]
+        h, w = sizes[i - 1]
+        if i < 5:                                            # skip half of the concat convolution's data gradient + the pooled gradient
+            dz = run.join(saved[f"z{i}"], run.empty(B, h, w, c), dcat[i], 2 * c, d_pool, direct_offset=c)
+        a = saved[f"a{i}"]
+        wgrad3(f"conv{i}_2", a, dz, c, c, True)
+        t = run.conv3x3(P[f"conv{i}_2.weight"], None, run.src(dz), B, h, w, c, c, dgrad=True)
+        da = run.join(a, t, t, c, None)
+        if i > 1:
+            cprev = LSID_STAGES[i - 2]
+            wgrad3(f"conv{i}_1", saved[f"p{i - 1}"], da, cprev, cprev, True)
+            d_pool = run.conv3x3(P[f"conv{i}_1.weight"], None, run.src(da), B, h, w, c, cprev, dgrad=True)
+        else:
+            wgrad3("conv1_1", x8, da, 4, 8, False)          # the image itself: no activation, 4 of the 8 staged channels
+    return G
+
+
+class _LsidFunction(torch.autograd.Function):
+    """The whole LSID forward and backward on libnoisediff_hip; inputs (x, *parameters in PARAM_NAMES order)."""
+
+    @staticmethod
+    def forward(ctx, x, *params):
+        P = dict(zip(PARAM_NAMES, (p.detach() for p in params)))
+        run = _Launcher(x.device)
+        saved: Dict[str, torch.Tensor] = {}
+        with torch.cuda.device(x.device):
+            out = _lsid_hip_forward(P, x, saved, run)
+        ctx.saved = saved                                    # raw tensors only; the packed weights and staging buffers are dropped with ``run``
+        ctx.save_for_backward(*params)                       # (version-checked: an optimizer step between forward and backward raises)
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_out):
+        params = ctx.saved_tensors
+        P = dict(zip(PARAM_NAMES, (p.detach() for p in params)))
+        run = _Launcher(grad_out.device)
+        with torch.cuda.device(grad_out.device):
+            G = _lsid_hip_backward(P, ctx.saved, grad_out, run)
+        ctx.saved = None
+        return (None,) + tuple(G[n] if need else None for n, need in zip(PARAM_NAMES, ctx.needs_input_grad[1:]))
+
+
+# --------------------------------------------------------------------------------------------------------- the module
+class TrainableLSID(nn.Module):
+    """``TrainableLSID(args=None)``: the reference's ``LSID(args)`` for training (4 input channels; ``args`` is accepted and unused, as there).
+    ``.hip()`` moves forward and backward onto the HIP library (CUDA tensors; raises without the library)."""
+
+    def __init__(self, args=None, seed: int = 0):
+        super().__init__()
+        self.block_size = 2
+        self._hip = False
+        for name, value in synth.make_state_dict(lsid_param_spec(), seed).items():     # N(0, sqrt(2 / (k*k*out))) weights, zero biases (SID_arch.py:96-103)
+            mod, leaf = name.rsplit(".", 1)
+            if mod not in self._modules:
+                self.add_module(mod, nn.Module())
+            self._modules[mod].register_parameter(leaf, nn.Parameter(value))
+
+    def hip(self, on: bool = True) -> "TrainableLSID":
+        if on:
+            L.load()
+        self._hip = bool(on)
+        return self
+
+    def _table(self) -> Dict[str, torch.Tensor]:
+        return {n: getattr(self._modules[n.rsplit(".", 1)[0]], n.rsplit(".", 1)[1]) for n in PARAM_NAMES}
+
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        P = self._table()
+        if not self._hip:
+            return lsid_forward_torch(P, x)
+        if x.device.type != "cuda" or any(p.device != x.device for p in P.values()):
+            raise L.HipError(f"TrainableLSID.hip() runs on the HIP library only: the input and every parameter must be on one GPU (input on {x.device})")
+        if x.dim() != 4 or x.shape[1] != 4:
+            raise ValueError(f"TrainableLSID takes (B, 4, H, W) images, got {tuple(x.shape)}")
+        if x.requires_grad:
+            raise ValueError("TrainableLSID.hip() does not compute the gradient of its input (conv1_1's data gradient is out of scope): "
+                             "pass an input that does not require grad, or use TrainableLSID without .hip()")
+        if any(p.dtype != torch.float32 for p in P.values()):
+            raise ValueError("TrainableLSID.hip() trains fp32 parameters")
+        if not (torch.is_grad_enabled() and any(p.requires_grad for p in P.values())):
+            with torch.no_grad():
+                return _LsidFunction.forward(_NoCtx(), x, *[P[n] for n in PARAM_NAMES])
+        return _LsidFunction.apply(x, *[P[n] for n in PARAM_NAMES])
+
+
+class _NoCtx:
+    """Stands in for the autograd context of a forward nobody differentiates (under torch.no_grad / inference)."""
+
+    def save_for_backward(self, *a):
+        pass
