@@ -3,16 +3,19 @@ consumer of the synthesized noise (BASELINE config 5).
 
 Same plug-in contract as NoiseDiffNet: ``LSID(args)``, reference state-dict names/shapes (strict load),
 ``forward(x)`` with an NCHW (B, 4, H, W) tensor.  It reuses the sampler's kernels: every ``Conv2d(3x3)`` is
-``nd_conv3x3(_wino2)_nhwc_f32`` storing the *pre-activation*; ``LeakyReLU(0.2)`` is applied by the consumer's
-prologue (ND_PRO_LEAKY; it commutes with max-pooling, and ND_PRO_LEAKY_SECOND handles
+``nd_conv3x3_{wino4, wino2, wino, direct}_nhwc_f32`` (chosen by ``train.conv3x3_kind``) storing the *pre-activation*; ``LeakyReLU(0.2)`` is
+applied by the consumer's prologue (ND_PRO_LEAKY; it commutes with max-pooling, and ND_PRO_LEAKY_SECOND handles
 ``cat(up(x), skip)`` where only the skip is activated); ``ConvTranspose2d(2, s=2)`` is one pointwise GEMM to
 4*C' columns with a pixel-shuffle store that also performs the crop.  Inference only; no CPU fallback.
+
+``lsid_forward_hip`` is the network's one list of launches: the plan here records it once per input shape and replays it,
+``lsid_train`` runs it on torch's stream as the forward of training.
 """
 from __future__ import annotations
 
 import ctypes as C
-import math
-from typing import Dict, List, Tuple
+import os
+from typing import Dict, List, Optional, Tuple
 
 import torch
 from torch import nn
@@ -20,8 +23,8 @@ from torch import nn
 from . import _lib as L
 from .net import _attach, _init
 from .spec import LSID_STAGES, lsid_param_spec
+from .train import CONV3X3_ENTRY, CONV3X3_PACK, _stream, conv3x3_kind
 
-import os
 WINO4 = os.environ.get("ND_WINO4", "1") != "0"           # A-B knob: 0 = never the F(4x4,3x3) kernel
 
 
@@ -54,8 +57,156 @@ class LSID(nn.Module):
         return self._plans[key].run(x)
 
 
+# ------------------------------------------------------------------ the network's launches, shared with lsid_train
+class _Launcher:
+    """Buffers and launches of one LSID pass; ``keep`` owns every buffer a launch reads or writes.  Weight packs and allocations execute at once.
+    The launches run now on torch's current stream (training), or, with ``stream`` given, are recorded in ``ops`` for replay on that stream
+    (the inference plan).  ``wino4`` False: no 3x3 convolution on the F(4x4,3x3) kernel."""
+
+    def __init__(self, dev: torch.device, wino4: bool, stream: Optional[C.c_void_p] = None):
+        self.lib = L.load()
+        self.dev, self.wino4 = dev, wino4
+        self.st = _stream(dev) if stream is None else stream
+        self.ops: Optional[List[tuple]] = None if stream is None else []
+        self.keep: List[object] = []
+
+    def empty(self, *shape) -> torch.Tensor:
+        t = torch.empty(*shape, dtype=torch.float32, device=self.dev)
+        self.keep.append(t)
+        return t
+
+    def launch(self, name: str, *args) -> None:
+        args += (self.st,)
+        if self.ops is None:
+            L.call(name, *args)
+        else:
+            self.keep.append(args)
+            self.ops.append((getattr(self.lib, name), args, name))
+
+    def pack(self, name: str, *args) -> None:
+        """A weight packing, run now; off torch's stream it first waits for torch, which produced the weight."""
+        if self.ops is not None:
+            torch.cuda.synchronize(self.dev)
+        L.call(name, *args, self.st)
+
+    # ---- weight packings
+    def pack_pw(self, m: torch.Tensor, cin: int, cout: int, unshuffle_c: int = 0) -> torch.Tensor:
+        out = self.empty(int(self.lib.nd_pack_pointwise_weight_floats(cin, cout)))
+        self.keep.append(m)
+        self.pack("nd_pack_pointwise_weight", m.data_ptr(), out.data_ptr(), cin, cout, unshuffle_c)
+        return out
+
+    def pack_pw_t(self, w: torch.Tensor, cin: int, cout: int) -> torch.Tensor:
+        out = self.empty(int(self.lib.nd_pack_pointwise_weight_floats(cin, cout)))
+        self.pack("nd_pack_pointwise_weight_t", w.data_ptr(), out.data_ptr(), cin, cout)
+        return out
+
+    def conv3x3(self, w_oihw: torch.Tensor, bias: Optional[torch.Tensor], src: L.Src, B: int, h: int, w: int, cin: int, cout: int,
+                dgrad: bool = False) -> torch.Tensor:
+        """One 3x3 convolution (``dgrad``: the data gradient of the layer whose forward weight is ``w_oihw``; cin / cout are the operator's)."""
+        kind = conv3x3_kind(B, h, w, cin, cout, src.c0, src.c1, max(src.ld0, src.ld1), self.wino4)
+        pack = CONV3X3_PACK[kind]
+        wp = self.empty(int(getattr(self.lib, pack + "_floats")(cin, cout)))
+        self.pack(pack + ("_dgrad" if dgrad else ""), w_oihw.data_ptr(), wp.data_ptr(), cin, cout)
+        out = self.empty(B, h, w, cout)
+        d = L.Conv3x3()
+        d.src, d.weight, d.out = src, wp.data_ptr(), out.data_ptr()
+        d.bias = bias.data_ptr() if bias is not None else None
+        d.B, d.H, d.W, d.cin, d.cout, d.ldo = B, h, w, cin, cout, cout
+        self.keep.append(d)
+        self.launch(CONV3X3_ENTRY[kind], C.byref(d))
+        return out
+
+    @staticmethod
+    def src(t: torch.Tensor, c: Optional[int] = None, ld: Optional[int] = None, t2: Optional[torch.Tensor] = None, mode: int = L.PRO_NONE,
+            offset: int = 0) -> L.Src:
+        s = L.Src()
+        s.p0, s.c0, s.ld0 = t.data_ptr() + 4 * offset, c or t.shape[-1], ld or t.shape[-1]
+        if t2 is not None:
+            s.p1, s.c1, s.ld1 = t2.data_ptr(), t2.shape[-1], t2.shape[-1]
+        s.mode = mode
+        return s
+
+    def pointwise(self, src: L.Src, wp: torch.Tensor, bias: Optional[torch.Tensor], out: torch.Tensor, B: int, HW: int, W: int, cin: int, cout: int,
+                  ldo: int, shuffle: Optional[Tuple[int, int, int]] = None, crop_src: Optional[Tuple[int, int]] = None) -> None:
+        d = L.Pointwise()
+        d.src, d.weight, d.out = src, wp.data_ptr(), out.data_ptr()
+        d.bias = bias.data_ptr() if bias is not None else None
+        d.B, d.HW, d.W, d.cin, d.cout, d.ldo = B, HW, W, cin, cout, ldo
+        if shuffle is not None:
+            d.shuffle_c, d.shuffle_h, d.shuffle_w = shuffle
+        self.keep.append(d)
+        if crop_src is not None:
+            self.launch("nd_pointwise_gemm_unshuffle_crop_nhwc_f32", C.byref(d), crop_src[0], crop_src[1])
+        else:
+            self.launch("nd_pointwise_gemm_nhwc_f32", C.byref(d))
+
+    def join(self, z: torch.Tensor, dz: torch.Tensor, d_direct: Optional[torch.Tensor], ld_direct: int, d_pool: Optional[torch.Tensor],
+             direct_offset: int = 0) -> torch.Tensor:
+        B, h, w, c = z.shape
+        self.launch("nd_leaky_grad_join_f32", z.data_ptr(), dz.data_ptr(), d_direct.data_ptr() + 4 * direct_offset if d_direct is not None else None,
+                    ld_direct, d_pool.data_ptr() if d_pool is not None else None, B, h, w, c)
+        return dz
+
+
+def _sizes(H: int, W: int) -> List[Tuple[int, int]]:
+    """Spatial size of each encoder stage: ceil-mode pooling halves with rounding up."""
+    out = [(H, W)]
+    for _ in range(4):
+        h, w = out[-1]
+        out.append(((h + 1) // 2, (w + 1) // 2))
+    return out
+
+
+def lsid_forward_hip(P: Dict[str, torch.Tensor], x: torch.Tensor, saved: Dict[str, torch.Tensor], run: _Launcher) -> torch.Tensor:
+    """LSID.forward (SID_arch.py:105-175) as launches of ``run`` on the parameter table ``P``: the (B, 4, H, W) output; fills ``saved`` with the raw
+    tensors lsid_train's backward reads."""
+    B, _, H, W = x.shape
+    sizes = _sizes(H, W)
+    xn = x.detach().to(torch.float32).contiguous()
+    run.keep.append(xn)
+    x8 = run.empty(B, H, W, 8)
+    run.launch("nd_nchw_to_nhwc_pad_f32", xn.data_ptr(), x8.data_ptr(), B, 4, H, W, 8)
+    saved["x8"] = x8
+    w11 = P["conv1_1.weight"]
+    w11 = torch.cat((w11, torch.zeros(w11.shape[0], 4, 3, 3, dtype=w11.dtype, device=w11.device)), 1).contiguous()   # conv1_1: 4 input channels padded to 8
+    run.keep.append(w11)
+    cur, mode, cin = x8, L.PRO_NONE, 8
+    for i, c in enumerate(LSID_STAGES, start=1):
+        h, w = sizes[i - 1]
+        wi1 = w11 if i == 1 else P[f"conv{i}_1.weight"]
+        a = run.conv3x3(wi1, P[f"conv{i}_1.bias"], run.src(cur, mode=mode), B, h, w, cin, c)
+        z = run.conv3x3(P[f"conv{i}_2.weight"], P[f"conv{i}_2.bias"], run.src(a, mode=L.PRO_LEAKY), B, h, w, c, c)   # raw; consumers apply LeakyReLU
+        saved[f"a{i}"], saved[f"z{i}"] = a, z
+        cur, mode, cin = z, L.PRO_LEAKY, c
+        if i < 5:
+            ph, pw = sizes[i]
+            p = run.empty(B, ph, pw, c)                                                  # max commutes with LeakyReLU
+            run.launch("nd_maxpool2x2_nhwc_f32", z.data_ptr(), p.data_ptr(), B, h, w, c)
+            saved[f"p{i}"] = p
+            cur = p
+    for j, c in zip(range(6, 10), reversed(LSID_STAGES[:-1])):
+        i = 10 - j                                           # the encoder stage of the skip
+        sh, sw = sizes[i - 1]
+        hp, wp_ = sizes[i]
+        wt = P[f"up{j}.weight"]                              # ConvTranspose2d(2, s=2) + crop to the skip's size (:135): (cin, c, 2, 2) -> rows (p1 p2 c'), columns cin
+        m = wt.permute(2, 3, 1, 0).reshape(4 * c, cin).contiguous()
+        up = run.empty(B, sh, sw, c)
+        run.pointwise(run.src(cur, mode=L.PRO_LEAKY), run.pack_pw(m, cin, 4 * c), None, up, B, hp * wp_, wp_, cin, 4 * c, c, shuffle=(c, sh, sw))
+        a = run.conv3x3(P[f"conv{j}_1.weight"], P[f"conv{j}_1.bias"], run.src(up, t2=saved[f"z{i}"], mode=L.PRO_LEAKY_SECOND), B, sh, sw, 2 * c, c)
+        z = run.conv3x3(P[f"conv{j}_2.weight"], P[f"conv{j}_2.bias"], run.src(a, mode=L.PRO_LEAKY), B, sh, sw, c, c)
+        saved[f"u{j}"], saved[f"a{j}"], saved[f"z{j}"] = up, a, z
+        cur, cin = z, c
+    y = run.empty(B, H, W, 4)
+    w10 = P["conv10.weight"].reshape(4, cin).contiguous()
+    run.pointwise(run.src(cur, mode=L.PRO_LEAKY), run.pack_pw(w10, cin, 4), P["conv10.bias"], y, B, H * W, W, cin, 4, 4)
+    out = run.empty(B, 4, H, W)
+    run.launch("nd_nhwc_to_nchw_f32", y.data_ptr(), out.data_ptr(), B, 4, H, W)
+    return out
+
+
 class _LsidPlan:
-    """Packed weights + workspace + recorded launches for one input shape."""
+    """One input shape: the forward recorded once by lsid_forward_hip (weights packed, buffers allocated), replayed on the plan's own HIP stream."""
 
     def __del__(self):                      # the plan owns its HIP stream
         s, self.stream = getattr(self, "stream", None), None
@@ -67,131 +218,18 @@ class _LsidPlan:
                 pass
 
     def __init__(self, net: LSID, dev: torch.device, B: int, H: int, W: int):
-        self.lib = L.load()
-        self.dev, self.B, self.H, self.W = dev, B, H, W
-        self.keep: List[object] = []
-        self.ops: List[tuple] = []
+        self.dev = dev
         with torch.cuda.device(dev), torch.inference_mode(False):
             s = C.c_void_p()
             L.call("nd_stream_create", C.byref(s))
             self.stream = s
-            sd = {k: v.detach().to(dev, torch.float32).contiguous() for k, v in net.state_dict().items()}
-            torch.cuda.synchronize(dev)
-            self.w: Dict[str, torch.Tensor] = {}
-            for name, t in sd.items():
-                if name.endswith(".bias"):
-                    self.w[name] = t
-                elif name.startswith("up"):          # (Cin, Cout, 2, 2) -> rows n = (p1 p2 c'), columns k = cin
-                    cin, cout = t.shape[:2]
-                    m = t.permute(2, 3, 1, 0).reshape(4 * cout, cin).contiguous()
-                    self.w[name] = self._pack_pw(m)
-                elif t.shape[-1] == 1:
-                    self.w[name] = self._pack_pw(t.reshape(t.shape[0], -1).contiguous())
-                else:
-                    if t.shape[1] % 8:               # conv1_1: 4 input channels, zero-padded to 8
-                        t = torch.cat((t, torch.zeros(t.shape[0], 8 - t.shape[1] % 8, 3, 3, device=dev)), 1).contiguous()
-                        torch.cuda.synchronize(dev)
-                    self.w[name] = self._pack_conv(t)
+            P = {k: v.detach().to(dev, torch.float32).contiguous() for k, v in net.state_dict().items()}
             self.x_nchw = torch.empty(B, 4, H, W, device=dev)
-            self.out_nchw = torch.empty(B, 4, H, W, device=dev)
-            self._record()
+            rec = _Launcher(dev, WINO4, stream=s)
+            rec.keep.append(P)                                # the packs read the weights, the recorded launches the biases
+            self.out_nchw = lsid_forward_hip(P, self.x_nchw, {}, rec)
+            self.ops, self.keep = rec.ops, rec.keep
             L.call("nd_stream_sync", self.stream)
-
-    # ------------------------------------------------------------------ helpers
-    def _f(self, *shape) -> torch.Tensor:
-        t = torch.empty(*shape, dtype=torch.float32, device=self.dev)
-        self.keep.append(t)
-        return t
-
-    def _pack_pw(self, m: torch.Tensor) -> torch.Tensor:
-        cout, cin = m.shape
-        out = self._f(self.lib.nd_pack_pointwise_weight_floats(cin, cout))
-        self.keep.append(m)
-        torch.cuda.synchronize(self.dev)
-        L.call("nd_pack_pointwise_weight", m.data_ptr(), out.data_ptr(), cin, cout, 0, self.stream)
-        return out
-
-    def _pack_conv(self, t: torch.Tensor):
-        """(direct, F(2x2,3x3), F(4x4,3x3) or None) packings of one 3x3 weight."""
-        cout, cin = t.shape[:2]
-        d = self._f(self.lib.nd_pack_conv3x3_weight_floats(cin, cout))
-        w = self._f(self.lib.nd_pack_conv3x3_wino_weight_floats(cin, cout))
-        self.keep.append(t)
-        L.call("nd_pack_conv3x3_weight", t.data_ptr(), d.data_ptr(), cin, cout, self.stream)
-        L.call("nd_pack_conv3x3_wino_weight", t.data_ptr(), w.data_ptr(), cin, cout, self.stream)
-        w4 = None
-        if WINO4 and cin > 16 and cin % 4 == 0 and cout % 4 == 0:
-            w4 = self._f(self.lib.nd_pack_conv3x3_wino4_weight_floats(cin, cout))
-            L.call("nd_pack_conv3x3_wino4_weight", t.data_ptr(), w4.data_ptr(), cin, cout, self.stream)
-        return d, w, w4
-
-    def _add(self, name: str, *args) -> None:
-        self.keep.append(args)
-        self.ops.append((getattr(self.lib, name), args, name))
-
-    def _src(self, t, t2=None, mode=L.PRO_NONE) -> L.Src:
-        s = L.Src()
-        s.p0, s.c0, s.ld0 = t.data_ptr(), t.shape[-1], t.shape[-1]
-        if t2 is not None:
-            s.p1, s.c1, s.ld1 = t2.data_ptr(), t2.shape[-1], t2.shape[-1]
-        s.mode = mode
-        return s
-
-    def _conv(self, name: str, src: L.Src, cin: int, cout: int, h: int, w: int) -> torch.Tensor:
-        out = self._f(self.B, h, w, cout)
-        wino = h >= 16 and w >= 16
-        d = L.Conv3x3()
-        d.src, d.weight, d.bias, d.out = src, self.w[name + ".weight"][1 if wino else 0].data_ptr(), self.w[name + ".bias"].data_ptr(), out.data_ptr()
-        d.B, d.H, d.W, d.cin, d.cout, d.ldo = self.B, h, w, cin, cout, cout
-        wino2 = wino and (src.c1 == 0 or src.c0 % 32 == 0) and self.B * h * w < (1 << 24) and self.B * h * w * 4 * max(src.ld0, src.ld1) < (1 << 31)
-        # F(4x4,3x3) where its kernel takes the layer (same rule as the engine's): the LeakyReLU prologues are applied while the halo is staged
-        wino4 = (wino and self.w[name + ".weight"][2] is not None and w >= 32 and (w % 32 == 0 or w >= 96) and w <= 2048
-                 and (src.c1 == 0 or src.c0 % 16 == 0) and self.B * h * w + w + 2 < (1 << 24)
-                 and (self.B * h * w + w + 2) * 4 * max(src.ld0, src.ld1) < (1 << 30) - (1 << 16))
-        if wino4:
-            d.weight = self.w[name + ".weight"][2].data_ptr()
-        self._add("nd_conv3x3_wino4_nhwc_f32" if wino4 else "nd_conv3x3_wino2_nhwc_f32" if wino2 else
-                  "nd_conv3x3_wino_nhwc_f32" if wino else "nd_conv3x3_nhwc_f32", C.byref(d), self.stream)
-        self.keep.append(d)
-        return out
-
-    # ------------------------------------------------------------------ the network (SID_arch.py:105-175)
-    def _record(self) -> None:
-        B, H, W = self.B, self.H, self.W
-        x8 = self._f(B, H, W, 8)
-        self._add("nd_nchw_to_nhwc_pad_f32", self.x_nchw.data_ptr(), x8.data_ptr(), B, 4, H, W, 8, self.stream)
-        feats: List[Tuple[torch.Tensor, int, int]] = []
-        x, mode, cin, h, w = x8, L.PRO_NONE, 8, H, W
-        for i, c in enumerate(LSID_STAGES, start=1):
-            a = self._conv(f"conv{i}_1", self._src(x, None, mode), cin, c, h, w)
-            x = self._conv(f"conv{i}_2", self._src(a, None, L.PRO_LEAKY), c, c, h, w)      # raw; consumers apply LeakyReLU
-            cin, mode = c, L.PRO_LEAKY
-            if i < 5:
-                feats.append((x, h, w))
-                ph, pw = (h + 1) // 2, (w + 1) // 2
-                p = self._f(B, ph, pw, c)                                                 # max commutes with LeakyReLU
-                self._add("nd_maxpool2x2_nhwc_f32", x.data_ptr(), p.data_ptr(), B, h, w, c, self.stream)
-                x, h, w = p, ph, pw
-        for i, c in zip(range(6, 10), reversed(LSID_STAGES[:-1])):
-            skip, sh, sw = feats.pop()
-            up = self._f(B, sh, sw, c)                      # ConvTranspose2d(2, s=2) + crop to the skip's size (:135)
-            d = L.Pointwise()
-            d.src, d.weight, d.out = self._src(x, None, L.PRO_LEAKY), self.w[f"up{i}.weight"].data_ptr(), up.data_ptr()
-            d.B, d.HW, d.W, d.cin, d.cout, d.ldo = B, h * w, w, cin, 4 * c, c
-            d.shuffle_c, d.shuffle_h, d.shuffle_w = c, sh, sw
-            self._add("nd_pointwise_gemm_nhwc_f32", C.byref(d), self.stream)
-            self.keep.append(d)
-            h, w = sh, sw
-            a = self._conv(f"conv{i}_1", self._src(up, skip, L.PRO_LEAKY_SECOND), 2 * c, c, h, w)
-            x = self._conv(f"conv{i}_2", self._src(a, None, L.PRO_LEAKY), c, c, h, w)
-            cin = c
-        y = self._f(B, H, W, 4)
-        d = L.Pointwise()
-        d.src, d.weight, d.bias, d.out = self._src(x, None, L.PRO_LEAKY), self.w["conv10.weight"].data_ptr(), self.w["conv10.bias"].data_ptr(), y.data_ptr()
-        d.B, d.HW, d.W, d.cin, d.cout, d.ldo = B, H * W, W, cin, 4, 4
-        self._add("nd_pointwise_gemm_nhwc_f32", C.byref(d), self.stream)
-        self.keep.append(d)
-        self._add("nd_nhwc_to_nchw_f32", y.data_ptr(), self.out_nchw.data_ptr(), B, 4, H, W, self.stream)
 
     def run(self, x: torch.Tensor) -> torch.Tensor:
         with torch.cuda.device(self.dev):

@@ -11,9 +11,10 @@ Parameters are registered under the reference's names and shapes (spec.lsid_para
 tests/test_lsid_train.py pins against the reference's loss and gradients.  With ``.hip()`` the whole network is ONE torch.autograd.Function
 (``_LsidFunction``) over the HIP library, forward and backward:
 
-  forward   the launches of lsid._LsidPlan._record: every convolution stores its RAW pre-activation, the consumers apply LeakyReLU(0.2) in their
-            prologue (ND_PRO_LEAKY / ND_PRO_LEAKY_SECOND), the ceil-mode max-pools run on raw values (max commutes with the activation), each
-            ConvTranspose2d(2, s=2) is one pointwise GEMM with a pixel-shuffle store that also crops.  Saved: the raw tensors below, nothing activated.
+  forward   lsid.lsid_forward_hip, the launches the inference LSID records: every convolution stores its RAW pre-activation, the consumers
+            apply LeakyReLU(0.2) in their prologue (ND_PRO_LEAKY / ND_PRO_LEAKY_SECOND), the ceil-mode max-pools run on raw values (max commutes
+            with the activation), each ConvTranspose2d(2, s=2) is one pointwise GEMM with a pixel-shuffle store that also crops.  Saved: the raw
+            tensors below, nothing activated.
   backward  in reverse: conv10's weight gradient (nd_linear_wgrad_leaky_f32) and data gradient (pointwise GEMM); per LeakyReLU the gradient join
             nd_leaky_grad_join_f32 (direct gradient + max-pool scatter, times the slope); per 3x3 convolution the weight gradient with the activation
             applied on load (nd_conv3x3_wgrad_leaky / _cat_leaky_second) and the data gradient as the forward kernels on dgrad-packed weights; per
@@ -27,8 +28,7 @@ gradients) from the parameters as they are: no cache that an optimizer step coul
 """
 from __future__ import annotations
 
-import ctypes as C
-from typing import Dict, List, Optional, Tuple
+from typing import Dict, Optional, Tuple
 
 import torch
 import torch.nn.functional as F
@@ -37,10 +37,11 @@ from torch.autograd.function import once_differentiable
 
 from . import _lib as L
 from . import synth
+from .lsid import _Launcher, _sizes, lsid_forward_hip
 from .spec import LSID_STAGES, lsid_param_spec
 
 SLOPE = 0.2
-# F(4x4,3x3) Winograd kernels where they take the layer (lsid.py's rule), for the forward / the data-gradient convolutions; False: F(2x2,3x3) there.
+# F(4x4,3x3) Winograd kernels where they take the layer (train.conv3x3_kind), for the forward / the data-gradient convolutions; False: F(2x2,3x3) there.
 # Measured at B = 4, 256 x 256 against float64 (max |g - g64| / max |g64| over the parameters): F(4x4) forward 1.8e-4, F(2x2) forward 5.2e-5 --
 # PyTorch's own fp32 path 6.3e-5; the data-gradient form changes none of these figures.  The forward is what the saved activations carry into
 # every weight gradient, so training keeps it on F(2x2).
@@ -68,156 +69,6 @@ def lsid_forward_torch(p: Dict[str, torch.Tensor], x: torch.Tensor) -> torch.Ten
 
 
 # --------------------------------------------------------------------------------------------------------- HIP launches
-def _stream(dev: torch.device) -> C.c_void_p:
-    return C.c_void_p(torch._C._cuda_getCurrentRawStream(dev.index if dev.index is not None else torch.cuda.current_device()))
-
-
-class _Launcher:
-    """Buffers and launches of one forward or backward pass on the current stream; ``keep`` owns every buffer a launch reads or writes."""
-
-    def __init__(self, dev: torch.device):
-        self.lib = L.load()
-        self.dev = dev
-        self.st = _stream(dev)
-        self.keep: List[object] = []
-
-    def empty(self, *shape) -> torch.Tensor:
-        t = torch.empty(*shape, dtype=torch.float32, device=self.dev)
-        self.keep.append(t)
-        return t
-
-    # ---- weight packings
-    def pack_pw(self, m: torch.Tensor, cin: int, cout: int, unshuffle_c: int = 0) -> torch.Tensor:
-        out = self.empty(int(self.lib.nd_pack_pointwise_weight_floats(cin, cout)))
-        self.keep.append(m)
-        L.call("nd_pack_pointwise_weight", m.data_ptr(), out.data_ptr(), cin, cout, unshuffle_c, self.st)
-        return out
-
-    def pack_pw_t(self, w: torch.Tensor, cin: int, cout: int) -> torch.Tensor:
-        out = self.empty(int(self.lib.nd_pack_pointwise_weight_floats(cin, cout)))
-        L.call("nd_pack_pointwise_weight_t", w.data_ptr(), out.data_ptr(), cin, cout, self.st)
-        return out
-
-    @staticmethod
-    def conv_kind(B: int, h: int, w: int, cin: int, cout: int, c0: int, c1: int, ld: int, wino4: bool = True) -> str:
-        """The forward kernel of a 3x3 layer (lsid._LsidPlan._conv's rule): 'wino4', 'wino2', 'wino' or 'direct'."""
-        wino = h >= 16 and w >= 16
-        if (wino4 and wino and cin > 16 and cin % 4 == 0 and cout % 4 == 0 and w >= 32 and (w % 32 == 0 or w >= 96) and w <= 2048
-                and (c1 == 0 or c0 % 16 == 0) and B * h * w + w + 2 < (1 << 24) and (B * h * w + w + 2) * 4 * ld < (1 << 30) - (1 << 16)):
-            return "wino4"
-        if wino and (c1 == 0 or c0 % 32 == 0) and B * h * w < (1 << 24) and B * h * w * 4 * ld < (1 << 31):
-            return "wino2"
-        return "wino" if wino else "direct"
-
-    _PACK = {"wino4": "nd_pack_conv3x3_wino4_weight", "wino2": "nd_pack_conv3x3_wino_weight", "wino": "nd_pack_conv3x3_wino_weight",
-             "direct": "nd_pack_conv3x3_weight"}
-    _ENTRY = {"wino4": "nd_conv3x3_wino4_nhwc_f32", "wino2": "nd_conv3x3_wino2_nhwc_f32", "wino": "nd_conv3x3_wino_nhwc_f32",
-              "direct": "nd_conv3x3_nhwc_f32"}
-
-    def conv3x3(self, w_oihw: torch.Tensor, bias: Optional[torch.Tensor], src: L.Src, B: int, h: int, w: int, cin: int, cout: int,
-                dgrad: bool = False, out: Optional[torch.Tensor] = None) -> torch.Tensor:
-        """One 3x3 convolution (``dgrad``: the data gradient of the layer whose forward weight is ``w_oihw``; cin / cout are the operator's)."""
-        kind = self.conv_kind(B, h, w, cin, cout, src.c0, src.c1, max(src.ld0, src.ld1), WINO4_DGRAD if dgrad else WINO4_FORWARD)
-        pack = self._PACK[kind]
-        wp = self.empty(int(getattr(self.lib, pack + "_floats")(cin, cout)))
-        L.call(pack + ("_dgrad" if dgrad else ""), w_oihw.data_ptr(), wp.data_ptr(), cin, cout, self.st)
-        if out is None:
-            out = self.empty(B, h, w, cout)
-        d = L.Conv3x3()
-        d.src, d.weight, d.out = src, wp.data_ptr(), out.data_ptr()
-        d.bias = bias.data_ptr() if bias is not None else None
-        d.B, d.H, d.W, d.cin, d.cout, d.ldo = B, h, w, cin, cout, cout
-        self.keep.append(d)
-        L.call(self._ENTRY[kind], C.byref(d), self.st)
-        return out
-
-    @staticmethod
-    def src(t: torch.Tensor, c: Optional[int] = None, ld: Optional[int] = None, t2: Optional[torch.Tensor] = None, mode: int = L.PRO_NONE,
-            offset: int = 0) -> L.Src:
-        s = L.Src()
-        s.p0, s.c0, s.ld0 = t.data_ptr() + 4 * offset, c or t.shape[-1], ld or t.shape[-1]
-        if t2 is not None:
-            s.p1, s.c1, s.ld1 = t2.data_ptr(), t2.shape[-1], t2.shape[-1]
-        s.mode = mode
-        return s
-
-    def pointwise(self, src: L.Src, wp: torch.Tensor, bias: Optional[torch.Tensor], out: torch.Tensor, B: int, HW: int, W: int, cin: int, cout: int,
-                  ldo: int, shuffle: Optional[Tuple[int, int, int]] = None, crop_src: Optional[Tuple[int, int]] = None) -> None:
-        d = L.Pointwise()
-        d.src, d.weight, d.out = src, wp.data_ptr(), out.data_ptr()
-        d.bias = bias.data_ptr() if bias is not None else None
-        d.B, d.HW, d.W, d.cin, d.cout, d.ldo = B, HW, W, cin, cout, ldo
-        if shuffle is not None:
-            d.shuffle_c, d.shuffle_h, d.shuffle_w = shuffle
-        self.keep.append(d)
-        if crop_src is not None:
-            L.call("nd_pointwise_gemm_unshuffle_crop_nhwc_f32", C.byref(d), crop_src[0], crop_src[1], self.st)
-        else:
-            L.call("nd_pointwise_gemm_nhwc_f32", C.byref(d), self.st)
-
-    def join(self, z: torch.Tensor, dz: torch.Tensor, d_direct: Optional[torch.Tensor], ld_direct: int, d_pool: Optional[torch.Tensor],
-             direct_offset: int = 0) -> torch.Tensor:
-        B, h, w, c = z.shape
-        L.call("nd_leaky_grad_join_f32", z.data_ptr(), dz.data_ptr(), d_direct.data_ptr() + 4 * direct_offset if d_direct is not None else None,
-               ld_direct, d_pool.data_ptr() if d_pool is not None else None, B, h, w, c, self.st)
-        return dz
-
-
-def _sizes(H: int, W: int) -> List[Tuple[int, int]]:
-    """Spatial size of each encoder stage: ceil-mode pooling halves with rounding up."""
-    out = [(H, W)]
-    for _ in range(4):
-        h, w = out[-1]
-        out.append(((h + 1) // 2, (w + 1) // 2))
-    return out
-
-
-def _lsid_hip_forward(P: Dict[str, torch.Tensor], x: torch.Tensor, saved: Dict[str, torch.Tensor], run: _Launcher) -> torch.Tensor:
-    """The forward launches (lsid._LsidPlan._record) on the current stream; fills ``saved`` with the raw tensors the backward reads."""
-    B, _, H, W = x.shape
-    sizes = _sizes(H, W)
-    xn = x.detach().to(torch.float32).contiguous()
-    run.keep.append(xn)
-    x8 = run.empty(B, H, W, 8)
-    L.call("nd_nchw_to_nhwc_pad_f32", xn.data_ptr(), x8.data_ptr(), B, 4, H, W, 8, run.st)
-    saved["x8"] = x8
-    w11 = P["conv1_1.weight"]
-    w11 = torch.cat((w11, torch.zeros(w11.shape[0], 4, 3, 3, dtype=w11.dtype, device=w11.device)), 1).contiguous()   # conv1_1: 4 input channels padded to 8
-    run.keep.append(w11)
-    cur, mode, cin = x8, L.PRO_NONE, 8
-    for i, c in enumerate(LSID_STAGES, start=1):
-        h, w = sizes[i - 1]
-        wi1 = w11 if i == 1 else P[f"conv{i}_1.weight"]
-        a = run.conv3x3(wi1, P[f"conv{i}_1.bias"], run.src(cur, mode=mode), B, h, w, cin, c)
-        z = run.conv3x3(P[f"conv{i}_2.weight"], P[f"conv{i}_2.bias"], run.src(a, mode=L.PRO_LEAKY), B, h, w, c, c)
-        saved[f"a{i}"], saved[f"z{i}"] = a, z
-        cur, mode, cin = z, L.PRO_LEAKY, c
-        if i < 5:
-            ph, pw = sizes[i]
-            p = run.empty(B, ph, pw, c)
-            L.call("nd_maxpool2x2_nhwc_f32", z.data_ptr(), p.data_ptr(), B, h, w, c, run.st)
-            saved[f"p{i}"] = p
-            cur = p
-    for j, c in zip(range(6, 10), reversed(LSID_STAGES[:-1])):
-        i = 10 - j                                           # the encoder stage of the skip
-        sh, sw = sizes[i - 1]
-        hp, wp_ = sizes[i]
-        wt = P[f"up{j}.weight"]                              # (cin, c, 2, 2) -> rows (p1 p2 c'), columns cin
-        m = wt.permute(2, 3, 1, 0).reshape(4 * c, cin).contiguous()
-        up = run.empty(B, sh, sw, c)
-        run.pointwise(run.src(cur, mode=L.PRO_LEAKY), run.pack_pw(m, cin, 4 * c), None, up, B, hp * wp_, wp_, cin, 4 * c, c, shuffle=(c, sh, sw))
-        a = run.conv3x3(P[f"conv{j}_1.weight"], P[f"conv{j}_1.bias"], run.src(up, t2=saved[f"z{i}"], mode=L.PRO_LEAKY_SECOND), B, sh, sw, 2 * c, c)
-        z = run.conv3x3(P[f"conv{j}_2.weight"], P[f"conv{j}_2.bias"], run.src(a, mode=L.PRO_LEAKY), B, sh, sw, c, c)
-        saved[f"u{j}"], saved[f"a{j}"], saved[f"z{j}"] = up, a, z
-        cur, cin = z, c
-    y = run.empty(B, H, W, 4)
-    w10 = P["conv10.weight"].reshape(4, cin).contiguous()
-    run.pointwise(run.src(cur, mode=L.PRO_LEAKY), run.pack_pw(w10, cin, 4), P["conv10.bias"], y, B, H * W, W, cin, 4, 4)
-    out = torch.empty(B, 4, H, W, dtype=torch.float32, device=x.device)
-    L.call("nd_nhwc_to_nchw_f32", y.data_ptr(), out.data_ptr(), B, 4, H, W, run.st)
-    return out
-
-
 def _lsid_hip_backward(P: Dict[str, torch.Tensor], saved: Dict[str, torch.Tensor], grad_out: torch.Tensor, run: _Launcher) -> Dict[str, torch.Tensor]:
     """Weight and bias gradients of every parameter from the raw tensors of the forward, in reverse launch order."""
     lib = run.lib
@@ -306,10 +157,10 @@ class _LsidFunction(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, *params):
         P = dict(zip(PARAM_NAMES, (p.detach() for p in params)))
-        run = _Launcher(x.device)
+        run = _Launcher(x.device, WINO4_FORWARD)
         saved: Dict[str, torch.Tensor] = {}
         with torch.cuda.device(x.device):
-            out = _lsid_hip_forward(P, x, saved, run)
+            out = lsid_forward_hip(P, x, saved, run)
         ctx.saved = saved                                    # raw tensors only; the packed weights and staging buffers are dropped with ``run``
         ctx.save_for_backward(*params)                       # (version-checked: an optimizer step between forward and backward raises)
         return out
@@ -319,7 +170,7 @@ class _LsidFunction(torch.autograd.Function):
     def backward(ctx, grad_out):
         params = ctx.saved_tensors
         P = dict(zip(PARAM_NAMES, (p.detach() for p in params)))
-        run = _Launcher(grad_out.device)
+        run = _Launcher(grad_out.device, WINO4_DGRAD)
         with torch.cuda.device(grad_out.device):
             G = _lsid_hip_backward(P, ctx.saved, grad_out, run)
         ctx.saved = None

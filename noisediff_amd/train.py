@@ -6,7 +6,7 @@
     loss = noisediff_amd.GaussianDiffusion(model, ...)(img, condition); loss.backward()
 
 ``Conv3x3Function`` is a ``torch.autograd.Function`` over the C ABI:
-  * forward      nd_conv3x3_{wino4, wino2, direct}_nhwc_f32 (the sampling path's kernels, same selection rule as the engine)
+  * forward      nd_conv3x3_{wino4, wino2, direct}_nhwc_f32 (the sampling path's kernels, chosen by ``conv3x3_kind``)
   * grad input   the SAME forward kernels on weights packed from ``w.flip(2, 3).transpose(0, 1)`` -- the data gradient of a
                  stride-1 "same" convolution is that convolution with the taps flipped and the channel roles swapped
                  (nd_pack_conv3x3_*_weight_dgrad read the forward weight that way in place)
@@ -69,6 +69,25 @@ def _stream(device: Optional[torch.device] = None) -> C.c_void_p:
 _SPLIT_K = __import__("os").environ.get("ND_TRAIN_SPLITK", "1") != "0"      # A/B knob (tools/): 0 = never the split-K form of conv3x3_wino4
 
 
+def conv3x3_kind(B: int, H: int, W: int, cin: int, cout: int, c0: int, c1: int, ld: int, wino4: bool = True) -> str:
+    """The kernel of a 3x3 convolution outside the sampling engine: 'wino4', 'wino2', 'wino' (F(2x2,3x3) past wino2's limits) or 'direct'.
+    ``c0`` / ``c1``: the channels of the two sources (c1 = 0: one source); ``ld``: the pixel stride the source-size limits are computed with;
+    ``wino4`` False: never the F(4x4,3x3) kernel.  Host-only: needs no library."""
+    wino = H >= 16 and W >= 16 and cin % 8 == 0
+    if (wino4 and wino and cin > 16 and cin % 4 == 0 and cout % 4 == 0 and cout <= 2048 and W >= 32 and (W % 32 == 0 or W >= 96) and W <= 2048
+            and (c1 == 0 or c0 % 16 == 0) and B * H * W + W + 2 < (1 << 24) and (B * H * W + W + 2) * 4 * ld < (1 << 30) - (1 << 16)):
+        return "wino4"
+    if wino and (c1 == 0 or c0 % 32 == 0) and B * H * W < (1 << 24) and B * H * W * 4 * ld < (1 << 31):
+        return "wino2"
+    return "wino" if wino else "direct"
+
+
+CONV3X3_PACK = {"wino4": "nd_pack_conv3x3_wino4_weight", "wino2": "nd_pack_conv3x3_wino_weight", "wino": "nd_pack_conv3x3_wino_weight",
+                "direct": "nd_pack_conv3x3_weight"}
+CONV3X3_ENTRY = {"wino4": "nd_conv3x3_wino4_nhwc_f32", "wino2": "nd_conv3x3_wino2_nhwc_f32", "wino": "nd_conv3x3_wino_nhwc_f32",
+                 "direct": "nd_conv3x3_nhwc_f32"}
+
+
 def _conv3x3_nhwc(x: torch.Tensor, w_oihw: torch.Tensor, bias: Optional[torch.Tensor], dgrad: bool = False, stats: bool = False,
                   x1: Optional[torch.Tensor] = None):
     """y = conv2d(x, w, bias, padding=1) on the HIP library; x (B, cin, H, W) channels_last, returns (B, cout, H, W) channels_last.
@@ -96,21 +115,13 @@ def _conv3x3_nhwc(x: torch.Tensor, w_oihw: torch.Tensor, bias: Optional[torch.Te
     w_oihw = w_oihw.detach().to(torch.float32).contiguous()
     with _on(x.device):
         out = torch.empty((B, cout, H, W), dtype=torch.float32, device=x.device, memory_format=torch.channels_last)
-        src_bytes = B * H * W * cin * 4
-        wino = H >= 16 and W >= 16 and cin % 8 == 0
-        wino4 = (wino and W >= 32 and (W % 32 == 0 or W >= 96) and W <= 2048 and cin > 16 and cout <= 2048
-                 and (B * H * W + W + 2) * cin * 4 < (1 << 30) - (1 << 16) and B * H * W + W + 2 < (1 << 24))
-        if x1 is not None and not (wino4 and c0 % 16 == 0 and x1.shape[1] % 16 == 0):
+        kind = conv3x3_kind(B, H, W, cin, cout, c0, cin - c0, cin)       # ld = c0 + c1 for a concat: stricter than the kernel's widest-source bound
+        if x1 is not None and (kind != "wino4" or c0 % 16 or x1.shape[1] % 16):
             raise L.HipError(f"conv3x3 over two sources needs the F(4x4) kernel and sources of whole 16-channel chunks ({c0} + {x1.shape[1]} channels, {H}x{W})")
-        wino2 = wino and B * H * W < (1 << 24) and src_bytes < (1 << 31)
-        if wino4:
-            pack, entry = "nd_pack_conv3x3_wino4_weight", "nd_conv3x3_wino4_nhwc_f32"
-        elif wino2:
-            pack, entry = "nd_pack_conv3x3_wino_weight", "nd_conv3x3_wino2_nhwc_f32"
-        else:
-            pack, entry = "nd_pack_conv3x3_weight", "nd_conv3x3_nhwc_f32"
-            if cin % 8:
-                raise L.HipError(f"conv3x3 on the HIP library needs cin % 8 == 0 (cin={cin})")
+        kind = "direct" if kind == "wino" else kind                      # past wino2's limits: the direct kernel
+        if kind == "direct" and cin % 8:
+            raise L.HipError(f"conv3x3 on the HIP library needs cin % 8 == 0 (cin={cin})")
+        pack, entry, wino4 = CONV3X3_PACK[kind], CONV3X3_ENTRY[kind], kind == "wino4"
         if wino4 and cached:
             wptr = _pack_cache(x.device).get(w_oihw, cin, cout, dgrad, st, kind="w4", base=wbase)
         else:
@@ -129,7 +140,7 @@ def _conv3x3_nhwc(x: torch.Tensor, w_oihw: torch.Tensor, bias: Optional[torch.Te
         splits = int(lib.nd_conv3x3_wino4_splitk_plan(B, H, W, cin, cout)) if wino4 and _SPLIT_K else 1
         st_t = sc_t = None
         if stats:                                                 # (the split-K form leaves the same slots from its reduction kernel)
-            slots = int(lib.nd_conv3x3_wino4_stat_slots(H, W) if wino4 else lib.nd_conv3x3_wino_stat_slots(H, W) if wino2
+            slots = int(lib.nd_conv3x3_wino4_stat_slots(H, W) if wino4 else lib.nd_conv3x3_wino_stat_slots(H, W) if kind == "wino2"
                         else lib.nd_conv3x3_stat_slots(H, W, cout, B))
             st_t = torch.empty((B, slots, cout, 2), dtype=torch.float32, device=x.device)
             sc_t = torch.empty(slots, dtype=torch.float32, device=x.device)
@@ -213,8 +224,7 @@ def cat_sources_ok(x0: torch.Tensor, x1: torch.Tensor, cout: Optional[int] = Non
     if cout is not None and (cout % 8 or cout > 2048):
         return False
     return (x0.is_cuda and x1.is_cuda and x0.dim() == 4 and tuple(x1.shape[2:]) == (H, W) and x1.shape[0] == B and c0 % 16 == 0 and c1 % 16 == 0
-            and H >= 16 and W >= 32 and (W % 32 == 0 or W >= 96) and W <= 2048
-            and (B * H * W + W + 2) * (c0 + c1) * 4 < (1 << 30) - (1 << 16) and B * H * W + W + 2 < (1 << 24))
+            and conv3x3_kind(B, H, W, c0 + c1, cout or 8, c0, c1, c0 + c1) == "wino4")      # ld = c0 + c1 as in _conv3x3_nhwc; no cout: 8
 
 
 class Conv3x3CatFunction(torch.autograd.Function):

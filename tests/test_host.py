@@ -360,6 +360,71 @@ def test_split_k_plan_is_a_function_of_the_shape():
     assert lib.nd_conv3x3_wino4_splitk_workspace_floats(2, 8, 8, 16, 4) == 2 * 8 * 8 * 16 * 4
 
 
+# The kernel of each of LSID's 3x3 operators per (B, H, W), with wino4 on / off: what the two LSID copies of the rule chose before
+# train.conv3x3_kind replaced them.  One group per stage: encoder stages 1-5 (conv_i_1, conv_i_2, conv_i_1's data gradient from stage 2 on), then
+# decoder stages 6-9 (conv_j_1 over the concat, conv_j_2, conv_j_1's data gradient); conv_k_2's data gradient has conv_k_2's arguments.
+# 4: wino4, 2: wino2, w: wino, d: direct.
+LSID_KINDS = {
+    (2, 64, 64): ("24 444 222 ddd ddd ddd 222 444 444", "22 222 222 ddd ddd ddd 222 222 222"),
+    (1, 36, 44): ("22 222 ddd ddd ddd ddd ddd 222 222", "22 222 ddd ddd ddd ddd ddd 222 222"),
+    (4, 256, 256): ("24 444 444 444 222 444 444 444 444", "22 222 222 222 222 222 222 222 222"),
+    (1, 512, 512): ("24 444 444 444 444 444 444 444 444", "22 222 222 222 222 222 222 222 222"),
+}
+
+
+def _lsid_conv3x3_ops(B, H, W):
+    """(B, h, w, cin, cout, c0, c1, ld) of LSID's 3x3 operators grouped per stage, as the HIP forward and backward pass them (ld: widest source)."""
+    from noisediff_amd.spec import LSID_STAGES
+    sizes = [(H, W)]
+    for _ in range(4):
+        sizes.append(((sizes[-1][0] + 1) // 2, (sizes[-1][1] + 1) // 2))
+    groups, cin = [], 8
+    for i, c in enumerate(LSID_STAGES):
+        h, w = sizes[i]
+        groups.append([(B, h, w, cin, c, cin, 0, cin), (B, h, w, c, c, c, 0, c)] + ([(B, h, w, c, cin, c, 0, c)] if i else []))
+        cin = c
+    for i in (3, 2, 1, 0):
+        c, (h, w) = LSID_STAGES[i], sizes[i]
+        groups.append([(B, h, w, 2 * c, c, c, c, c), (B, h, w, c, c, c, 0, c), (B, h, w, c, 2 * c, c, 0, c)])
+    return groups
+
+
+@pytest.mark.parametrize("B,H,W", sorted(LSID_KINDS))
+def test_conv3x3_kind_keeps_the_lsid_kernels(B, H, W):
+    from noisediff_amd.train import conv3x3_kind
+    letter = {"wino4": "4", "wino2": "2", "wino": "w", "direct": "d"}
+    for wino4, want in zip((True, False), LSID_KINDS[(B, H, W)]):
+        got = " ".join("".join(letter[conv3x3_kind(*op, wino4=wino4)] for op in g) for g in _lsid_conv3x3_ops(B, H, W))
+        assert got == want, (wino4, got)
+
+
+def _cuda_like(*shape):
+    """What cat_sources_ok reads of a CUDA tensor, without a GPU."""
+    return SimpleNamespace(shape=torch.Size(shape), is_cuda=True, dim=lambda: len(shape))
+
+
+def test_conv3x3_kind_keeps_the_train_and_lsid_decisions_at_their_limits():
+    from noisediff_amd import train
+    kind = train.conv3x3_kind
+    # conv9_1 at B = 16, 512 x 512 (c0 = c1 = 32): LSID bounds the source by its widest stride and takes wino4, train.py by c0 + c1 and refuses it
+    assert kind(16, 512, 512, 64, 32, 32, 32, 32) == "wino4"
+    assert kind(16, 512, 512, 64, 32, 32, 32, 64) == "wino2"
+    assert not train.cat_sources_ok(_cuda_like(16, 32, 512, 512), _cuda_like(16, 32, 512, 512), 32)
+    assert train.cat_sources_ok(_cuda_like(2, 32, 64, 64), _cuda_like(2, 32, 64, 64), 32)
+    assert train.cat_sources_ok(_cuda_like(2, 32, 64, 64), _cuda_like(2, 32, 64, 64))
+    # past 2^24 pixels: F(2x2) wino (LSID runs it, train.py takes the direct kernel instead)
+    assert kind(64, 512, 512, 64, 64, 64, 0, 64) == "wino"
+    # a concat with c0 % 16 != 0 or c1 % 16 != 0: not wino4, so train.py refuses it
+    assert kind(2, 64, 64, 40, 32, 8, 32, 40) == "wino"
+    assert not train.cat_sources_ok(_cuda_like(2, 8, 64, 64), _cuda_like(2, 32, 64, 64), 32)
+    assert not train.cat_sources_ok(_cuda_like(2, 32, 64, 64), _cuda_like(2, 8, 64, 64), 32)
+    assert not train.cat_sources_ok(_cuda_like(2, 32, 64, 64), _cuda_like(2, 32, 64, 64), 4096)
+    # cin % 8 != 0: direct (train.py raises); cout > 2048 and a width the F(4x4) kernel does not tile: wino2
+    assert kind(1, 64, 64, 12, 16, 12, 0, 12) == "direct"
+    assert kind(1, 64, 64, 64, 4096, 64, 0, 64) == "wino2"
+    assert kind(2, 64, 40, 64, 64, 64, 0, 64) == "wino2"
+
+
 def test_sampling_split_k_plan_looks_at_the_sample_geometry_only():
     """nd_conv3x3_wino4_16_splitk_plan (host code, no GPU) has no batch argument: BASELINE config 2's 16 x 16 and 32 x 32 stages are cut into K ranges
     (about 32 items per sample, at least four 16-channel chunks per range), the layers of the 256 x 256 workload that reach the 16 x 16-region form

@@ -90,6 +90,23 @@ def test_hip_loss_and_gradients_match_the_reference(golden, loss_name, B, H, W):
 
 
 @pytest.mark.gpu
+@pytest.mark.parametrize("B,H,W", [(2, 64, 64), (1, 36, 44)])
+def test_hip_forward_on_the_inference_kernels_is_the_inference_lsid_bit_for_bit(monkeypatch, B, H, W):
+    """Training runs the launch list the inference LSID records (lsid.lsid_forward_hip): with the F(4x4) forward kernels allowed, as inference
+    has them, the outputs are equal bit for bit.  At 64 x 64 the stages cover wino4, wino2 and direct."""
+    from noisediff_amd import LSID, lsid, lsid_train
+    monkeypatch.setattr(lsid_train, "WINO4_FORWARD", True)
+    monkeypatch.setattr(lsid, "WINO4", True)
+    net = _hip_net()
+    inference = LSID(None)
+    inference.load_state_dict(net.state_dict(), strict=True)
+    inference = inference.to(DEV).eval()
+    x = _data(B, H, W)[0].to(DEV)
+    with torch.no_grad():
+        assert torch.equal(net(x), inference(x))
+
+
+@pytest.mark.gpu
 def test_hip_gradients_at_the_training_size_match_float64():
     """B = 4, 256 x 256 (script.sh:17's crop and batch), the L1 loss's gradient at the float64 output fed to both runs: every parameter gradient
     within 1e-4 of its max |g| of float64 PyTorch.  (2e-5 is out of reach of fp32 here: PyTorch's own fp32 path is 6.3e-5 away on its worst
