@@ -15,14 +15,16 @@ step over the whole per-GPU batch: the captured graph [write t -> time MLP -> U-
 fused posterior/noise update -> advance] -- the unit the 1000-step sampler repeats 1000 times with
 identical cost.  K steps are timed after W warm-up steps; one sampled patch = T = 1000 such steps, so
     value = n_gpus * batch_per_gpu / (T * seconds_per_step)       [patches/s, whole job].
-`--full` instead times complete 1000-step .sample() calls (K = number of calls).
+`--sample-calls` instead times complete 1000-step .sample() calls (K = number of calls).
 The W + K steps are the first steps of one sample (seed 1), started again should they run past its last step, so that the same
 arguments time the same steps; `--dump-outputs DIR` writes what the last of them returned -- x_t after it and the network output
-(`--full`: the last sample() call's result) -- as DIR/<name>.npy, float32, for comparing two builds output for output.
+(`--sample-calls`: the last sample() call's result) -- as DIR/<name>.npy, float32, for comparing two builds output for output.
 
-Also on the JSON line: `roofline` for the dominant kernel family (conv3x3: exact-fp32 MFMA bound)
-measured with HIP events on the library's stream in a separate instrumented pass over the same
-steps, and `cpu_baseline`: the CPU oracle's p_sample step timed on this box's host cores.
+A plain run does only what the headline needs: set-up, the untimed soak, the W warm-up and K timed steps, the dump, the JSON line.
+`--full` adds, behind the timed steps: `full_sample` (N = 1), one complete sample() call timed on the host clock; `roofline`
+(rank 0) for the dominant kernel family (conv3x3: exact-fp32 MFMA bound) measured with HIP events on the library's stream in a
+separate instrumented pass over the same steps; and `cpu_baseline` (N = 1): the CPU oracle's p_sample step timed on this box's
+host cores.  `--no-full-sample`, `--no-roofline` and `--no-cpu` leave one of them out.
 """
 from __future__ import annotations
 
@@ -60,19 +62,21 @@ def parse():
     ap.add_argument("--config", choices=["cfg2", "cfg3", "cfg4", "ref48"], default=None,
                     help="BASELINE.json presets: cfg2 d64/128x128/B16 DDPM; cfg3 (default workload) d64/256x256/B16 per GPU DDPM; "
                          "cfg4 d128 + mid attention/256x256/B8 per GPU/250-step DDIM")
-    ap.add_argument("--full", action="store_true", help="time whole 1000-step sample() calls instead of K steps")
-    ap.add_argument("--no-cpu", action="store_true", help="skip the CPU baseline leg")
-    ap.add_argument("--no-roofline", action="store_true")
+    ap.add_argument("--sample-calls", action="store_true", help="time whole 1000-step sample() calls instead of K steps")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure what the headline does not need: one complete sample() call, the roofline pass and the CPU baseline")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: skip the CPU baseline leg")
+    ap.add_argument("--no-roofline", action="store_true", help="with --full: skip the roofline pass")
     ap.add_argument("--eager", action="store_true", help="launch kernels one by one instead of replaying the hipGraph")
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend (nccl == RCCL on ROCm; gloo for plumbing tests)")
     ap.add_argument("--one-device", action="store_true", help="testing only: every rank uses cuda:0 (single-GPU box)")
     ap.add_argument("--broadcast", choices=["weights", "plan-slices", "arena"], default="weights",
                     help="what the one collective carries: the raw fp32 weights (every rank packs its arena), the packed slices the plan reads, the whole packed arena")
     ap.add_argument("--soak-s", type=float, default=3.0, help="seconds of untimed step replays before the W warm-up steps")
-    ap.add_argument("--no-full-sample", action="store_true", help="skip the one complete sample() call timed behind the K-step leg (N = 1 only)")
+    ap.add_argument("--no-full-sample", action="store_true", help="with --full: skip the one complete sample() call timed behind the K-step leg (N = 1 only)")
     ap.add_argument("--no-alt", action="store_true", help="accepted and ignored (r4 timed a second product form here; there is one form since r5)")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
-                    help="after the timed steps, write what the last timed step (or, with --full, the last sample() call) returned as DIR/<name>.npy")
+                    help="after the timed steps, write what the last timed step (or, with --sample-calls, the last sample() call) returned as DIR/<name>.npy")
     return ap.parse_args()
 
 
@@ -426,8 +430,8 @@ def roofline(a, loop, plan, L, per_step):
         "hbm_frac_at_algorithmic_bytes": d["bytes"] / (d["ms"] * 1e-3) / 1e9 / PEAK_HBM_GBS,
         "all_conv3x3": {"algorithmic_tflops": tot_flop / (tot_ms * 1e-3) / 1e12, "executed_tflops": tot_exec / (tot_ms * 1e-3) / 1e12,
                         "executed_frac": tot_exec / (tot_ms * 1e-3) / 1e12 / PEAK_FP32_MFMA_TFLOPS,
-                        "ms_per_step": tot_ms / n_inst, "share_of_step": (tot_ms / n_inst) / (per_step * 1e3) if not a.full else None},
-        "whole_step": None if (unit is None or a.full) else {
+                        "ms_per_step": tot_ms / n_inst, "share_of_step": (tot_ms / n_inst) / (per_step * 1e3) if not a.sample_calls else None},
+        "whole_step": None if (unit is None or a.sample_calls) else {
             "algorithmic_gflop_per_patch_step": unit, "algorithmic_tflops": a.batch * unit / per_step / 1e3,
             "algorithmic_frac_of_fp32_peak": a.batch * unit / per_step / 1e3 / PEAK_FP32_MFMA_TFLOPS,
             "executed_gflop_per_step": exec_gf, "executed_tflops": exec_gf / per_step / 1e3,
@@ -541,7 +545,7 @@ def main():
         torch.cuda.synchronize(dev)
 
     soak_steps, timed_restarts, own_restarts = 0, None, None
-    if a.full:
+    if a.sample_calls:
         kw = dict(batch_size=B, condition={k: v.to(dev) for k, v in cond.items()})
         for _ in range(a.warmup):
             gd.sample(seed=1, **kw)
@@ -597,13 +601,13 @@ def main():
         value = world * B / (n_sample_steps * per_step)
     dumped = None
     if a.dump_outputs:
-        outputs = {"sample": last} if a.full else {"x": plan.read_nchw(plan.x), "model_out": plan.read_nchw(plan.model_out)}
+        outputs = {"sample": last} if a.sample_calls else {"x": plan.read_nchw(plan.x), "model_out": plan.read_nchw(plan.model_out)}
         dumped = dump_outputs(a.dump_outputs, outputs if world == 1 else {f"{k}_rank{rank}": v for k, v in outputs.items()}, DUMP_BYTES // world)
     if world > 1:
         # every rank timed the same K steps between the same two barriers; its own GPU-side time for them (HIP events on the
         # library's stream around a second, untimed-by-the-metric replay of K steps) tells a slow rank from a slow barrier
         own_ms = None
-        if not a.full:
+        if not a.sample_calls:
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             ext = torch.cuda.ExternalStream(plan.e.stream.value, device=dev)
             e0.record(ext)
@@ -617,7 +621,7 @@ def main():
         wall = [float(t[0]) for t in every]
         gpu = [float(t[1]) for t in every]
         per_step = max(wall) * 1e-3
-        value = world * B / per_step if a.full else world * B / (n_sample_steps * per_step)
+        value = world * B / per_step if a.sample_calls else world * B / (n_sample_steps * per_step)
         if bcast is not None:
             try:
                 ver = ".".join(str(v) for v in torch.cuda.nccl.version())
@@ -638,14 +642,14 @@ def main():
         "config": {"workload": f"NoiseDiffNet dim={a.dim}{' + mid Attention' if a.mid_attn else ''}, {S}x{S}x4 patches, " +
                                sampler + " (sigmoid2, pred_v), "
                                f"{B} patches per GPU; a step = " +
-                               ("one full sample() call" if a.full else
+                               ("one full sample() call" if a.sample_calls else
                                 "one reverse-diffusion step (U-Net forward + fused posterior/noise update) over the per-GPU batch; "
                                 f"patches/s = n_gpus*{B}/({n_sample_steps}*s_per_step)"),
                    "global_batch": world * B, "launch": "eager" if a.eager else "hipGraph replay",
                    "noise": "device Philox4x32-10", "untimed_soak_steps": soak_steps,
                    "sample_restarts_timed": timed_restarts},
     }
-    if rank == 0 and world == 1 and not a.full and not a.eager and not a.no_full_sample:
+    if a.full and rank == 0 and world == 1 and not a.sample_calls and not a.eager and not a.no_full_sample:
         # the metric itself, once: ONE complete sample() call (x_T, every reverse step, the final clamp and the NCHW read-back) on the same condition; the
         # K-step figure above extrapolates a step x n_sample_steps, this is the driver-visible check of that extrapolation
         kw = dict(batch_size=B, condition={k: v.to(dev) for k, v in cond.items()})
@@ -664,9 +668,9 @@ def main():
         out["multi_gpu"] = bcast
     if dumped:
         out["dumped_outputs"] = {"dir": a.dump_outputs, "arrays": dumped}
-    if rank == 0 and not a.no_roofline:
+    if a.full and rank == 0 and not a.no_roofline:
         out["roofline"] = roofline(a, loop, plan, L, per_step)
-    if rank == 0 and world == 1 and not a.no_cpu:
+    if a.full and rank == 0 and world == 1 and not a.no_cpu:
         out["cpu_baseline"] = cpu_baseline({k: v for k, v in sd.items() if not k.startswith("mid_attn.")}, a.dim, S, n_sample_steps, B)
         out["config"]["speedup_vs_cpu_baseline"] = value / out["cpu_baseline"]["value"]
     if rank == 0:
