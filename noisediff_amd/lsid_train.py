@@ -69,6 +69,18 @@ def lsid_forward_torch(p: Dict[str, torch.Tensor], x: torch.Tensor) -> torch.Ten
 
 
 # --------------------------------------------------------------------------------------------------------- HIP launches
+def convt2x2_dgrad(run: _Launcher, w: torch.Tensor, d_up: torch.Tensor, ld_up: int, B: int, h: int, w_: int, up_h: int, up_w: int) -> torch.Tensor:
+    """The data gradient (B, h, w_, cin) of ConvTranspose2d(cin, c, 2, s=2) + crop to (up_h, up_w), weight ``w`` (cin, c, 2, 2): a pointwise GEMM
+    over the zero-filled pixel unshuffle of ``d_up`` -- its first c channels, pixel stride ``ld_up``."""
+    cin, c = w.shape[0], w.shape[1]
+    t = run.empty(B, h, w_, cin)
+    src = run.src(d_up, c=4 * c, ld=ld_up)
+    src.unshuffle = 1
+    run.pointwise(src, run.pack_pw(w.reshape(cin, 4 * c).contiguous(), 4 * c, cin, unshuffle_c=c), None, t, B, h * w_, w_, 4 * c, cin, cin,
+                  crop_src=(up_h, up_w))
+    return t
+
+
 def _lsid_hip_backward(P: Dict[str, torch.Tensor], saved: Dict[str, torch.Tensor], grad_out: torch.Tensor, run: _Launcher) -> Dict[str, torch.Tensor]:
     """Weight and bias gradients of every parameter from the raw tensors of the forward, in reverse launch order."""
     lib = run.lib
@@ -125,11 +137,7 @@ def _lsid_hip_backward(P: Dict[str, torch.Tensor], saved: Dict[str, torch.Tensor
         L.call("nd_convt2x2_wgrad_leaky_f32", zp.data_ptr(), cin, dc.data_ptr(), 2 * c, gw.data_ptr(),
                ws(lib.nd_convt2x2_wgrad_workspace_floats(B, hp, wp_, cin, c)).data_ptr(), B, hp, wp_, cin, c, h, w, run.st)
         G[f"up{j}.weight"] = gw
-        wt = P[f"up{j}.weight"].reshape(cin, 4 * c).contiguous()
-        t = run.empty(B, hp, wp_, cin)
-        src = run.src(dc, c=4 * c, ld=2 * c)
-        src.unshuffle = 1
-        run.pointwise(src, run.pack_pw(wt, 4 * c, cin, unshuffle_c=c), None, t, B, hp * wp_, wp_, 4 * c, cin, cin, crop_src=(h, w))
+        t = convt2x2_dgrad(run, P[f"up{j}.weight"], dc, 2 * c, B, hp, wp_, h, w)
         dz = run.join(zp, t, t, cin, None)
     # ---- down path, deepest stage first; dz is the gradient of z5
     d_pool: Optional[torch.Tensor] = None
