@@ -321,6 +321,28 @@ int nd_pointwise_gemm_nhwc_f32(const nd_pointwise* d, void* stream);
  * <= (2 H, 2 W) pixels (H = HW / W), read as its pixel unshuffle with zeros for the rows / columns the forward cropped away; weight packed by
  * nd_pack_pointwise_weight(w.reshape(cin, 4 c) of the ConvTranspose weight (cin, c, 2, 2), ..., cin = 4 c, cout = cin, unshuffle_c = c). */
 int nd_pointwise_gemm_unshuffle_crop_nhwc_f32(const nd_pointwise* d, int src_h, int src_w, void* stream);
+
+/* ------------------------------------------------------------------ scoring of denoised frames (test_denoising.py:220-263,318-343)
+ * Images are fp32 NCHW [B][C][H][W], contiguous.  Results are per image; an image's results do not depend on B and a repeated call gives
+ * the same bits (fixed reduction order, no atomics).  Each call is two launches; the workspace is the caller's.
+ *
+ * nd_image_quality_f32: skimage's peak_signal_noise_ratio and structural_similarity(channel_axis=2, data_range=R) of est against target,
+ * both clipped to [0, R] first (NaN kept), as tensor2im does.  PSNR = 10 log10(R^2 / mse), mse = mean of fl32(fl32(x - y)^2) accumulated in
+ * fp64; SSIM with a 7 x 7 uniform window, cov_norm 49/48, K1 0.01, K2 0.03, window sums and S in fp64, S averaged over the interior
+ * [3, H-3) x [3, W-3), then over channels.  `scale` (may be NULL): per-image fp32 k of nd_illum_scale_f32; est is then read as
+ * clip(fl32(k * clamp(est, 0, 1)), 0, R), the illumination-corrected prediction without a pass over memory.  psnr / ssim / mse: fp64 [B].
+ * H and W must be at least 7 (ND_E_SHAPE).  Workspace: nd_image_quality_workspace_bytes(B, C, H, W) bytes, 8-byte aligned. */
+int64_t nd_image_quality_workspace_bytes(int B, int C, int H, int W);
+int nd_image_quality_f32(const float* est, const float* target, const float* scale, double data_range, double* psnr, double* ssim,
+                         double* mse, void* workspace, int B, int C, int H, int W, void* stream);
+/* IlluminanceCorrect's scale (:252-263): p = clamp(pred, 0, 1), num = sum p s and den = sum p p over the elements with source != 1, in fp64;
+ * k64 = num / den (NaN or inf when den is 0, as the reference), k32 = k64 rounded to fp32.  source_batch: 1 (one source for every image) or
+ * B.  Workspace: nd_illum_scale_workspace_bytes(B, C, H, W) bytes. */
+int64_t nd_illum_scale_workspace_bytes(int B, int C, int H, int W);
+int nd_illum_scale_f32(const float* pred, const float* source, int source_batch, float* k32, double* k64, void* workspace,
+                       int B, int C, int H, int W, void* stream);
+/* out = k32[b] * clamp(pred, 0, 1) in fp32: IlluminanceCorrect's output.  out may alias pred. */
+int nd_illum_apply_f32(const float* pred, const float* k32, float* out, int B, int C, int H, int W, void* stream);
 /* (cout, cin) row-major (Linear / 1x1 conv weight) -> [cinP/4][coutP][4]; `unshuffle_c` > 0
  * permutes K from (c p1 p2) to (p1 p2 c) for a pixel-unshuffled input with c = unshuffle_c. */
 int64_t nd_pack_pointwise_weight_floats(int cin, int cout);

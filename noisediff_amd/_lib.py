@@ -69,7 +69,7 @@ class SamplerState(C.Structure):
                 ("n_steps", C.c_int32), ("B", C.c_int32)]
 
 
-i32, i64, u64, vp, f32 = C.c_int, C.c_int64, C.c_uint64, C.c_void_p, C.c_float
+i32, i64, u64, vp, f32, f64 = C.c_int, C.c_int64, C.c_uint64, C.c_void_p, C.c_float, C.c_double
 
 # name -> (restype, argtypes); everything include/noisediff_hip.h declares
 SIGNATURES = {
@@ -194,6 +194,11 @@ SIGNATURES = {
     "nd_convt2x2_wgrad_workspace_floats": (i64, [i32, i32, i32, i32, i32]),
     "nd_convt2x2_wgrad_leaky_f32": (i32, [vp, i32, vp, i32, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp]),
     "nd_pointwise_gemm_unshuffle_crop_nhwc_f32": (i32, [C.POINTER(Pointwise), i32, i32, vp]),
+    "nd_image_quality_workspace_bytes": (i64, [i32, i32, i32, i32]),
+    "nd_image_quality_f32": (i32, [vp, vp, vp, f64, vp, vp, vp, vp, i32, i32, i32, i32, vp]),
+    "nd_illum_scale_workspace_bytes": (i64, [i32, i32, i32, i32]),
+    "nd_illum_scale_f32": (i32, [vp, vp, i32, vp, vp, vp, i32, i32, i32, i32, vp]),
+    "nd_illum_apply_f32": (i32, [vp, vp, vp, i32, i32, i32, i32, vp]),
 }
 
 _UNCHECKED = {"nd_version", "nd_last_error", "nd_stream_device", "nd_conv3x3_wgrad_form", "nd_adam_chunk_elements", "nd_conv7x7_c4_wgrad_workspace_floats", "nd_conv3x3_stat_slots", "nd_conv3x3_tiling_id", "nd_pack_conv3x3_weight_floats",
@@ -201,7 +206,7 @@ _UNCHECKED = {"nd_version", "nd_last_error", "nd_stream_device", "nd_conv3x3_wgr
               "nd_pack_conv3x3_wino_weight_floats", "nd_pack_conv3x3_wino4_weight_floats", "nd_conv3x3_wino4_splitk_plan", "nd_conv3x3_wino4_16_splitk_plan", "nd_conv3x3_wino4_splitk_workspace_floats", "nd_token_sum_workspace_floats", "nd_cond_step_lds_bytes", "nd_conv3x3_wgrad_workspace_floats",
               "nd_groupnorm_train_workspace_floats", "nd_linear_wgrad_workspace_floats",
               "nd_layernorm_train_workspace_floats", "nd_groupnorm_silu_train_workspace_floats", "nd_conv3x3_wgrad_cat_workspace_floats",
-              "nd_convt2x2_wgrad_workspace_floats"}
+              "nd_convt2x2_wgrad_workspace_floats", "nd_image_quality_workspace_bytes", "nd_illum_scale_workspace_bytes"}
 
 _lib: Optional[C.CDLL] = None
 
