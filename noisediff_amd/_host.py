@@ -1,0 +1,71 @@
+"""Host-side helpers of everything that launches the HIP library on torch tensors and torch's streams -- inference (lsid, metrics) and training
+(train) alike: the stream and device of a launch, fp32 allocations and workspaces, the "no CPU path" check, and the one rule that picks the kernel
+of a 3x3 convolution outside the sampling engine.  Imports only ``torch`` and ``_lib``; needs neither a GPU nor the built library at import time.
+"""
+from __future__ import annotations
+
+import ctypes as C
+from typing import Optional
+
+import torch
+
+from . import _lib as L
+
+
+class _Nop:
+    def __enter__(self):
+        return None
+
+    def __exit__(self, *a):
+        return False
+
+
+_NOP = _Nop()
+
+
+def _on(device: torch.device):
+    """The library launches on the CURRENT device: switch only when the tensors live elsewhere (the context manager costs ~10 us of
+    host time per call, and a training step makes several hundred calls)."""
+    return _NOP if device.index == torch.cuda.current_device() else torch.cuda.device(device)
+
+
+def _stream(device: Optional[torch.device] = None) -> C.c_void_p:
+    """torch's current stream OF THE TENSORS' DEVICE (not of the current device: a caller may sit on another GPU)."""
+    idx = torch.cuda.current_device() if device is None or device.index is None else device.index
+    return C.c_void_p(torch._C._cuda_getCurrentRawStream(idx))         # (torch.cuda.current_stream(...).cuda_stream builds a Stream object: 5 us, x 1800 per step)
+
+
+def _need_gpu(t: torch.Tensor) -> None:
+    """There is no fallback: a CPU tensor raises."""
+    if t.device.type != "cuda":
+        raise L.HipError(f"noisediff_amd.train runs on the HIP library only; tensor is on {t.device} and there is no CPU path")
+
+
+def _empty(shape, device: torch.device, **kw) -> torch.Tensor:
+    """An uninitialised fp32 tensor on the tensors' device."""
+    return torch.empty(shape, dtype=torch.float32, device=device, **kw)
+
+
+def _workspace(entry: str, device: torch.device, *dims) -> torch.Tensor:
+    """A buffer sized by the library's own rule ``entry`` for these dimensions: the scratch of one launch (``nd_*_workspace_floats``) or a packed
+    weight (``nd_pack_*_floats``).  One call of the entry per buffer."""
+    return torch.empty(int(getattr(L.load(), entry)(*dims)), dtype=torch.float32, device=device)
+
+
+def conv3x3_kind(B: int, H: int, W: int, cin: int, cout: int, c0: int, c1: int, ld: int, wino4: bool = True) -> str:
+    """The kernel of a 3x3 convolution outside the sampling engine: 'wino4', 'wino2', 'wino' (F(2x2,3x3) past wino2's limits) or 'direct'.
+    ``c0`` / ``c1``: the channels of the two sources (c1 = 0: one source); ``ld``: the pixel stride the source-size limits are computed with;
+    ``wino4`` False: never the F(4x4,3x3) kernel.  Host-only: needs no library."""
+    wino = H >= 16 and W >= 16 and cin % 8 == 0
+    if (wino4 and wino and cin > 16 and cin % 4 == 0 and cout % 4 == 0 and cout <= 2048 and W >= 32 and (W % 32 == 0 or W >= 96) and W <= 2048
+            and (c1 == 0 or c0 % 16 == 0) and B * H * W + W + 2 < (1 << 24) and (B * H * W + W + 2) * 4 * ld < (1 << 30) - (1 << 16)):
+        return "wino4"
+    if wino and (c1 == 0 or c0 % 32 == 0) and B * H * W < (1 << 24) and B * H * W * 4 * ld < (1 << 31):
+        return "wino2"
+    return "wino" if wino else "direct"
+
+
+CONV3X3_PACK = {"wino4": "nd_pack_conv3x3_wino4_weight", "wino2": "nd_pack_conv3x3_wino_weight", "wino": "nd_pack_conv3x3_wino_weight",
+                "direct": "nd_pack_conv3x3_weight"}
+CONV3X3_ENTRY = {"wino4": "nd_conv3x3_wino4_nhwc_f32", "wino2": "nd_conv3x3_wino2_nhwc_f32", "wino": "nd_conv3x3_wino_nhwc_f32",
+                 "direct": "nd_conv3x3_nhwc_f32"}

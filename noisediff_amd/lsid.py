@@ -3,7 +3,7 @@ consumer of the synthesized noise (BASELINE config 5).
 
 Same plug-in contract as NoiseDiffNet: ``LSID(args)``, reference state-dict names/shapes (strict load),
 ``forward(x)`` with an NCHW (B, 4, H, W) tensor.  It reuses the sampler's kernels: every ``Conv2d(3x3)`` is
-``nd_conv3x3_{wino4, wino2, wino, direct}_nhwc_f32`` (chosen by ``train.conv3x3_kind``) storing the *pre-activation*; ``LeakyReLU(0.2)`` is
+``nd_conv3x3_{wino4, wino2, wino, direct}_nhwc_f32`` (chosen by ``_host.conv3x3_kind``) storing the *pre-activation*; ``LeakyReLU(0.2)`` is
 applied by the consumer's prologue (ND_PRO_LEAKY; it commutes with max-pooling, and ND_PRO_LEAKY_SECOND handles
 ``cat(up(x), skip)`` where only the skip is activated); ``ConvTranspose2d(2, s=2)`` is one pointwise GEMM to
 4*C' columns with a pixel-shuffle store that also performs the crop.  Inference only; no CPU fallback.
@@ -23,7 +23,7 @@ from torch import nn
 from . import _lib as L
 from .net import _attach, _init
 from .spec import LSID_STAGES, lsid_param_spec
-from .train import CONV3X3_ENTRY, CONV3X3_PACK, _stream, conv3x3_kind
+from ._host import CONV3X3_ENTRY, CONV3X3_PACK, _stream, conv3x3_kind
 
 WINO4 = os.environ.get("ND_WINO4", "1") != "0"           # A-B knob: 0 = never the F(4x4,3x3) kernel
 

@@ -23,7 +23,7 @@ import torch
 from torch import nn
 
 from . import _lib as L
-from .train import _stream
+from ._host import _stream
 
 WINDOW = 7         # structural_similarity's default win_size
 

@@ -29,11 +29,13 @@ from __future__ import annotations
 import ctypes as C
 from typing import Dict, Optional
 
+import numpy as np
 import torch
 from torch.autograd.function import once_differentiable
 from torch import nn
 
 from . import _lib as L
+from ._host import CONV3X3_ENTRY, CONV3X3_PACK, _empty, _need_gpu, _on, _stream, _workspace, conv3x3_kind
 
 
 def _nhwc(t: torch.Tensor) -> torch.Tensor:
@@ -43,49 +45,22 @@ def _nhwc(t: torch.Tensor) -> torch.Tensor:
     return t.contiguous(memory_format=torch.channels_last)
 
 
-class _Nop:
-    def __enter__(self):
-        return None
-
-    def __exit__(self, *a):
-        return False
-
-
-_NOP = _Nop()
-
-
-def _on(device: torch.device):
-    """The library launches on the CURRENT device: switch only when the tensors live elsewhere (the context manager costs ~10 us of
-    host time per call, and a training step makes several hundred calls)."""
-    return _NOP if device.index == torch.cuda.current_device() else torch.cuda.device(device)
-
-
-def _stream(device: Optional[torch.device] = None) -> C.c_void_p:
-    """torch's current stream OF THE TENSORS' DEVICE (not of the current device: a caller may sit on another GPU)."""
-    idx = torch.cuda.current_device() if device is None or device.index is None else device.index
-    return C.c_void_p(torch._C._cuda_getCurrentRawStream(idx))         # (torch.cuda.current_stream(...).cuda_stream builds a Stream object: 5 us, x 1800 per step)
-
-
 _SPLIT_K = __import__("os").environ.get("ND_TRAIN_SPLITK", "1") != "0"      # A/B knob (tools/): 0 = never the split-K form of conv3x3_wino4
 
 
-def conv3x3_kind(B: int, H: int, W: int, cin: int, cout: int, c0: int, c1: int, ld: int, wino4: bool = True) -> str:
-    """The kernel of a 3x3 convolution outside the sampling engine: 'wino4', 'wino2', 'wino' (F(2x2,3x3) past wino2's limits) or 'direct'.
-    ``c0`` / ``c1``: the channels of the two sources (c1 = 0: one source); ``ld``: the pixel stride the source-size limits are computed with;
-    ``wino4`` False: never the F(4x4,3x3) kernel.  Host-only: needs no library."""
-    wino = H >= 16 and W >= 16 and cin % 8 == 0
-    if (wino4 and wino and cin > 16 and cin % 4 == 0 and cout % 4 == 0 and cout <= 2048 and W >= 32 and (W % 32 == 0 or W >= 96) and W <= 2048
-            and (c1 == 0 or c0 % 16 == 0) and B * H * W + W + 2 < (1 << 24) and (B * H * W + W + 2) * 4 * ld < (1 << 30) - (1 << 16)):
-        return "wino4"
-    if wino and (c1 == 0 or c0 % 32 == 0) and B * H * W < (1 << 24) and B * H * W * 4 * ld < (1 << 31):
-        return "wino2"
-    return "wino" if wino else "direct"
+def _pack_pointwise(w_ptr: int, packed_ptr: int, cin: int, cout: int, transposed: bool, st) -> None:
+    """The operand of nd_pointwise_gemm_nhwc_f32 from a Linear / 1x1 weight (cout, cin); ``transposed``: from the FORWARD weight (cin, cout) of the layer
+    whose data gradient dx = dy @ w the GEMM is, read in place."""
+    if transposed:
+        L.call("nd_pack_pointwise_weight_t", w_ptr, packed_ptr, cin, cout, st)
+    else:
+        L.call("nd_pack_pointwise_weight", w_ptr, packed_ptr, cin, cout, 0, st)       # (0: no pixel-unshuffled input channels)
 
 
-CONV3X3_PACK = {"wino4": "nd_pack_conv3x3_wino4_weight", "wino2": "nd_pack_conv3x3_wino_weight", "wino": "nd_pack_conv3x3_wino_weight",
-                "direct": "nd_pack_conv3x3_weight"}
-CONV3X3_ENTRY = {"wino4": "nd_conv3x3_wino4_nhwc_f32", "wino2": "nd_conv3x3_wino2_nhwc_f32", "wino": "nd_conv3x3_wino_nhwc_f32",
-                 "direct": "nd_conv3x3_nhwc_f32"}
+def _pack_conv3x3(kind: str, w_ptr: int, packed_ptr: int, cin: int, cout: int, dgrad: bool, st) -> None:
+    """The operand of the ``kind`` kernel (conv3x3_kind) from an OIHW weight; ``dgrad``: the data gradient's, read in place from the FORWARD weight
+    (cin / cout are the operator's)."""
+    L.call(CONV3X3_PACK[kind] + ("_dgrad" if dgrad else ""), w_ptr, packed_ptr, cin, cout, st)
 
 
 def _conv3x3_nhwc(x: torch.Tensor, w_oihw: torch.Tensor, bias: Optional[torch.Tensor], dgrad: bool = False, stats: bool = False,
@@ -105,8 +80,7 @@ def _conv3x3_nhwc(x: torch.Tensor, w_oihw: torch.Tensor, bias: Optional[torch.Te
     cout = w_oihw.shape[1 if dgrad else 0]
     if w_oihw.shape[0 if dgrad else 1] != cin:
         raise ValueError(f"conv3x3: x {tuple(x.shape)} does not match weight {tuple(w_oihw.shape)}" + (" (data gradient)" if dgrad else ""))
-    if x.device.type != "cuda":
-        raise L.HipError(f"noisediff_amd.train runs on the HIP library only; tensor is on {x.device} and there is no CPU path")
+    _need_gpu(x)
     if cin % 4 or cout % 4:
         raise L.HipError(f"conv3x3 on the HIP library needs channel counts that are multiples of 4 (cin={cin}, cout={cout})")
     st = _stream(x.device)
@@ -114,19 +88,19 @@ def _conv3x3_nhwc(x: torch.Tensor, w_oihw: torch.Tensor, bias: Optional[torch.Te
     cached = wbase is not None
     w_oihw = w_oihw.detach().to(torch.float32).contiguous()
     with _on(x.device):
-        out = torch.empty((B, cout, H, W), dtype=torch.float32, device=x.device, memory_format=torch.channels_last)
+        out = _empty((B, cout, H, W), x.device, memory_format=torch.channels_last)
         kind = conv3x3_kind(B, H, W, cin, cout, c0, cin - c0, cin)       # ld = c0 + c1 for a concat: stricter than the kernel's widest-source bound
         if x1 is not None and (kind != "wino4" or c0 % 16 or x1.shape[1] % 16):
             raise L.HipError(f"conv3x3 over two sources needs the F(4x4) kernel and sources of whole 16-channel chunks ({c0} + {x1.shape[1]} channels, {H}x{W})")
         kind = "direct" if kind == "wino" else kind                      # past wino2's limits: the direct kernel
         if kind == "direct" and cin % 8:
             raise L.HipError(f"conv3x3 on the HIP library needs cin % 8 == 0 (cin={cin})")
-        pack, entry, wino4 = CONV3X3_PACK[kind], CONV3X3_ENTRY[kind], kind == "wino4"
+        wino4 = kind == "wino4"
         if wino4 and cached:
             wptr = _pack_cache(x.device).get(w_oihw, cin, cout, dgrad, st, kind="w4", base=wbase)
         else:
-            wp = torch.empty(int(getattr(lib, pack + "_floats")(cin, cout)), dtype=torch.float32, device=x.device)
-            L.call(pack + ("_dgrad" if dgrad else ""), w_oihw.data_ptr(), wp.data_ptr(), cin, cout, st)
+            wp = _workspace(CONV3X3_PACK[kind] + "_floats", x.device, cin, cout)
+            _pack_conv3x3(kind, w_oihw.data_ptr(), wp.data_ptr(), cin, cout, dgrad, st)
             wptr = wp.data_ptr()
         d = L.Conv3x3()
         d.src.p0, d.src.c0, d.src.ld0, d.src.mode = x.data_ptr(), c0, c0, L.PRO_NONE
@@ -142,17 +116,40 @@ def _conv3x3_nhwc(x: torch.Tensor, w_oihw: torch.Tensor, bias: Optional[torch.Te
         if stats:                                                 # (the split-K form leaves the same slots from its reduction kernel)
             slots = int(lib.nd_conv3x3_wino4_stat_slots(H, W) if wino4 else lib.nd_conv3x3_wino_stat_slots(H, W) if kind == "wino2"
                         else lib.nd_conv3x3_stat_slots(H, W, cout, B))
-            st_t = torch.empty((B, slots, cout, 2), dtype=torch.float32, device=x.device)
-            sc_t = torch.empty(slots, dtype=torch.float32, device=x.device)
+            st_t, sc_t = _empty((B, slots, cout, 2), x.device), _empty(slots, x.device)
             d.stats, d.slot_count = st_t.data_ptr(), sc_t.data_ptr()
         if splits > 1:      # few (sample, region, cout tile) items for 256 CUs (the deep layers at training batch sizes): cut along cin
-            ws = torch.empty(int(lib.nd_conv3x3_wino4_splitk_workspace_floats(B, H, W, cout, splits)), dtype=torch.float32, device=x.device)
+            ws = _workspace("nd_conv3x3_wino4_splitk_workspace_floats", x.device, B, H, W, cout, splits)
             L.call("nd_conv3x3_wino4_splitk_nhwc_f32", C.byref(d), ws.data_ptr(), splits, st)
         else:
-            L.call(entry, C.byref(d), st)
+            L.call(CONV3X3_ENTRY[kind], C.byref(d), st)
         # wp / b are dropped on return: safe, because the kernels were enqueued on torch's CURRENT stream and the caching
         # allocator reuses a block only for work that is enqueued later on that same stream
     return (out, st_t, sc_t) if stats else out
+
+
+def _conv3x3_forward(ctx, xn, weight, bias, want_stats, x1=None):
+    """The forward of Conv3x3Function / Conv3x3CatFunction (``x1``: the second source); ``want_stats``: (y, st, sc) with the statistics epilogue."""
+    ctx.has_bias = bias is not None
+    if not want_stats:
+        return _conv3x3_nhwc(xn, weight, bias, x1=x1)
+    y, st, sc = _conv3x3_nhwc(xn, weight, bias, stats=True, x1=x1)
+    ctx.mark_non_differentiable(st, sc)
+    ctx.set_materialize_grads(False)                             # no zero tensors for the statistics outputs' (never used) gradients
+    return y, st, sc
+
+
+def _conv3x3_wgrad(xn: torch.Tensor, g: torch.Tensor, cout: int, want_b: bool):
+    """(dW (cout, cin, 3, 3), db or None) of a 3x3 convolution from its input ``xn`` and its output gradient ``g`` (both channels_last) on
+    nd_conv3x3_wgrad_nhwc_f32; the bias gradient falls out of the staged dY tiles."""
+    B, cin, H, W = xn.shape
+    dev = xn.device
+    with _on(dev):
+        dw = _empty((cout, cin, 3, 3), dev)
+        db = _empty(cout, dev) if want_b else None
+        ws = _workspace("nd_conv3x3_wgrad_workspace_floats", dev, B, H, W, cin, cout)
+        L.call("nd_conv3x3_wgrad_nhwc_f32", xn.data_ptr(), cin, g.data_ptr(), cout, dw.data_ptr(), L.ptr(db), ws.data_ptr(), B, H, W, cin, cout, _stream(dev))
+    return dw, db
 
 
 class Conv3x3Function(torch.autograd.Function):
@@ -162,15 +159,7 @@ class Conv3x3Function(torch.autograd.Function):
     def forward(ctx, x, weight, bias, want_stats=False):
         xn = _nhwc(x)
         ctx.save_for_backward(xn, weight)
-        ctx.has_bias = bias is not None
-        ctx.n_out = 1
-        if not want_stats:
-            return _conv3x3_nhwc(xn, weight, bias)
-        y, st, sc = _conv3x3_nhwc(xn, weight, bias, stats=True)
-        ctx.mark_non_differentiable(st, sc)
-        ctx.set_materialize_grads(False)                         # no zero tensors for the statistics outputs' (never used) gradients
-        ctx.n_out = 3
-        return y, st, sc
+        return _conv3x3_forward(ctx, xn, weight, bias, want_stats)
 
     @staticmethod
     @once_differentiable
@@ -178,31 +167,27 @@ class Conv3x3Function(torch.autograd.Function):
         xn, weight = ctx.saved_tensors
         if grad_out is None:                                     # (materialize_grads is off for the statistics variant)
             return None, None, None, None
-        lib = L.load()
         g = _nhwc(grad_out)
-        B, cin, H, W = xn.shape
-        cout = weight.shape[0]
         grad_x = grad_w = grad_b = None
         if ctx.needs_input_grad[0]:
             # dL/dx = conv(dL/dy, flip(w)^T): the forward operator itself, its weight packed straight from the forward layer's
             grad_x = _conv3x3_nhwc(g, weight, None, dgrad=True)
         want_b = ctx.has_bias and ctx.needs_input_grad[2]
         if ctx.needs_input_grad[1]:
-            with _on(xn.device):
-                grad_w = torch.empty((cout, cin, 3, 3), dtype=torch.float32, device=xn.device)
-                grad_b = torch.empty(cout, dtype=torch.float32, device=xn.device) if want_b else None     # falls out of the staged dY tiles
-                ws = torch.empty(int(lib.nd_conv3x3_wgrad_workspace_floats(B, H, W, cin, cout)), dtype=torch.float32, device=xn.device)
-                L.call("nd_conv3x3_wgrad_nhwc_f32", xn.data_ptr(), cin, g.data_ptr(), cout, grad_w.data_ptr(),
-                       grad_b.data_ptr() if want_b else None, ws.data_ptr(), B, H, W, cin, cout, _stream(xn.device))
+            grad_w, grad_b = _conv3x3_wgrad(xn, g, weight.shape[0], want_b)
         elif want_b:
             grad_b = g.sum(dim=(0, 2, 3))
         return grad_x, grad_w, grad_b, None
 
 
-def conv3x3(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """Differentiable F.conv2d(x, weight, bias, padding=1) for 3x3 kernels on the HIP library."""
+def _check_conv3x3(x: torch.Tensor, weight: torch.Tensor) -> None:
     if tuple(weight.shape[2:]) != (3, 3) or x.dim() != 4 or x.shape[1] != weight.shape[1]:
         raise ValueError(f"conv3x3: x {tuple(x.shape)} / weight {tuple(weight.shape)} is not a 3x3 convolution")
+
+
+def conv3x3(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Differentiable F.conv2d(x, weight, bias, padding=1) for 3x3 kernels on the HIP library."""
+    _check_conv3x3(x, weight)
     return Conv3x3Function.apply(x, weight, bias)
 
 
@@ -210,8 +195,7 @@ def conv3x3_with_stats(x: torch.Tensor, weight: torch.Tensor, bias: Optional[tor
     """conv3x3 plus the kernel's GroupNorm statistics epilogue: (y, (st, sc)) for ``group_norm_silu(y, ..., conv_stats=)`` -- the norm then needs no
     pass of its own over y for its moments, as in the sampling engine (Block: conv -> statistics -> finalize -> apply); the split-K form of the deep
     layers leaves the same slots from its reduction kernel."""
-    if tuple(weight.shape[2:]) != (3, 3) or x.dim() != 4 or x.shape[1] != weight.shape[1]:
-        raise ValueError(f"conv3x3: x {tuple(x.shape)} / weight {tuple(weight.shape)} is not a 3x3 convolution")
+    _check_conv3x3(x, weight)
     y, st, sc = Conv3x3Function.apply(x, weight, bias, True)
     return y, (st, sc)
 
@@ -236,13 +220,7 @@ class Conv3x3CatFunction(torch.autograd.Function):
     def forward(ctx, x0, x1, weight, bias, want_stats=False):
         a, b = _nhwc(x0), _nhwc(x1)
         ctx.save_for_backward(a, b, weight)
-        ctx.has_bias = bias is not None
-        if not want_stats:
-            return _conv3x3_nhwc(a, weight, bias, x1=b)
-        y, st, sc = _conv3x3_nhwc(a, weight, bias, stats=True, x1=b)
-        ctx.mark_non_differentiable(st, sc)
-        ctx.set_materialize_grads(False)
-        return y, st, sc
+        return _conv3x3_forward(ctx, a, weight, bias, want_stats, x1=b)
 
     @staticmethod
     @once_differentiable
@@ -261,23 +239,15 @@ class Conv3x3CatFunction(torch.autograd.Function):
         want_b = ctx.has_bias and ctx.needs_input_grad[3]
         if ctx.needs_input_grad[2] and H % 4 == 0 and W % 16 == 0 and c0 % 32 == 0 and c1 % 32 == 0 and cout % 16 == 0 and lib.nd_conv3x3_wgrad_form(-1) != 1:
             with _on(a.device):                                          # the Winograd-domain forms read a cin block from either source: ONE weight gradient
-                grad_w = torch.empty((cout, c0 + c1, 3, 3), dtype=torch.float32, device=a.device)
-                grad_b = torch.empty(cout, dtype=torch.float32, device=a.device) if want_b else None
-                ws = torch.empty(int(lib.nd_conv3x3_wgrad_workspace_floats(B, H, W, c0 + c1, cout)), dtype=torch.float32, device=a.device)
+                grad_w = _empty((cout, c0 + c1, 3, 3), a.device)
+                grad_b = _empty(cout, a.device) if want_b else None
+                ws = _workspace("nd_conv3x3_wgrad_workspace_floats", a.device, B, H, W, c0 + c1, cout)
                 L.call("nd_conv3x3_wgrad_cat_nhwc_f32", a.data_ptr(), c0, c0, b.data_ptr(), c1, c1, g.data_ptr(), cout, grad_w.data_ptr(),
-                       grad_b.data_ptr() if want_b else None, ws.data_ptr(), B, H, W, cout, _stream(a.device))
-        elif ctx.needs_input_grad[2]:
-            with _on(a.device):
-                parts = []
-                for i, (src, c) in enumerate(((a, c0), (b, c1))):
-                    dw = torch.empty((cout, c, 3, 3), dtype=torch.float32, device=a.device)
-                    if i == 0 and want_b:
-                        grad_b = torch.empty(cout, dtype=torch.float32, device=a.device)
-                    ws = torch.empty(int(lib.nd_conv3x3_wgrad_workspace_floats(B, H, W, c, cout)), dtype=torch.float32, device=a.device)
-                    L.call("nd_conv3x3_wgrad_nhwc_f32", src.data_ptr(), c, g.data_ptr(), cout, dw.data_ptr(),
-                           grad_b.data_ptr() if (i == 0 and want_b) else None, ws.data_ptr(), B, H, W, c, cout, _stream(a.device))
-                    parts.append(dw)
-                grad_w = torch.cat(parts, dim=1)
+                       L.ptr(grad_b), ws.data_ptr(), B, H, W, cout, _stream(a.device))
+        elif ctx.needs_input_grad[2]:                                    # per source, joined along cin; the bias gradient from the first source's launch
+            dw0, grad_b = _conv3x3_wgrad(a, g, cout, want_b)
+            dw1, _ = _conv3x3_wgrad(b, g, cout, False)
+            grad_w = torch.cat((dw0, dw1), dim=1)
         elif want_b:
             grad_b = g.sum(dim=(0, 2, 3))
         return gx0, gx1, grad_w, grad_b, None
@@ -299,16 +269,14 @@ class GroupNormFunction(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, weight, bias, groups, eps):
-        lib = L.load()
         xn = _nhwc(x)
-        if xn.device.type != "cuda":
-            raise L.HipError(f"noisediff_amd.train runs on the HIP library only; tensor is on {xn.device} and there is no CPU path")
+        _need_gpu(xn)
         B, C_, H, W = xn.shape
         st = _stream(xn.device)
         with _on(xn.device):
             y = torch.empty_like(xn, memory_format=torch.channels_last)
-            mean_rstd = torch.empty((B, groups, 2), dtype=torch.float32, device=xn.device)
-            ws = torch.empty(int(lib.nd_groupnorm_train_workspace_floats(B, H * W, C_)), dtype=torch.float32, device=xn.device)
+            mean_rstd = _empty((B, groups, 2), xn.device)
+            ws = _workspace("nd_groupnorm_train_workspace_floats", xn.device, B, H * W, C_)
             w32, b32 = weight.detach().float().contiguous(), bias.detach().float().contiguous()
             L.call("nd_groupnorm_train_forward_f32", xn.data_ptr(), C_, w32.data_ptr(), b32.data_ptr(), y.data_ptr(), C_, mean_rstd.data_ptr(),
                    ws.data_ptr(), B, H * W, C_, groups, float(eps), st)
@@ -320,14 +288,13 @@ class GroupNormFunction(torch.autograd.Function):
     @once_differentiable
     def backward(ctx, grad_out):
         xn, weight, mean_rstd = ctx.saved_tensors
-        lib = L.load()
         g = _nhwc(grad_out)
         B, C_, H, W = xn.shape
         with _on(xn.device):
             dx = torch.empty_like(xn, memory_format=torch.channels_last)
-            dgamma = torch.empty(C_, dtype=torch.float32, device=xn.device)
-            dbeta = torch.empty(C_, dtype=torch.float32, device=xn.device)
-            ws = torch.empty(int(lib.nd_groupnorm_train_workspace_floats(B, H * W, C_)), dtype=torch.float32, device=xn.device)
+            dgamma = _empty(C_, xn.device)
+            dbeta = _empty(C_, xn.device)
+            ws = _workspace("nd_groupnorm_train_workspace_floats", xn.device, B, H * W, C_)
             w32 = weight.detach().float().contiguous()
             L.call("nd_groupnorm_train_backward_f32", g.data_ptr(), C_, xn.data_ptr(), C_, w32.data_ptr(), mean_rstd.data_ptr(), dx.data_ptr(), C_,
                    dgamma.data_ptr(), dbeta.data_ptr(), ws.data_ptr(), B, H * W, C_, ctx.groups, _stream(xn.device))
@@ -347,18 +314,16 @@ class GroupNormSiLUFunction(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, weight, bias, scale_shift, res, groups, eps, st=None, sc=None):
-        lib = L.load()
         xn = _nhwc(x)
         rn = None if res is None else _nhwc(res)
-        if xn.device.type != "cuda":
-            raise L.HipError(f"noisediff_amd.train runs on the HIP library only; tensor is on {xn.device} and there is no CPU path")
+        _need_gpu(xn)
         B, C_, H, W = xn.shape
         ss = None if scale_shift is None else scale_shift.detach().reshape(B, 2 * C_).float().contiguous()
         with _on(xn.device):
             y = torch.empty_like(xn, memory_format=torch.channels_last)
-            mean_rstd = torch.empty((B, groups, 2), dtype=torch.float32, device=xn.device)
-            mad = torch.empty((B, 3, C_), dtype=torch.float32, device=xn.device)
-            ws = torch.empty(int(lib.nd_groupnorm_silu_train_workspace_floats(B, H * W, C_)), dtype=torch.float32, device=xn.device)
+            mean_rstd = _empty((B, groups, 2), xn.device)
+            mad = _empty((B, 3, C_), xn.device)
+            ws = _workspace("nd_groupnorm_silu_train_workspace_floats", xn.device, B, H * W, C_)
             w32, b32 = weight.detach().float().contiguous(), bias.detach().float().contiguous()
             if st is not None:       # the convolution's statistics epilogue already holds the partial moments: finalize (saving mean / rstd) + one apply pass
                 stp = _stream(xn.device)
@@ -378,15 +343,14 @@ class GroupNormSiLUFunction(torch.autograd.Function):
     @once_differentiable
     def backward(ctx, grad_out):
         xn, weight, bias, mean_rstd, mad, ss = ctx.saved_tensors
-        lib = L.load()
         g = _nhwc(grad_out)
         B, C_, H, W = xn.shape
         with _on(xn.device):
             dx = torch.empty_like(xn, memory_format=torch.channels_last)
-            dgamma = torch.empty(C_, dtype=torch.float32, device=xn.device)
-            dbeta = torch.empty(C_, dtype=torch.float32, device=xn.device)
-            dss = torch.empty((B, 2 * C_), dtype=torch.float32, device=xn.device) if ctx.has_ss else None
-            ws = torch.empty(int(lib.nd_groupnorm_silu_train_workspace_floats(B, H * W, C_)), dtype=torch.float32, device=xn.device)
+            dgamma = _empty(C_, xn.device)
+            dbeta = _empty(C_, xn.device)
+            dss = _empty((B, 2 * C_), xn.device) if ctx.has_ss else None
+            ws = _workspace("nd_groupnorm_silu_train_workspace_floats", xn.device, B, H * W, C_)
             w32, b32 = weight.detach().float().contiguous(), bias.detach().float().contiguous()
             L.call("nd_groupnorm_silu_train_backward_f32", g.data_ptr(), C_, xn.data_ptr(), C_, w32.data_ptr(), b32.data_ptr(),
                    ss.data_ptr() if ctx.has_ss else None, mean_rstd.data_ptr(), mad.data_ptr(), dx.data_ptr(), C_, dgamma.data_ptr(), dbeta.data_ptr(),
@@ -421,14 +385,13 @@ class BroadcastAddFunction(torch.autograd.Function):
     @staticmethod
     @once_differentiable
     def backward(ctx, grad_out):
-        lib = L.load()
         B, N, C_ = grad_out.shape
         g = grad_out if grad_out.is_contiguous() and grad_out.dtype == torch.float32 else grad_out.float().contiguous()
         grad_vec = None
         if ctx.needs_input_grad[1]:
             with _on(g.device):
-                grad_vec = torch.empty((B, C_), dtype=torch.float32, device=g.device)
-                ws = torch.empty(int(lib.nd_token_sum_workspace_floats(B, N, C_)), dtype=torch.float32, device=g.device)
+                grad_vec = _empty((B, C_), g.device)
+                ws = _workspace("nd_token_sum_workspace_floats", g.device, B, N, C_)
                 L.call("nd_token_sum_f32", g.data_ptr(), C_, grad_vec.data_ptr(), ws.data_ptr(), B, N, C_, _stream(g.device))
             grad_vec = grad_vec.view(ctx.vec_shape)
         return grad_out, grad_vec
@@ -448,8 +411,7 @@ class ModulateSiLUFunction(torch.autograd.Function):
     @staticmethod
     def forward(ctx, n, ss):
         nn_, sn = _nhwc(n), _nhwc(ss)
-        if nn_.device.type != "cuda":
-            raise L.HipError(f"noisediff_amd.train runs on the HIP library only; tensor is on {nn_.device} and there is no CPU path")
+        _need_gpu(nn_)
         B, C_, H, W = nn_.shape
         with _on(nn_.device):
             y = torch.empty_like(nn_, memory_format=torch.channels_last)
@@ -501,6 +463,15 @@ def _hip_norm_forward(self: nn.GroupNorm, x: torch.Tensor) -> torch.Tensor:
 _PW_GEMM = __import__("os").environ.get("ND_TRAIN_PW", "1") != "0"
 
 
+class _PackEntry:
+    """One cached packing: ``param`` the nn.Parameter it was packed from (held strongly: see _PackCache), ``buf`` the packed operand, ``version`` the
+    parameter's version counter at the last packing (-1: stale), ``flag`` the data-gradient form, ``volatile``: packed while a stream was capturing."""
+    __slots__ = ("param", "buf", "version", "cin", "cout", "flag", "volatile")
+
+    def __init__(self, param: nn.Parameter, buf: torch.Tensor, cin: int, cout: int, flag: bool):
+        self.param, self.buf, self.version, self.cin, self.cout, self.flag, self.volatile = param, buf, -1, cin, cout, flag, False
+
+
 class _PackCache:
     """Packed operands of one device's weights: the Linear / 1x1 weights (kind "pw": nd_pack_pointwise_weight, ``flag`` = the transposed data-gradient
     packing) and the 3x3 weights on the F(4x4) kernels (kind "w4": nd_pack_conv3x3_wino4_weight, ``flag`` = the data-gradient form).  An entry belongs
@@ -521,12 +492,14 @@ class _PackCache:
     p.data = ...) are dropped: their address is no longer the parameter's."""
     _FLOATS = {"pw": "nd_pack_pointwise_weight_floats", "w4": "nd_pack_conv3x3_wino4_weight_floats"}
     _BATCH = {"pw": "nd_pack_pointwise_weights_batch", "w4": "nd_pack_conv3x3_wino4_weights_batch"}
-    # entry fields
-    _REF, _BUF, _VER, _CIN, _COUT, _FLAG, _VOLATILE = range(7)
 
     def __init__(self, device: torch.device):
         self.device = device
-        self.entries: Dict[tuple, list] = {}        # key -> [ref() -> the base parameter (held), packed buffer, version packed, cin, cout, flag, volatile]
+        self._last_table: Dict[str, torch.Tensor] = {}       # the table of each kind's last batched repack: alive until the next one (the launch is asynchronous)
+        self._reset()
+
+    def _reset(self) -> None:
+        self.entries: Dict[tuple, _PackEntry] = {}
         self.tables: Dict[str, Optional[torch.Tensor]] = {"pw": None, "w4": None}     # device copies of the nd_pack_item records, in the order of `order`
         self.order: Dict[str, list] = {"pw": [], "w4": []}
 
@@ -551,68 +524,62 @@ class _PackCache:
 
     def invalidate(self) -> None:
         for e in self.entries.values():
-            e[self._VER] = -1
+            e.version = -1
 
     def get(self, w: torch.Tensor, cin: int, cout: int, flag: bool, st, kind: str = "pw", base=None) -> int:
         """Device pointer of the packing of ``w`` (``base``: the parameter behind it where the caller has already detached ``w``)."""
-        lib = L.load()
         key = (kind, w.data_ptr(), tuple(w.shape), flag)
         base = base if base is not None else self._base(w)
         if base is None:
             raise L.HipError("_PackCache.get: not a parameter (check cacheable() first)")
         e = self.entries.get(key)
-        if e is not None and e[self._REF]() is not base:     # the parameter that owned this address is gone (or replaced): the entry goes with it
+        if e is not None and e.param is not base:            # the parameter that owned this address is gone (or replaced): the entry goes with it
             self._drop(key)
             e = None
         if e is None:
             if len(self.entries) >= 4096:            # (a model is a few hundred weights: anything beyond is a leak -- start over)
-                self.entries.clear(); self.order = {"pw": [], "w4": []}; self.tables = {"pw": None, "w4": None}
-            buf = torch.empty(int(getattr(lib, self._FLOATS[kind])(cin, cout)), dtype=torch.float32, device=self.device)
-            e = self.entries[key] = [(lambda b=base: b), buf, -1, cin, cout, flag, False]
+                self._reset()
+            e = self.entries[key] = _PackEntry(base, _workspace(self._FLOATS[kind], self.device, cin, cout), cin, cout, flag)
             self.order[kind].append(key)
             self.tables[kind] = None
         capturing = torch.cuda.is_current_stream_capturing()
-        if e[self._VER] != base._version or (e[self._VOLATILE] and not capturing):
-            if e[self._VOLATILE] and not capturing:
-                e[self._VER] = -1                    # packed inside a captured graph: replays may have moved the weight since, unseen by the version counter
+        if e.version != base._version or (e.volatile and not capturing):
+            if e.volatile and not capturing:
+                e.version = -1                       # packed inside a captured graph: replays may have moved the weight since, unseen by the version counter
             self._repack_stale(kind, st)
-        return e[self._BUF].data_ptr()
+        return e.buf.data_ptr()
 
-    def _pack_one(self, kind: str, key, e, st) -> None:
-        ptr, buf, cin, cout, flag = key[1], e[self._BUF], e[self._CIN], e[self._COUT], e[self._FLAG]
+    def _pack_one(self, kind: str, key, e: _PackEntry, st) -> None:
         if kind == "pw":
-            L.call("nd_pack_pointwise_weight_t" if flag else "nd_pack_pointwise_weight", ptr, buf.data_ptr(), cin, cout, *(() if flag else (0,)), st)
+            _pack_pointwise(key[1], e.buf.data_ptr(), e.cin, e.cout, e.flag, st)
         else:
-            L.call("nd_pack_conv3x3_wino4_weight" + ("_dgrad" if flag else ""), ptr, buf.data_ptr(), cin, cout, st)
+            _pack_conv3x3("wino4", key[1], e.buf.data_ptr(), e.cin, e.cout, e.flag, st)
 
     def _repack_stale(self, kind: str, st) -> None:
         def gone(k):
-            # the parameter has been freed, or its storage has moved (module.to(), p.data = ...) and the address this entry was keyed on is no longer inside it:
-            # the entry must not be repacked from that address (ADVICE r5 asked for weak references; a strong one used to keep the old storage alive)
-            base = self.entries[k][self._REF]()
-            if base is None:
-                return True
+            # the parameter's storage has moved (module.to(), p.data = ...) and the address this entry was keyed on is no longer inside it: the entry must
+            # not be repacked from that address
+            base = self.entries[k].param
             lo = base.data_ptr()
             return not (lo <= k[1] < lo + max(base.numel(), 1) * base.element_size())
         for k in [k for k in self.order[kind] if gone(k)]:
             self._drop(k)
         order = self.order[kind]
-        live = {k: self.entries[k][self._REF]() for k in order}
-        stale = [k for k in order if self.entries[k][self._VER] != live[k]._version]
+        stale = [k for k in order if self.entries[k].version != self.entries[k].param._version]
         capturing = torch.cuda.is_current_stream_capturing()
         if (self.tables[kind] is None or len(stale) != len(order)) and capturing:
             # a new descriptor table would need a host-to-device copy, which a capturing stream refuses: one capturable launch per stale weight instead
             for k in stale:
                 e = self.entries[k]
                 self._pack_one(kind, k, e, st)
-                e[self._VER], e[self._VOLATILE] = live[k]._version, True
+                e.version, e.volatile = e.param._version, True
             return
         if self.tables[kind] is None or len(stale) != len(order):
             # first use, or only part of the table is stale (a partially frozen model): a table of the stale entries only
             items = (L.PackItem * len(stale))()
             for i, k in enumerate(stale):
                 e = self.entries[k]
-                items[i].w, items[i].packed, items[i].cin, items[i].cout, items[i].transposed = k[1], e[self._BUF].data_ptr(), e[self._CIN], e[self._COUT], int(e[self._FLAG])
+                items[i].w, items[i].packed, items[i].cin, items[i].cout, items[i].transposed = k[1], e.buf.data_ptr(), e.cin, e.cout, int(e.flag)
             host = torch.frombuffer(bytearray(bytes(items)), dtype=torch.uint8)
             table = host.to(self.device)                     # (synchronous copy of a few KB)
             if len(stale) == len(order):
@@ -620,12 +587,12 @@ class _PackCache:
         else:
             table = self.tables[kind]
         L.call(self._BATCH[kind], table.data_ptr(), len(stale), st)
-        self._last_table = getattr(self, "_last_table", {})
-        self._last_table[kind] = table                       # alive until the next repack (the launch is asynchronous)
+        self._last_table[kind] = table
         for k in stale:
-            self.entries[k][self._VER] = live[k]._version
+            e = self.entries[k]
+            e.version = e.param._version
             if capturing:
-                self.entries[k][self._VOLATILE] = True
+                e.volatile = True
 
 
 _PACK_CACHES: Dict[int, _PackCache] = {}
@@ -667,7 +634,6 @@ def _pointwise_gemm(x2: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tens
     """y[N, cout] = x2[N, cin] @ W^T (+ bias) (+ res[N, cout]) on nd_pointwise_gemm_nhwc_f32 (pointwise.hip: the sampling path's 1x1 / Linear kernels, exact-fp32
     MFMA), W = ``w`` (cout, cin); ``transposed``: W^T = ``w`` -- the forward weight of the layer whose data gradient dx = dy @ w this is (packed
     in place by nd_pack_pointwise_weight_t).  ``res``: a residual added in the kernel's epilogue (the sampling engine's res0)."""
-    lib = L.load()
     N, cin = x2.shape
     c0 = cin
     if x2b is not None:                                                  # tokens of a second source: the virtual concatenation cat((x2, x2b), -1)
@@ -675,16 +641,13 @@ def _pointwise_gemm(x2: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tens
     cout = w.shape[1] if transposed else w.shape[0]
     st = _stream(x2.device)
     with _on(x2.device):
-        y = torch.empty((N, cout), dtype=torch.float32, device=x2.device)
+        y = _empty((N, cout), x2.device)
         if _PackCache.cacheable(w):                   # a parameter (or a view of one): its packing is cached until the optimizer changes it
             wptr = _pack_cache(x2.device).get(w, cin, cout, transposed, st)
         else:
-            wp = torch.empty(int(lib.nd_pack_pointwise_weight_floats(cin, cout)), dtype=torch.float32, device=x2.device)
+            wp = _workspace("nd_pack_pointwise_weight_floats", x2.device, cin, cout)
             w32 = w.detach().float().contiguous()
-            if transposed:
-                L.call("nd_pack_pointwise_weight_t", w32.data_ptr(), wp.data_ptr(), cin, cout, st)
-            else:
-                L.call("nd_pack_pointwise_weight", w32.data_ptr(), wp.data_ptr(), cin, cout, 0, st)
+            _pack_pointwise(w32.data_ptr(), wp.data_ptr(), cin, cout, transposed, st)
             wptr = wp.data_ptr()
         d = L.Pointwise()
         d.src.p0, d.src.c0, d.src.ld0, d.src.mode = x2.data_ptr(), c0, c0, L.PRO_NONE
@@ -703,6 +666,26 @@ def _pointwise_gemm(x2: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tens
 
 def _pw_takes(N: int, cin: int, cout: int) -> bool:
     return _PW_GEMM and cin % 4 == 0 and cout % 4 == 0 and 0 < N < (1 << 31) and N * max(cin, cout) * 4 < (1 << 40)
+
+
+def _linear_wgrad(x2: torch.Tensor, g2: torch.Tensor, want_b: bool):
+    """(dW (cout, cin), db or None) of a Linear from its input tokens ``x2`` (N, cin) and its output gradient ``g2`` (N, cout) on nd_linear_wgrad_f32
+    (fixed summation order); the bias gradient is the same pass's column sums of ``g2``."""
+    _need_gpu(x2)
+    (N, cin), cout, dev = x2.shape, g2.shape[1], x2.device
+    with _on(dev):
+        dw = _empty((cout, cin), dev)
+        db = _empty(cout, dev) if want_b else None
+        ws = _workspace("nd_linear_wgrad_workspace_floats", dev, N, cin, cout)
+        L.call("nd_linear_wgrad_f32", x2.data_ptr(), cin, g2.data_ptr(), cout, dw.data_ptr(), L.ptr(db), ws.data_ptr(), N, cin, cout, _stream(dev))
+    return dw, db
+
+
+def _linear_wgrad_cat(t0: torch.Tensor, t1: torch.Tensor, g2: torch.Tensor, want_b: bool):
+    """_linear_wgrad of a Linear over cat((t0, t1), -1): per source, joined along cin; the bias gradient from the first source's launch only."""
+    dw0, db = _linear_wgrad(_tokens(t0, t0.shape[-1]), g2, want_b)
+    dw1, _ = _linear_wgrad(_tokens(t1, t1.shape[-1]), g2, False)
+    return torch.cat((dw0, dw1), dim=1), db
 
 
 class LinearFunction(torch.autograd.Function):
@@ -728,7 +711,6 @@ class LinearFunction(torch.autograd.Function):
     @once_differentiable
     def backward(ctx, grad_out):
         x, weight = ctx.saved_tensors
-        lib = L.load()
         cout, cin = weight.shape
         grad_x = grad_w = grad_b = None
         g2 = _tokens(grad_out, cout)
@@ -738,16 +720,7 @@ class LinearFunction(torch.autograd.Function):
             else:
                 grad_x = grad_out @ weight
         if ctx.needs_input_grad[1] or (ctx.has_bias and ctx.needs_input_grad[2]):
-            x2 = _tokens(x, cin)
-            if x2.device.type != "cuda":
-                raise L.HipError(f"noisediff_amd.train runs on the HIP library only; tensor is on {x2.device} and there is no CPU path")
-            N = x2.shape[0]
-            with _on(x2.device):
-                grad_w = torch.empty((cout, cin), dtype=torch.float32, device=x2.device)
-                grad_b = torch.empty(cout, dtype=torch.float32, device=x2.device) if ctx.has_bias else None
-                ws = torch.empty(int(lib.nd_linear_wgrad_workspace_floats(N, cin, cout)), dtype=torch.float32, device=x2.device)
-                L.call("nd_linear_wgrad_f32", x2.data_ptr(), cin, g2.data_ptr(), cout, grad_w.data_ptr(),
-                       grad_b.data_ptr() if grad_b is not None else None, ws.data_ptr(), N, cin, cout, _stream(x2.device))
+            grad_w, grad_b = _linear_wgrad(_tokens(x, cin), g2, ctx.has_bias)
         return grad_x, grad_w, grad_b, (grad_out if len(ctx.needs_input_grad) > 3 and ctx.needs_input_grad[3] else None)
 
 
@@ -767,40 +740,32 @@ class LinearCatFunction(torch.autograd.Function):
     @once_differentiable
     def backward(ctx, grad_out):
         t0, t1, weight = ctx.saved_tensors
-        lib = L.load()
         cout, cin = weight.shape
-        c0, c1 = t0.shape[-1], t1.shape[-1]
+        c0 = t0.shape[-1]
         g0 = g1 = grad_w = grad_b = None
         g2 = _tokens(grad_out, cout)
         if ctx.needs_input_grad[0] or ctx.needs_input_grad[1]:
             full = _pointwise_gemm(g2, weight, None, True).view(*t0.shape[:-1], cin)
             g0, g1 = (full[..., :c0] if ctx.needs_input_grad[0] else None), (full[..., c0:] if ctx.needs_input_grad[1] else None)
         if ctx.needs_input_grad[2] or (ctx.has_bias and ctx.needs_input_grad[3]):
-            with _on(g2.device):
-                parts = []
-                for i, (t, c) in enumerate(((t0, c0), (t1, c1))):
-                    x2 = _tokens(t, c)
-                    N = x2.shape[0]
-                    dw = torch.empty((cout, c), dtype=torch.float32, device=x2.device)
-                    if i == 0 and ctx.has_bias:
-                        grad_b = torch.empty(cout, dtype=torch.float32, device=x2.device)
-                    ws = torch.empty(int(lib.nd_linear_wgrad_workspace_floats(N, c, cout)), dtype=torch.float32, device=x2.device)
-                    L.call("nd_linear_wgrad_f32", x2.data_ptr(), c, g2.data_ptr(), cout, dw.data_ptr(),
-                           grad_b.data_ptr() if (i == 0 and grad_b is not None) else None, ws.data_ptr(), N, c, cout, _stream(x2.device))
-                    parts.append(dw)
-                grad_w = torch.cat(parts, dim=1)
+            grad_w, grad_b = _linear_wgrad_cat(t0, t1, g2, ctx.has_bias)
         return g0, g1, grad_w, grad_b
+
+
+def _cat_tokens(op: str, x0: torch.Tensor, x1: torch.Tensor, weight: torch.Tensor):
+    """The argument check of the 1x1 convolutions over cat((x0, x1), 1), and the two sources as contiguous NHWC tokens (views when channels_last)."""
+    if x0.dim() != 4 or tuple(weight.shape[2:]) != (1, 1) or x0.shape[1] + x1.shape[1] != weight.shape[1] or x0.shape[1] % 4 or x1.shape[1] % 4 \
+            or weight.shape[0] % 4 or not (x0.is_cuda and x1.is_cuda):
+        raise ValueError(f"{op}: x0 {tuple(x0.shape)} + x1 {tuple(x1.shape)} / weight {tuple(weight.shape)}")
+    t0, t1 = x0.permute(0, 2, 3, 1), x1.permute(0, 2, 3, 1)
+    return (t0 if t0.is_contiguous() else t0.contiguous()), (t1 if t1.is_contiguous() else t1.contiguous())
 
 
 def conv1x1_cat(x0: torch.Tensor, x1: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Differentiable F.conv2d(torch.cat((x0, x1), 1), weight, bias) for 1x1 kernels that never builds the concatenation (channels_last in and out; both
     channel counts multiples of 4)."""
-    if x0.dim() != 4 or tuple(weight.shape[2:]) != (1, 1) or x0.shape[1] + x1.shape[1] != weight.shape[1] or x0.shape[1] % 4 or x1.shape[1] % 4 \
-            or weight.shape[0] % 4 or not (x0.is_cuda and x1.is_cuda):
-        raise ValueError(f"conv1x1_cat: x0 {tuple(x0.shape)} + x1 {tuple(x1.shape)} / weight {tuple(weight.shape)}")
-    t0, t1 = x0.permute(0, 2, 3, 1), x1.permute(0, 2, 3, 1)
-    y = LinearCatFunction.apply(t0 if t0.is_contiguous() else t0.contiguous(), t1 if t1.is_contiguous() else t1.contiguous(), weight.flatten(1), bias)
-    return y.permute(0, 3, 1, 2)
+    t0, t1 = _cat_tokens("conv1x1_cat", x0, x1, weight)
+    return LinearCatFunction.apply(t0, t1, weight.flatten(1), bias).permute(0, 3, 1, 2)
 
 
 class ShortcutCatFunction(torch.autograd.Function):
@@ -824,7 +789,7 @@ class ShortcutCatFunction(torch.autograd.Function):
     def backward(ctx, d0, d1, dr):
         t0, t1, weight = ctx.saved_tensors
         cout, cin = weight.shape
-        c0, c1 = t0.shape[-1], t1.shape[-1]
+        c0 = t0.shape[-1]
         if dr is None:
             return d0, d1, None, None
         g2 = _tokens(dr, cout)
@@ -847,31 +812,15 @@ class ShortcutCatFunction(torch.autograd.Function):
                 g1 = full[..., c0:] if d1 is None else full[..., c0:] + d1
         grad_w = grad_b = None
         if ctx.needs_input_grad[2] or (ctx.has_bias and ctx.needs_input_grad[3]):
-            lib = L.load()
-            with _on(g2.device):
-                parts = []
-                for i, (t, c) in enumerate(((t0, c0), (t1, c1))):
-                    x2 = _tokens(t, c)
-                    N = x2.shape[0]
-                    dw = torch.empty((cout, c), dtype=torch.float32, device=x2.device)
-                    if i == 0 and ctx.has_bias:
-                        grad_b = torch.empty(cout, dtype=torch.float32, device=x2.device)
-                    ws = torch.empty(int(lib.nd_linear_wgrad_workspace_floats(N, c, cout)), dtype=torch.float32, device=x2.device)
-                    L.call("nd_linear_wgrad_f32", x2.data_ptr(), c, g2.data_ptr(), cout, dw.data_ptr(),
-                           grad_b.data_ptr() if (i == 0 and grad_b is not None) else None, ws.data_ptr(), N, c, cout, _stream(x2.device))
-                    parts.append(dw)
-                grad_w = torch.cat(parts, dim=1)
+            grad_w, grad_b = _linear_wgrad_cat(t0, t1, g2, ctx.has_bias)
         return g0, g1, grad_w, grad_b
 
 
 def conv1x1_shortcut_cat(x0: torch.Tensor, x1: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor] = None):
     """(x0', x1', F.conv2d(torch.cat((x0, x1), 1), weight, bias)) for a ResnetBlock whose shortcut is a 1x1 convolution of a concatenation: x0' / x1' are the inputs
     again, to be read by the block's first convolution, whose data gradient then joins the shortcut's inside one GEMM (ShortcutCatFunction)."""
-    if x0.dim() != 4 or tuple(weight.shape[2:]) != (1, 1) or x0.shape[1] + x1.shape[1] != weight.shape[1] or x0.shape[1] % 4 or x1.shape[1] % 4 \
-            or weight.shape[0] % 4 or not (x0.is_cuda and x1.is_cuda):
-        raise ValueError(f"conv1x1_shortcut_cat: x0 {tuple(x0.shape)} + x1 {tuple(x1.shape)} / weight {tuple(weight.shape)}")
-    t0, t1 = x0.permute(0, 2, 3, 1), x1.permute(0, 2, 3, 1)
-    a0, a1, r = ShortcutCatFunction.apply(t0 if t0.is_contiguous() else t0.contiguous(), t1 if t1.is_contiguous() else t1.contiguous(), weight.flatten(1), bias)
+    t0, t1 = _cat_tokens("conv1x1_shortcut_cat", x0, x1, weight)
+    a0, a1, r = ShortcutCatFunction.apply(t0, t1, weight.flatten(1), bias)
     return a0.permute(0, 3, 1, 2), a1.permute(0, 3, 1, 2), r.permute(0, 3, 1, 2)
 
 
@@ -909,17 +858,16 @@ class Conv7x7Function(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, weight, bias):
-        lib = L.load()
         B, cin, H, W = x.shape
         cout = weight.shape[0]
         xn = x.detach().permute(0, 2, 3, 1).contiguous().float()          # NHWC, 4 channels
         st = _stream(x.device)
         with _on(x.device):
-            wp = torch.empty(196 * cout, dtype=torch.float32, device=x.device)
+            wp = _empty(196 * cout, x.device)
             w32 = weight.detach().float().contiguous()
             L.call("nd_pack_conv7x7_weight", w32.data_ptr(), wp.data_ptr(), cout, st)
             b32 = bias.detach().float().contiguous() if bias is not None else torch.zeros(cout, dtype=torch.float32, device=x.device)
-            y = torch.empty((B, H, W, cout), dtype=torch.float32, device=x.device)
+            y = _empty((B, H, W, cout), x.device)
             L.call("nd_conv7x7_c4_f32", xn.data_ptr(), wp.data_ptr(), b32.data_ptr(), y.data_ptr(), cout, B, H, W, cout, st)
         ctx.save_for_backward(x, weight)
         ctx.has_bias = bias is not None
@@ -929,34 +877,27 @@ class Conv7x7Function(torch.autograd.Function):
     @once_differentiable
     def backward(ctx, grad_out):
         x, weight = ctx.saved_tensors
-        lib = L.load()
         B, cin, H, W = x.shape
         cout = weight.shape[0]
         grad_x = grad_w = grad_b = None
         if ctx.needs_input_grad[0]:
             grad_x = torch.nn.grad.conv2d_input(x.shape, weight, grad_out, padding=3)
-        if (ctx.needs_input_grad[1] or (ctx.has_bias and ctx.needs_input_grad[2])) and cin == 4 and \
-                int(lib.nd_conv7x7_c4_wgrad_workspace_floats(B, H, W, cout)) >= 0:
+        want_w = ctx.needs_input_grad[1] or (ctx.has_bias and ctx.needs_input_grad[2])
+        ws_floats = int(L.load().nd_conv7x7_c4_wgrad_workspace_floats(B, H, W, cout)) if want_w and cin == 4 else -1      # (negative: not a shape of the kernel)
+        if ws_floats >= 0:
             # nd_conv7x7_c4_wgrad_f32: the GEMM over the pixels straight from halo tiles (no unfolded image: 205 MB and two copies at B = 4, 256 x 256)
             g = _tokens(grad_out.permute(0, 2, 3, 1), cout)                 # (pixels, cout)
             xn = x.detach().permute(0, 2, 3, 1).contiguous().float()
             with _on(xn.device):
-                grad_w = torch.empty(weight.shape, dtype=torch.float32, device=xn.device)
-                grad_b = torch.empty(cout, dtype=torch.float32, device=xn.device) if ctx.has_bias else None
-                ws = torch.empty(int(lib.nd_conv7x7_c4_wgrad_workspace_floats(B, H, W, cout)), dtype=torch.float32, device=xn.device)
-                L.call("nd_conv7x7_c4_wgrad_f32", xn.data_ptr(), g.data_ptr(), cout, grad_w.data_ptr(), grad_b.data_ptr() if grad_b is not None else None,
-                       ws.data_ptr(), B, H, W, cout, _stream(xn.device))
-        elif ctx.needs_input_grad[1] or (ctx.has_bias and ctx.needs_input_grad[2]):
+                grad_w = _empty(weight.shape, xn.device)
+                grad_b = _empty(cout, xn.device) if ctx.has_bias else None
+                ws = _empty(ws_floats, xn.device)
+                L.call("nd_conv7x7_c4_wgrad_f32", xn.data_ptr(), g.data_ptr(), cout, grad_w.data_ptr(), L.ptr(grad_b), ws.data_ptr(), B, H, W, cout,
+                       _stream(xn.device))
+        elif want_w:
             g2 = _tokens(grad_out.permute(0, 2, 3, 1), cout)                # (pixels, cout)
             cols = torch.nn.functional.unfold(x.detach().float(), kernel_size=7, padding=3)      # (B, cin * 49, H W): index ci * 49 + ky * 7 + kx == weight.flatten(1)'s
-            x2 = cols.transpose(1, 2).reshape(B * H * W, cin * 49).contiguous()
-            N, K = x2.shape
-            with _on(x2.device):
-                gw = torch.empty((cout, K), dtype=torch.float32, device=x2.device)
-                grad_b = torch.empty(cout, dtype=torch.float32, device=x2.device) if ctx.has_bias else None
-                ws = torch.empty(int(lib.nd_linear_wgrad_workspace_floats(N, K, cout)), dtype=torch.float32, device=x2.device)
-                L.call("nd_linear_wgrad_f32", x2.data_ptr(), K, g2.data_ptr(), cout, gw.data_ptr(),
-                       grad_b.data_ptr() if grad_b is not None else None, ws.data_ptr(), N, K, cout, _stream(x2.device))
+            gw, grad_b = _linear_wgrad(cols.transpose(1, 2).reshape(B * H * W, cin * 49).contiguous(), g2, ctx.has_bias)
             grad_w = gw.view(weight.shape)
         return grad_x, grad_w, grad_b
 
@@ -990,16 +931,12 @@ class LayerNormFunction(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, weight, bias, eps):
-        lib = L.load()
-        x2 = x.reshape(-1, x.shape[-1])
-        if x2.dtype != torch.float32 or not x2.is_contiguous():
-            x2 = x2.float().contiguous()
-        if x2.device.type != "cuda":
-            raise L.HipError(f"noisediff_amd.train runs on the HIP library only; tensor is on {x2.device} and there is no CPU path")
+        x2 = _tokens(x, x.shape[-1])
+        _need_gpu(x2)
         N, C_ = x2.shape
         with _on(x2.device):
             y = torch.empty_like(x2)
-            stats = torch.empty((N, 2), dtype=torch.float32, device=x2.device)
+            stats = _empty((N, 2), x2.device)
             w32, b32 = weight.detach().float().contiguous(), bias.detach().float().contiguous()
             L.call("nd_layernorm_train_forward_f32", x2.data_ptr(), C_, w32.data_ptr(), b32.data_ptr(), y.data_ptr(), C_, stats.data_ptr(),
                    N, C_, float(eps), _stream(x2.device))
@@ -1011,16 +948,13 @@ class LayerNormFunction(torch.autograd.Function):
     @once_differentiable
     def backward(ctx, grad_out):
         x2, weight, stats = ctx.saved_tensors
-        lib = L.load()
         N, C_ = x2.shape
-        g2 = grad_out.reshape(N, C_)
-        if g2.dtype != torch.float32 or not g2.is_contiguous():
-            g2 = g2.float().contiguous()
+        g2 = _tokens(grad_out, C_)
         with _on(x2.device):
             dx = torch.empty_like(x2)
-            dgamma = torch.empty(C_, dtype=torch.float32, device=x2.device)
-            dbeta = torch.empty(C_, dtype=torch.float32, device=x2.device)
-            ws = torch.empty(int(lib.nd_layernorm_train_workspace_floats(N, C_)), dtype=torch.float32, device=x2.device)
+            dgamma = _empty(C_, x2.device)
+            dbeta = _empty(C_, x2.device)
+            ws = _workspace("nd_layernorm_train_workspace_floats", x2.device, N, C_)
             w32 = weight.detach().float().contiguous()
             L.call("nd_layernorm_train_backward_f32", g2.data_ptr(), C_, x2.data_ptr(), C_, w32.data_ptr(), stats.data_ptr(), dx.data_ptr(), C_,
                    dgamma.data_ptr(), dbeta.data_ptr(), ws.data_ptr(), N, C_, _stream(x2.device))
@@ -1142,17 +1076,125 @@ class Adam(torch.optim.Adam):
                 raise NotImplementedError(f"noisediff_amd.train.Adam: {k}=True is not built (use torch.optim.Adam)")
         kw.pop("foreach", None)
         super().__init__(params, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, foreach=False, **{k: v for k, v in kw.items() if k != "fused"})
-        self._nd_tables: Dict[tuple, tuple] = {}     # (group index, parameter data_ptrs) -> (chunk table on the device, number of chunks)
+        self._nd_init_caches()
+
+    def _nd_init_caches(self) -> None:
+        """Everything the instance keeps besides torch.optim.Adam's own defaults / state / param_groups."""
+        self._nd_tables: Dict[tuple, tuple] = {}     # (group index, capturable, parameter data_ptrs) -> the group's laid-out table (_nd_table)
+        self._nd_captured_lr: Dict[int, float] = {}  # id(group) -> the learning rate its captured step was recorded with
+        self._nd_captured: list = []                 # tables of captured steps: a replay reads them, so they live as long as the optimizer
+        self._nd_keep = None                         # tables of the last step: alive until the next one (the launch is asynchronous)
+
+    def __setstate__(self, state) -> None:
+        """torch.optim.Optimizer.__getstate__ keeps only defaults / state / param_groups: a deep copy or an unpickled optimizer arrives here without the
+        caches (load_state_dict comes through here too, with them: its tables are checked against the new state tensors in _nd_table)."""
+        super().__setstate__(state)
+        if "_nd_tables" not in self.__dict__:
+            self._nd_init_caches()
 
     def check_captured_lr(self) -> None:
         """Call before replaying a captured training step: a captured ``capturable=True`` step carries the learning rate it was captured with (a launch
         argument).  Raises if a scheduler or the caller has changed ``group['lr']`` since -- re-capture the step then."""
-        cap = getattr(self, "_nd_captured_lr", {})
         for group in self.param_groups:
-            lr0 = cap.get(id(group))
+            lr0 = self._nd_captured_lr.get(id(group))
             if lr0 is not None and float(group["lr"]) != lr0:
                 raise RuntimeError(f"noisediff_amd.train.Adam: the captured step was recorded with lr={lr0:g}, the group now has lr={float(group['lr']):g}: "
                                    "a replay would ignore the change; capture the step again")
+
+    def _nd_table(self, gi: int, group: dict, ps: list, capturing: bool) -> tuple:
+        """Validate group ``gi``'s parameters ``ps`` (those with a gradient) and lay out what does not change from step to step: (nd_adam_item records
+        without the gradient pointers and step sizes, chunk table on the device, number of chunks, exp_avg, exp_avg_sq and step tensors).  Checked and
+        laid out once per set of parameters (the host side of a step is ~1 ms this way, 4.4 per parameter)."""
+        dev = ps[0].device
+        cap = bool(group.get("capturable"))                              # step counters on the device, nothing computed on the host (nd_adam_step_capturable_f32)
+        key = (gi, cap, tuple(p.data_ptr() for p in ps))
+        ent = self._nd_tables.get(key)
+        if ent is not None:
+            # load_state_dict (or anything else) replaced the state tensors: lay the table out again (compared by object, not by id() of a dict that
+            # may have been freed and its id reused)
+            _, _, _, ms0, vs0, steps0 = ent
+            for p, m0, v0, t0 in zip(ps, ms0, vs0, steps0):
+                st = self.state[p]
+                if st.get("exp_avg") is not m0 or st.get("exp_avg_sq") is not v0 or st.get("step") is not t0:
+                    ent = None
+                    break
+        if ent is not None:
+            return ent
+        if capturing:
+            raise RuntimeError("noisediff_amd.train.Adam: run a step with the same parameters before the capture (state and tables are built on the first step)")
+        if len(self._nd_tables) > 64:
+            self._nd_tables.clear()
+        for p in ps:
+            if p.grad.is_sparse or p.dtype != torch.float32 or not p.is_cuda or p.device != dev or not p.is_contiguous():
+                raise NotImplementedError("noisediff_amd.train.Adam updates dense, contiguous fp32 parameters of one GPU per group")
+            st = self.state[p]
+            if len(st) == 0:                                             # torch.optim.Adam._init_group's state
+                st["step"] = torch.zeros((), dtype=torch.float32, device=p.device) if cap else torch.tensor(0.0, dtype=torch.float32)
+                st["exp_avg"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+                st["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+            m, v = st["exp_avg"], st["exp_avg_sq"]
+            if not (m.is_contiguous() and v.is_contiguous()) or m.device != dev or v.device != dev:
+                raise NotImplementedError("noisediff_amd.train.Adam: optimizer state must be contiguous and on the parameter's device")
+            if cap and not (st["step"].is_cuda and st["step"].dtype == torch.float32):
+                raise NotImplementedError("noisediff_amd.train.Adam(capturable=True): the step counters must be fp32 tensors on the parameter's device")
+            if not cap and st["step"].is_cuda:
+                raise NotImplementedError("noisediff_amd.train.Adam: step counters on the device need capturable=True")
+        items = np.zeros(len(ps), dtype=np.dtype(L.AdamItem))            # nd_adam_item
+        ms, vs, steps = [self.state[p]["exp_avg"] for p in ps], [self.state[p]["exp_avg_sq"] for p in ps], [self.state[p]["step"] for p in ps]
+        items["p"] = [p.data_ptr() for p in ps]
+        items["m"] = [t.data_ptr() for t in ms]
+        items["v"] = [t.data_ptr() for t in vs]
+        items["n"] = [p.numel() for p in ps]
+        if cap:
+            items["step"] = [t.data_ptr() for t in steps]
+        per = int(L.load().nd_adam_chunk_elements())
+        pairs = [(i, c) for i, p in enumerate(ps) for c in range((p.numel() + per - 1) // per)]
+        chunks = torch.tensor(pairs, dtype=torch.int32).reshape(-1, 2).to(dev)
+        ent = self._nd_tables[key] = (items, chunks, len(pairs), ms, vs, steps)
+        return ent
+
+    def _nd_launch(self, group: dict, ps: list, ent: tuple, capturing: bool) -> None:
+        """One launch for group's parameters ``ps`` over its table ``ent`` (_nd_table) with this step's gradient pointers and step sizes."""
+        dev, cap = ps[0].device, bool(group.get("capturable"))
+        beta1, beta2 = group["betas"]
+        lr = float(group["lr"])
+        if cap and capturing:
+            # the learning rate is a launch argument: a captured step replays with the value it was captured with (the reference's CosineAnnealingLR
+            # and its hand-written group['lr'] = ..., trainer_diffusion.py:95,104-105, do not reach a replayed graph) -- refuse a silent mismatch
+            self._nd_captured_lr[id(group)] = lr
+        items, chunks, n_chunks, ms, vs, steps = ent
+        gs = [p.grad for p in ps]
+        if not all(g.is_contiguous() and g.dtype == torch.float32 and not g.is_sparse for g in gs):
+            gs = [g.contiguous() if not g.is_sparse and g.dtype == torch.float32 else None for g in gs]
+            if any(g is None for g in gs):
+                raise NotImplementedError("noisediff_amd.train.Adam updates from dense fp32 gradients")
+        items = items.copy()
+        items["g"] = [g.data_ptr() for g in gs]
+        items["vec4"] = ((items["p"] | items["g"] | items["m"] | items["v"]) & 15) == 0
+        if not cap:
+            torch._foreach_add_(steps, 1.0)                              # (CPU scalars: one C++ loop)
+            # every parameter's OWN step count (a cheap loop over CPU scalars): parameters that were stepped under another set -- grad None on some
+            # steps -- carry different counts, and each gets its own bias correction
+            ts = np.array([float(t) for t in steps], dtype=np.float64)
+            items["step_size"] = lr / (1.0 - beta1 ** ts)
+            items["bias2_sqrt"] = np.sqrt(1.0 - beta2 ** ts)
+        # pointers and step sizes of this step (a few KB): pinned + asynchronous, so the host keeps running ahead of the device
+        host_table = torch.from_numpy(items.view(np.uint8)).pin_memory()
+        table = host_table.to(dev, non_blocking=True)
+        with _on(dev):
+            if cap:
+                L.call("nd_adam_step_capturable_f32", table.data_ptr(), len(ps), chunks.data_ptr(), n_chunks, lr, float(beta1), float(beta2),
+                       float(group["eps"]), float(group["weight_decay"]), _stream(dev))
+            else:
+                L.call("nd_adam_step_f32", table.data_ptr(), len(ps), chunks.data_ptr(), n_chunks, float(beta1), float(beta2), float(group["eps"]),
+                       float(group["weight_decay"]), _stream(dev))
+        if capturing:                                                    # a captured step replays with these tables: they live as long as the optimizer
+            self._nd_captured.append((table, host_table, gs))
+        self._nd_keep = (table, gs)
+        # the kernel wrote through raw pointers: tell autograd (and the packing caches, which compare version counters) that these tensors changed
+        torch.autograd.graph.increment_version(ps)
+        torch.autograd.graph.increment_version(ms)
+        torch.autograd.graph.increment_version(vs)
 
     @torch.no_grad()
     def step(self, closure=None):
@@ -1164,105 +1206,14 @@ class Adam(torch.optim.Adam):
         if capturing and not all(g.get("capturable") for g in self.param_groups):
             raise RuntimeError("noisediff_amd.train.Adam computes its step sizes on the host unless built with capturable=True: this step cannot be captured "
                                "into a CUDA graph")
-        lib = L.load()
-        import numpy as np
-        per = int(lib.nd_adam_chunk_elements())
-        item_t = np.dtype([("p", "<u8"), ("g", "<u8"), ("m", "<u8"), ("v", "<u8"), ("n", "<i8"), ("step_size", "<f4"), ("bias2_sqrt", "<f4"), ("vec4", "<i4"),
-                           ("reserved", "<i4"), ("step", "<u8")])                    # nd_adam_item (L.AdamItem)
-        # ---- what does not change from step to step is checked and laid out once per set of parameters (the host side of a step is ~1 ms this way, 4.4
-        #      per parameter); EVERY group's table is validated before ANY group is launched (a rebuild in the middle used to re-run the whole
-        #      step and move the groups already updated twice)
+        L.load()
+        # EVERY group's table is validated before ANY group is launched (a rebuild in the middle used to re-run the whole step and move the
+        # groups already updated twice)
         work = []
         for gi, group in enumerate(self.param_groups):
             ps = [p for p in group["params"] if p.grad is not None]
-            if not ps:
-                continue
-            dev = ps[0].device
-            cap = bool(group.get("capturable"))                          # step counters on the device, nothing computed on the host (nd_adam_step_capturable_f32)
-            key = (gi, cap, tuple(p.data_ptr() for p in ps))
-            ent = self._nd_tables.get(key)
-            if ent is not None:
-                # load_state_dict (or anything else) replaced the state tensors: lay the table out again (compared by object, not by id() of a dict that
-                # may have been freed and its id reused)
-                _, _, _, ms0, vs0, steps0 = ent
-                for p, m0, v0, t0 in zip(ps, ms0, vs0, steps0):
-                    st = self.state[p]
-                    if st.get("exp_avg") is not m0 or st.get("exp_avg_sq") is not v0 or st.get("step") is not t0:
-                        ent = None
-                        break
-            if ent is None:
-                if capturing:
-                    raise RuntimeError("noisediff_amd.train.Adam: run a step with the same parameters before the capture (state and tables are built on the first step)")
-                if len(self._nd_tables) > 64:
-                    self._nd_tables.clear()
-                for p in ps:
-                    if p.grad.is_sparse or p.dtype != torch.float32 or not p.is_cuda or p.device != dev or not p.is_contiguous():
-                        raise NotImplementedError("noisediff_amd.train.Adam updates dense, contiguous fp32 parameters of one GPU per group")
-                    st = self.state[p]
-                    if len(st) == 0:                                     # torch.optim.Adam._init_group's state
-                        st["step"] = torch.zeros((), dtype=torch.float32, device=p.device) if cap else torch.tensor(0.0, dtype=torch.float32)
-                        st["exp_avg"] = torch.zeros_like(p, memory_format=torch.preserve_format)
-                        st["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.preserve_format)
-                    m, v = st["exp_avg"], st["exp_avg_sq"]
-                    if not (m.is_contiguous() and v.is_contiguous()) or m.device != dev or v.device != dev:
-                        raise NotImplementedError("noisediff_amd.train.Adam: optimizer state must be contiguous and on the parameter's device")
-                    if cap and not (st["step"].is_cuda and st["step"].dtype == torch.float32):
-                        raise NotImplementedError("noisediff_amd.train.Adam(capturable=True): the step counters must be fp32 tensors on the parameter's device")
-                    if not cap and st["step"].is_cuda:
-                        raise NotImplementedError("noisediff_amd.train.Adam: step counters on the device need capturable=True")
-                items = np.zeros(len(ps), dtype=item_t)
-                ms, vs, steps = [self.state[p]["exp_avg"] for p in ps], [self.state[p]["exp_avg_sq"] for p in ps], [self.state[p]["step"] for p in ps]
-                items["p"] = [p.data_ptr() for p in ps]
-                items["m"] = [t.data_ptr() for t in ms]
-                items["v"] = [t.data_ptr() for t in vs]
-                items["n"] = [p.numel() for p in ps]
-                if cap:
-                    items["step"] = [t.data_ptr() for t in steps]
-                pairs = [(i, c) for i, p in enumerate(ps) for c in range((p.numel() + per - 1) // per)]
-                chunks = torch.tensor(pairs, dtype=torch.int32).reshape(-1, 2).to(dev)
-                ent = self._nd_tables[key] = (items, chunks, len(pairs), ms, vs, steps)
-            work.append((group, ps, dev, cap, ent))
-        for group, ps, dev, cap, ent in work:
-            beta1, beta2 = group["betas"]
-            lr = float(group["lr"])
-            if cap:
-                # the learning rate is a launch argument: a captured step replays with the value it was captured with (the reference's CosineAnnealingLR
-                # and its hand-written group['lr'] = ..., trainer_diffusion.py:95,104-105, do not reach a replayed graph) -- refuse a silent mismatch
-                if capturing:
-                    self._nd_captured_lr = getattr(self, "_nd_captured_lr", {})
-                    self._nd_captured_lr[id(group)] = lr
-            items, chunks, n_chunks, ms, vs, steps = ent
-            # ---- this step: gradient pointers, step sizes
-            gs = [p.grad for p in ps]
-            if not all(g.is_contiguous() and g.dtype == torch.float32 and not g.is_sparse for g in gs):
-                gs = [g.contiguous() if not g.is_sparse and g.dtype == torch.float32 else None for g in gs]
-                if any(g is None for g in gs):
-                    raise NotImplementedError("noisediff_amd.train.Adam updates from dense fp32 gradients")
-            items = items.copy()
-            items["g"] = [g.data_ptr() for g in gs]
-            items["vec4"] = ((items["p"] | items["g"] | items["m"] | items["v"]) & 15) == 0
-            if not cap:
-                torch._foreach_add_(steps, 1.0)                          # (CPU scalars: one C++ loop)
-                # every parameter's OWN step count (a cheap loop over CPU scalars): parameters that were stepped under another set -- grad None on some
-                # steps -- carry different counts, and each gets its own bias correction
-                ts = np.array([float(t) for t in steps], dtype=np.float64)
-                items["step_size"] = lr / (1.0 - beta1 ** ts)
-                items["bias2_sqrt"] = np.sqrt(1.0 - beta2 ** ts)
-            # pointers and step sizes of this step (a few KB): pinned + asynchronous, so the host keeps running ahead of the device
-            host_table = torch.from_numpy(items.view(np.uint8)).pin_memory()
-            table = host_table.to(dev, non_blocking=True)
-            with _on(dev):
-                if cap:
-                    L.call("nd_adam_step_capturable_f32", table.data_ptr(), len(ps), chunks.data_ptr(), n_chunks, lr, float(beta1), float(beta2),
-                           float(group["eps"]), float(group["weight_decay"]), _stream(dev))
-                else:
-                    L.call("nd_adam_step_f32", table.data_ptr(), len(ps), chunks.data_ptr(), n_chunks, float(beta1), float(beta2), float(group["eps"]),
-                           float(group["weight_decay"]), _stream(dev))
-            if capturing:                                                # a captured step replays with these tables: they live as long as the optimizer
-                self._nd_captured = getattr(self, "_nd_captured", []) + [(table, host_table, gs)]
-            self._nd_keep = (table, gs)                                  # alive until the next step (the launch is asynchronous)
-            # the kernel wrote through raw pointers: tell autograd (and the packing caches, which compare version counters) that these tensors changed
-            torch.autograd.graph.increment_version(ps)
-            torch.autograd.graph.increment_version(ms)
-            torch.autograd.graph.increment_version(vs)
+            if ps:
+                work.append((group, ps, self._nd_table(gi, group, ps, capturing)))
+        for group, ps, ent in work:
+            self._nd_launch(group, ps, ent, capturing)
         return loss

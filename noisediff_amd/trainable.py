@@ -21,7 +21,7 @@ import torch
 import torch.nn.functional as F
 from torch import nn
 
-from . import synth
+from . import synth, train
 from .spec import noisediff_param_spec
 
 P = Dict[str, torch.Tensor]
@@ -62,7 +62,6 @@ class _Ops:
         w = torch.cat([self.p[n + ".mlp.1.weight"] for n in names])
         b = torch.cat([self.p[n + ".mlp.1.bias"] for n in names])
         if self.hip and t_act.is_cuda:
-            from . import train
             ss_all = train.linear(t_act, w, b)
         else:
             ss_all = F.linear(t_act, w, b)
@@ -85,11 +84,9 @@ class _Ops:
         if res is not None:
             if (self.hip and not isinstance(x, tuple) and x.is_cuda and w.shape[2:] == (1, 1) and padding == 0 and w.shape[0] % 4 == 0 and w.shape[1] % 4 == 0
                     and res.shape[1] == w.shape[0]):
-                from . import train
                 return train.conv1x1(x, w, b, res=res)
             return self.conv(name, x, padding) + res
         if isinstance(x, tuple):
-            from . import train
             if self.hip and train.cat_sources_ok(*x, w.shape[0]):
                 if w.shape[2:] == (3, 3) and padding == 1:
                     return train.conv3x3_cat(x[0], x[1], w, b)
@@ -97,18 +94,14 @@ class _Ops:
                     return train.conv1x1_cat(x[0], x[1], w, b)
             x = torch.cat(x, dim=1)
         if self.hip and x.is_cuda and w.shape[2:] == (3, 3) and padding == 1 and w.shape[0] % 8 == 0 and w.shape[1] % 8 == 0:
-            from . import train
             return train.conv3x3(x, w, b)
         if self.hip and x.is_cuda and w.shape[2:] == (1, 1) and padding == 0 and w.shape[0] % 4 == 0 and w.shape[1] % 4 == 0:
-            from . import train
             return train.conv1x1(x, w, b)
         if self.hip and x.is_cuda and tuple(w.shape[1:]) == (4, 7, 7) and padding == 3 and w.shape[0] % 4 == 0:
-            from . import train
             return train.conv7x7_c4(x, w, b)                                    # the stem (init_conv / cond_init_conv)
         if self.hip and x.is_cuda and w.shape[2:] == (1, 1) and padding == 0 and w.shape[0] % 4 == 0 and w.shape[1] < 4:
             # pos_enc.weights (2 -> 8 channels, Diffusion_arch.py:328): as a 4-channel 1x1 convolution with two zero input channels -- the zero weight columns
             # receive gradients that the slice drops
-            from . import train
             pad = 4 - w.shape[1]
             return train.conv1x1(F.pad(x, (0, 0, 0, 0, 0, pad)), F.pad(w, (0, 0, 0, 0, 0, pad)), b)
         if x.is_cuda:
@@ -119,7 +112,6 @@ class _Ops:
         """``res``: linear(x) + res, the addition in the GEMM's epilogue on the library."""
         w, b = self.p[name + ".weight"], self.p.get(name + ".bias")
         if self.hip and x.is_cuda and w.shape[0] % 4 == 0 and w.shape[1] % 4 == 0:
-            from . import train
             return train.linear(x, w, b, res)
         if x.is_cuda:
             self._left_library(name, "linear", f"{w.shape[1]} -> {w.shape[0]}: channel counts must be multiples of 4")
@@ -129,7 +121,6 @@ class _Ops:
     def group_norm(self, name: str, x: torch.Tensor, groups: int) -> torch.Tensor:
         w, b = self.p[name + ".weight"], self.p[name + ".bias"]
         if self.hip and x.is_cuda:
-            from . import train
             if train._group_norm_ok(x.shape[1], groups):                     # wider nets (dim > 128: C > 1024) stay on PyTorch's norm
                 return train.group_norm(x, groups, w, b, 1e-5)
             self._left_library(name, "group_norm", f"C = {x.shape[1]}, {groups} groups: outside the library's norm (C <= 1024, C % 4 == 0)")
@@ -138,7 +129,6 @@ class _Ops:
     def layer_norm(self, name: str, x: torch.Tensor) -> torch.Tensor:
         w, b = self.p[name + ".weight"], self.p[name + ".bias"]
         if self.hip and x.is_cuda:
-            from . import train
             if train._layer_norm_ok(x.shape[-1]):
                 return train.layer_norm(x, w, b, 1e-5)
             self._left_library(name, "layer_norm", f"C = {x.shape[-1]}: the library's LayerNorm takes C = 64, 128 or a multiple of 256")
@@ -148,7 +138,6 @@ class _Ops:
     def block(self, name: str, x, groups: int, ss=None, res=None):
         """Block: conv3x3 -> GroupNorm -> optional x (scale + 1) + shift -> SiLU   (Diffusion_arch.py:128-144); ``ss`` = scale | shift
         along dim 1: (B, 2C, 1, 1) from the time embedding or (B, 2C, H, W) per-pixel maps."""
-        from . import train
         w = self.p[name + ".proj.weight"]
         pair = x if isinstance(x, tuple) else None                             # (x0, x1) = torch.cat((x0, x1), 1), read as two sources where the kernels can
         if pair is not None and not (self.hip and train.cat_sources_ok(*pair, w.shape[0]) and train._group_norm_ok(w.shape[0], groups)
@@ -191,7 +180,6 @@ class _Ops:
         if isinstance(x, tuple) and name + ".res_conv.weight" not in self.p:
             x = torch.cat(x, dim=1)                                            # an identity shortcut needs the tensor itself
         if isinstance(x, tuple) and self.hip:
-            from . import train
             w = self.p[name + ".res_conv.weight"]
             if train.cat_sources_ok(*x, w.shape[0]):               # (what conv() asks before it reads the pair as two sources)
                 # the shortcut hands the pair on to block1: that convolution's data gradient then joins the shortcut's in one GEMM instead of two additions
@@ -228,7 +216,6 @@ class _Ops:
         if ctx.shape[1] == 1:                                                # norm1 feeds only the (dead) queries: skipped, its gradient is zero
             vec = _ZeroGrads.apply(self.cross_attention(name + ".attn", t, ctx), self.p[name + ".norm1.weight"], self.p[name + ".norm1.bias"])   # (b, 1, C): the same vector for every token
             if self.hip and t.is_cuda:
-                from . import train
                 t = train.broadcast_add(t, vec)                                     # its gradient: a token sum on the library (fixed order)
             else:
                 t = vec + t

@@ -348,6 +348,24 @@ def test_accelerate_retargets_the_class_so_replicas_and_copies_resolve_forward_t
         conv(torch.zeros(1, 8, 16, 16))                                          # still no CPU fallback
 
 
+def test_adam_copies_and_pickles_arrive_with_their_caches():
+    """torch.optim.Optimizer.__getstate__ keeps only defaults / state / param_groups, so a deep copy and a pickle round trip of train.Adam come back
+    through __setstate__ without the instance's own caches: they must be there and empty (the first step() reads them), the copy's parameters its own."""
+    import copy
+    import pickle
+    from torch import nn
+    from noisediff_amd import train
+    opt = train.Adam([nn.Parameter(torch.zeros(4)), nn.Parameter(torch.ones(3, 2))], lr=2e-3, weight_decay=0.01)
+    opt._nd_tables[("stale",)] = ()                                              # what a copy must not inherit
+    for other in (copy.deepcopy(opt), pickle.loads(pickle.dumps(opt))):
+        assert type(other) is train.Adam and other.defaults == opt.defaults
+        assert other._nd_tables == {} and other._nd_captured_lr == {} and other._nd_captured == [] and other._nd_keep is None
+        other.check_captured_lr()
+        assert all(a is not b and torch.equal(a, b) for a, b in zip(other.param_groups[0]["params"], opt.param_groups[0]["params"]))
+    opt.load_state_dict(opt.state_dict())                                       # comes through __setstate__ too: keeps its caches
+    assert ("stale",) in opt._nd_tables
+
+
 def test_split_k_plan_is_a_function_of_the_shape():
     """nd_conv3x3_wino4_splitk_plan (host code, no GPU): 1 where the layer's (sample, region, cout tile) items fill the chip or cin leaves
     no room, else the power of two that brings them to about 256 with at least four 16-channel chunks per range."""

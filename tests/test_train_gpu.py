@@ -701,6 +701,24 @@ def test_adam_one_launch_step_matches_torch_optim_adam(weight_decay):
         for name in ("exp_avg", "exp_avg_sq"):
             assert rel_err(got[1]["state"][k][name].cpu().numpy(), ref[1]["state"][k][name].cpu().numpy()) < 2e-6
         assert float(got[1]["state"][k]["step"]) == float(ref[1]["state"][k]["step"]) == 4.0
+    # a deep copy (the optimizer's own parameter copies, after two steps of the original) steps them as torch.optim.Adam steps the originals' twins
+    pair = []
+    for cls in (torch.optim.Adam, train.Adam):
+        ps = make()
+        opt = cls(ps, lr=3e-3, betas=(0.9, 0.99), eps=1e-8, weight_decay=weight_decay)
+        for step in range(2):
+            grads(ps, step)
+            opt.step()
+        if cls is train.Adam:
+            opt = copy.deepcopy(opt)
+            ps = opt.param_groups[0]["params"]
+        for step in range(2, 4):
+            grads(ps, step)
+            opt.step()
+        torch.cuda.synchronize()
+        pair.append([p.detach().cpu() for p in ps])
+    for a, b in zip(*pair):
+        assert rel_err(b.numpy(), a.numpy()) < 2e-6
     with pytest.raises(NotImplementedError):
         train.Adam(make(), amsgrad=True)
     with pytest.raises(L.HipError):
@@ -893,7 +911,7 @@ def test_packing_cache_sees_data_writes_after_invalidate_and_drops_dead_models()
     del stale
     cache = train._pack_cache(DEV)
     n_live = len(cache.entries)
-    assert n_live > 0 and all(isinstance(e[cache._REF](), nn.Parameter) for e in cache.entries.values())
+    assert n_live > 0 and all(isinstance(e.param, nn.Parameter) for e in cache.entries.values())
     # a non-parameter leaf is never cached
     w = torch.randn(64, 64, device=DEV)
     assert not train._PackCache.cacheable(w) and train._PackCache.cacheable(net[1].weight.flatten(1))

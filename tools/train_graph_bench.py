@@ -44,4 +44,4 @@ for (B, S) in [(4, 256), (8, 128)]:
     for _ in range(8): g.replay()
     torch.cuda.synchronize()
     graphed = (time.perf_counter() - t0) / 8
-    print(f"B={B} {S}x{S}: eager {eager * 1e3:.1f} ms/step, one captured graph per step {graphed * 1e3:.1f} ms/step, loss {float(loss.detach()):.6f}", flush=True)
+    print(f"B={B} {S}x{S}: eager {eager * 1e3:.2f} ms/step, one captured graph per step {graphed * 1e3:.2f} ms/step, loss {float(loss.detach()):.6f}", flush=True)
