@@ -343,6 +343,45 @@ int nd_illum_scale_f32(const float* pred, const float* source, int source_batch,
                        int B, int C, int H, int W, void* stream);
 /* out = k32[b] * clamp(pred, 0, 1) in fp32: IlluminanceCorrect's output.  out may alias pred. */
 int nd_illum_apply_f32(const float* pred, const float* k32, float* out, int B, int C, int H, int W, void* stream);
+
+/* ------------------------------------------------------------------ the denoiser's training batch (dataset_denoising.py:80-168, trainer_denoising.py:100-166,207-217)
+ * nd_denoise_batch_f32: ONE launch from generated noise patches to the (noisy, clean) pair TrainableLSID takes.  noise, clean: fp32 NCHW
+ * [B][4][patch][patch]; noisy, clean_out: [B][4][crop_h][crop_w].  Per output element (c, y, x), with the row of `table` for its sample:
+ *   source row ys = cy + (flip ? crop_h-1-y : y), column xs = cx + x (the flip is torch.flip(dims=[2]): the H axis);
+ *   n = clip(noise, -1, 1); v = clip(n + clean, 0, 1); g = clip(clean, 0, 1)   (clips keep NaN);
+ *   with the four dark-shading planes (all or none; [4][map_h][map_w] of nd_pack_darkshading_f32; `branch` != 0 reads the high-ISO pair):
+ *     im = v / ratio; im = im * 15871 + 512; im = clip(im, 0, 16383); im -= (ds_k[c][y0+ys][x0+xs] * iso + ds_b[c][y0+ys][x0+xs]) + blc;
+ *     im = max(im - 512, 0); im = im / 15871; im = im * ratio; v = clip(im, 0, 1)       -- fp32, one IEEE operation each, in this order;
+ *   with `sna` ([B][ND_DENOISE_SNA_WORDS] fp32: wb[4], K; NULL = no augmentation; a row whose wb is all zero is skipped):
+ *     lam = (double)g * 15871 / ratio * wb[c] / K in fp64, k ~ Poisson(lam) by nd_philox_poisson_f32's generator with element index
+ *     c crop_h crop_w + y crop_w + x, sample index first_sample + b and draw index `draw`; then in fp32
+ *     gt = g * 15871 / ratio; dy = gt * wb[c]; dn = k * K; dy = dy * ratio / 15871; dn = dn / 15871; dn = dn * ratio;
+ *     noisy = v + dn; clean_out = g + dy (no clip); without it noisy = v, clean_out = g.
+ * table, sna and rng are DEVICE memory, read by the kernel: a captured graph replays with new crops, flips and augmentations once the
+ * caller has rewritten them.  rng ({seed, first_sample, draw} as int64, or NULL) overrides the three arguments, as nd_sampler_state.rng does.
+ * counts_in (fp32 [B][4][crop_h][crop_w] or NULL): use these counts and draw nothing; counts_out (or NULL): the counts used (0 where
+ * the augmentation is off).  A table row that points outside the patch or the planes gives NaN for its sample and reads nothing.
+ * patch, crop_h, crop_w even; noise, clean, counts and outputs 8-byte aligned (16-byte stores when crop_w % 4 == 0 and the outputs allow). */
+typedef struct nd_denoise_sample {
+    int32_t x0, y0;         /* origin of the patch in the packed frame: where the shading planes are read                   */
+    int32_t cx, cy;         /* crop offset inside the patch: even, 0 <= cx <= patch - crop_w, 0 <= cy <= patch - crop_h      */
+    int32_t flip;           /* != 0: rows reversed                                                                         */
+    int32_t branch;         /* != 0: the high-ISO planes (iso > 1600)                                                      */
+    float iso, ratio, blc;  /* blc = blc_mean[iso]                                                                         */
+    int32_t reserved[3];
+} nd_denoise_sample;
+#define ND_DENOISE_SNA_WORDS 8
+int nd_denoise_batch_f32(const float* noise, const float* clean, const float* ds_k_high, const float* ds_b_high, const float* ds_k_low,
+                         const float* ds_b_low, int map_h, int map_w, const nd_denoise_sample* table, const float* sna, const int64_t* rng,
+                         uint64_t seed, int64_t first_sample, int32_t draw, const float* counts_in, float* counts_out, float* noisy,
+                         float* clean_out, int B, int patch, int crop_h, int crop_w, void* stream);
+/* out[b][i] ~ Poisson((double)rate[b][i]) as fp32, i < n_per_sample: Philox4x32-10 keyed by `seed`, counter {i, first_sample + b, draw, block};
+ * uniforms (word + 0.5) 2^-32 in fp64 and every decision in fp64.  rate 0: 0; rate < 10: inversion on word 0 of block 0; else Hoermann's
+ * transformed rejection, attempt t on words 2 (t % 2), 2 (t % 2) + 1 of block t / 2.  A negative, NaN or infinite rate gives NaN. */
+int nd_philox_poisson_f32(const float* rate, float* out, uint64_t seed, int64_t first_sample, int32_t draw, int B, int64_t n_per_sample,
+                          void* stream);
+/* A Bayer map [H2][W2] -> planes [4][H2/2][W2/2] in pack_np_raw's channel order: plane c at (Y, X) is bayer[2Y + (c >= 2)][2X + (c == 1 || c == 2)]. */
+int nd_pack_darkshading_f32(const float* bayer, float* planes, int H2, int W2, void* stream);
 /* (cout, cin) row-major (Linear / 1x1 conv weight) -> [cinP/4][coutP][4]; `unshuffle_c` > 0
  * permutes K from (c p1 p2) to (p1 p2 c) for a pixel-unshuffled input with c = unshuffle_c. */
 int64_t nd_pack_pointwise_weight_floats(int cin, int cout);

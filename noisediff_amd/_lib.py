@@ -199,6 +199,9 @@ SIGNATURES = {
     "nd_illum_scale_workspace_bytes": (i64, [i32, i32, i32, i32]),
     "nd_illum_scale_f32": (i32, [vp, vp, i32, vp, vp, vp, i32, i32, i32, i32, vp]),
     "nd_illum_apply_f32": (i32, [vp, vp, vp, i32, i32, i32, i32, vp]),
+    "nd_denoise_batch_f32": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, vp, vp, vp, u64, i64, i32, vp, vp, vp, vp, i32, i32, i32, i32, vp]),
+    "nd_philox_poisson_f32": (i32, [vp, vp, u64, i64, i32, i32, i64, vp]),
+    "nd_pack_darkshading_f32": (i32, [vp, vp, i32, i32, vp]),
 }
 
 _UNCHECKED = {"nd_version", "nd_last_error", "nd_stream_device", "nd_conv3x3_wgrad_form", "nd_adam_chunk_elements", "nd_conv7x7_c4_wgrad_workspace_floats", "nd_conv3x3_stat_slots", "nd_conv3x3_tiling_id", "nd_pack_conv3x3_weight_floats",

@@ -14,22 +14,6 @@
 
 namespace {
 
-struct Philox {
-    // Philox4x32-10 (Salmon et al. 2011); restated in oracle/noisediff_oracle.py::philox4x32_10
-    static __device__ __forceinline__ void round(uint32_t (&c)[4], uint32_t k0, uint32_t k1) {
-        const uint64_t p0 = (uint64_t)0xD2511F53u * c[0], p1 = (uint64_t)0xCD9E8D57u * c[2];
-        const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c[1] ^ k0, n2 = (uint32_t)(p0 >> 32) ^ c[3] ^ k1;
-        c[1] = (uint32_t)p1; c[3] = (uint32_t)p0; c[0] = n0; c[2] = n2;
-    }
-    static __device__ __forceinline__ void gen(uint32_t (&c)[4], uint32_t k0, uint32_t k1) {
-#pragma unroll
-        for (int i = 0; i < 10; ++i) {
-            round(c, k0, k1);
-            k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-        }
-    }
-};
-
 // four N(0,1) for quad `q` of sample `sample` at noise draw `step1` (0 = x_T, i+1 = i-th step)
 __device__ __forceinline__ f32x4 philox_normal4(uint64_t seed, uint32_t sample, uint32_t step1, uint32_t q) {
     uint32_t c[4] = {q, sample, step1, 0u};
