@@ -226,6 +226,7 @@ extern "C" int nd_affine_silu_add_f32(const float* t, int ldt, const float* mad,
                                       int ldr1, float* out, int ldo, int B, int HW, int C, void* stream) {
     ND_REQUIRE(t && mad && out, ND_E_BADARG, "nd_affine_silu_add: null pointer");
     ND_REQUIRE(B > 0 && HW > 0 && C > 0 && C % 4 == 0, ND_E_SHAPE, "nd_affine_silu_add: C=%d must be a multiple of 4", C);
+    ND_REQUIRE(ldt >= C && ldo >= C && (!res0 || ldr0 >= C) && (!res1 || ldr1 >= C), ND_E_SHAPE, "nd_affine_silu_add: strides >= C");
     ND_REQUIRE(ldt % 4 == 0 && ldo % 4 == 0 && (!res0 || ldr0 % 4 == 0) && (!res1 || ldr1 % 4 == 0), ND_E_ALIGN, "nd_affine_silu_add: strides");
     ND_REQUIRE(nd_aligned16(t) && nd_aligned16(mad) && nd_aligned16(res0) && nd_aligned16(res1) && nd_aligned16(out), ND_E_ALIGN,
                "nd_affine_silu_add: pointers must be 16-byte aligned");
@@ -241,7 +242,8 @@ extern "C" int nd_affine_silu_add_f32(const float* t, int ldt, const float* mad,
 
 extern "C" int nd_rmsnorm_nhwc_f32(const float* x, int ldx, const float* g, float* out, int ldo, int B, int HW, int C, void* stream) {
     ND_REQUIRE(x && g && out, ND_E_BADARG, "nd_rmsnorm: null pointer");
-    ND_REQUIRE(B > 0 && HW > 0 && C > 0 && C % 4 == 0 && ldx % 4 == 0 && ldo % 4 == 0, ND_E_SHAPE, "nd_rmsnorm: C and strides must be multiples of 4");
+    ND_REQUIRE(B > 0 && HW > 0 && C > 0 && C % 4 == 0 && ldx % 4 == 0 && ldo % 4 == 0 && ldx >= C && ldo >= C, ND_E_SHAPE,
+               "nd_rmsnorm: C and strides must be multiples of 4, strides >= C");
     ND_REQUIRE(nd_aligned16(x) && nd_aligned16(g) && nd_aligned16(out), ND_E_ALIGN, "nd_rmsnorm: alignment");
     const size_t npix = (size_t)B * HW;
     const int blocks = (int)((npix + 3) / 4 < 4096 ? (npix + 3) / 4 : 4096);

@@ -16,7 +16,7 @@ pytestmark = pytest.mark.gpu
 
 from noisediff_amd import _lib as L, synth
 from oracle import noisediff_oracle as O
-from util import rel_err
+from util import derived, rel_err
 
 TOL = 2e-5
 
@@ -653,11 +653,15 @@ def test_linear_attention_matches_reference_semantics(ctx, N, golden):
     qd = hu.dev(qkv)
     L.call("nd_linear_attention_f32", qd.data_ptr(), 3 * heads * dh, out.data_ptr(), heads * dh, ws.data_ptr(), B, N, heads, dh, ctx.stream)
     ctx.sync()
-    q, k, v = (t.reshape(B, N, heads, dh).permute(0, 2, 3, 1) for t in qkv.chunk(3, dim=-1))      # b h c n
-    q = q.softmax(dim=-2) * dh ** -0.5
-    k = k.softmax(dim=-1)
-    ref = torch.einsum("bhde,bhdn->bhen", torch.einsum("bhdn,bhen->bhde", k, v), q)                # b h e n
-    assert rel_err(out.cpu(), ref.permute(0, 3, 1, 2).reshape(B, N, heads * dh)) < TOL
+    def core(dtype):
+        q, k, v = (t.reshape(B, N, heads, dh).permute(0, 2, 3, 1) for t in qkv.to(dtype).chunk(3, dim=-1))      # b h c n
+        q = q.softmax(dim=-2) * dh ** -0.5
+        k = k.softmax(dim=-1)
+        ref = torch.einsum("bhde,bhdn->bhen", torch.einsum("bhdn,bhen->bhde", k, v), q)            # b h e n
+        return ref.permute(0, 3, 1, 2).reshape(B, N, heads * dh)
+    # the outputs shrink with N (max|ref| 0.079 at N = 64, 0.014 at 2248): float64 reference, scale max|ref| without rel_err's floor of 1, bound from the
+    # fp32 torch evaluation's own error (util.derived)
+    derived(out.cpu(), core(torch.float64), core(torch.float32), f"N {N}")
     if N != 64:
         return
     # full block on the golden input (B=2, C=128, 8x8)
