@@ -382,6 +382,57 @@ int nd_philox_poisson_f32(const float* rate, float* out, uint64_t seed, int64_t 
                           void* stream);
 /* A Bayer map [H2][W2] -> planes [4][H2/2][W2/2] in pack_np_raw's channel order: plane c at (Y, X) is bayer[2Y + (c >= 2)][2X + (c == 1 || c == 2)]. */
 int nd_pack_darkshading_f32(const float* bayer, float* planes, int H2, int W2, void* stream);
+
+/* ------------------------------------------------------------------ raw Bayer frames (utils/raw_util.py:17-35,112-139, test_denoising.py:86-114,267-293,
+ * dataloader/dataset_denoising.py:172-372).  frames: uint16 [N][H2][W2] in DEVICE memory, H2 and W2 even; packed pixel (Y, X) has channel
+ * 0 = Bayer (2Y, 2X), 1 = (2Y, 2X+1), 2 = (2Y+1, 2X+1), 3 = (2Y+1, 2X): pack_raw's order and nd_pack_darkshading_f32's.  One row of `table`
+ * (DEVICE memory, rewritten between replays of a captured launch) per output sample: output row y of the h x w window reads packed row
+ * y0 + (flip ? h-1-y : y) (torch.flip(dims=[2])) and column x0 + x of frame `frame`.  x0, y0: any integers with the window inside the frame
+ * (and inside the shading planes where they are read).  A row that points outside gives NaN for its sample and reads nothing.
+ * black, white: the sensor's levels (512, 16383); wb = white - black in fp32.  d = (ds_k[c][Y][X] * iso + ds_b[c][Y][X]) + blc in fp32 from
+ * the planes of nd_pack_darkshading_f32 (`branch` != 0: the high-ISO pair).  Every operation below is one IEEE operation, in this order. */
+typedef struct nd_raw_sample {
+    int32_t frame;          /* index of the frame the window is read from                                                  */
+    int32_t frame_clean;    /* ND_RAW_TRAIN_REAL: index of the long-exposure frame written to clean_out                      */
+    int32_t x0, y0;         /* window origin in packed pixels                                                              */
+    int32_t flip;           /* != 0: rows reversed                                                                         */
+    int32_t branch;         /* != 0: the high-ISO planes (iso > 1600)                                                      */
+    float iso, ratio, blc;  /* blc = blc_mean[iso]                                                                         */
+    int32_t reserved;
+    double k, sd, ratio64;  /* nd_raw_poisson_gaussian_f32: the gain, sqrt(var) and the ratio in fp64                        */
+} nd_raw_sample;
+enum nd_raw_mode {
+    ND_RAW_PACK = 0,        /* v = max(x - black, 0); ND_RAW_RESCALE: v = v / wb; ND_RAW_CLIP: v = clip(v * ratio, 0, 1)     (pack_raw) */
+    ND_RAW_PACK_SHADED = 1, /* v = (x - black) / wb; v = clip(v * ratio, 0, 1); v = v / ratio; v = v * wb + black; v = clip(v, 0, white);
+                             * v = v - d; v = max(v - black, 0); v = v / wb; v = clip(v * ratio, 0, 1)
+                             * (pack_raw_withdarkshading(...) * ratio and load_image's clip); needs the planes                         */
+    ND_RAW_TRAIN_REAL = 2   /* v = max(x - black, 0); v = v - d (with planes); v = v * ratio; v = clip(v, 0, wb); v = v / wb; and
+                             * clean_out = max(x' - black, 0) / wb from frame_clean  (RealSonyDenoisingDataset.__getitem__)             */
+};
+#define ND_RAW_RESCALE 1
+#define ND_RAW_CLIP 2
+/* out (and clean_out for ND_RAW_TRAIN_REAL, NULL otherwise): fp32 NCHW [B][4][h][w], x = (float)code.  The four planes: all or none,
+ * [4][map_h][map_w].  frames and the table 4-byte aligned at least (the table 8-byte), outputs 4-byte; a thread takes 4, 2 or 1 packed
+ * columns (the widest that w and the outputs' alignment allow) and loads by the widest form each address allows. */
+int nd_raw_pack_u16_f32(const uint16_t* frames, int N, int H2, int W2, const float* ds_k_high, const float* ds_b_high, const float* ds_k_low,
+                        const float* ds_b_low, int map_h, int map_w, const nd_raw_sample* table, int mode, int flags, float black, float white,
+                        float* out, float* clean_out, int B, int h, int w, void* stream);
+/* PossionGaussianDenoisingDataset.apply_noise (:332-345) fused with pack_raw(rescale=False) and the two divisions of __getitem__ (:359-360):
+ *   c = max(x - black, 0) (fp32); latent = c / (float)ratio64 (fp32); lam = (double)latent / k; n ~ Poisson(lam); z ~ N(0, 1);
+ *   noisy = fl32(clip((k n + sd z) ratio64, 0, wb) / wb), every operation in fp64; clean_out = c / wb (fp32).
+ * n: nd_philox_poisson_f32's generator, key = seed, counter {element index c h w + y w + x of the OUTPUT position, first_sample + b, draw,
+ * block}.  z: Box-Muller in fp64 on words 0 and 1 of block 32 of the same counter (the Poisson draw stops at block 31):
+ * u = (word + 0.5) 2^-32, z = sqrt(-2 log(u0)) cos((2 pi) u1), rounded to fp32 before it is used, so that normals_out replays it exactly.
+ * rng ({seed, first_sample, draw} as int64 in device memory, or NULL) overrides the three arguments.  counts_in / normals_in (fp32
+ * [B][4][h][w] or NULL) replace the draws; counts_out / normals_out (or NULL) return what was used. */
+int nd_raw_poisson_gaussian_f32(const uint16_t* frames, int N, int H2, int W2, const nd_raw_sample* table, const int64_t* rng, uint64_t seed,
+                                int64_t first_sample, int32_t draw, const float* counts_in, const float* normals_in, float* counts_out,
+                                float* normals_out, float black, float white, float* noisy, float* clean_out, int B, int h, int w,
+                                void* stream);
+/* The write half of postprocess_bayer (test_denoising.py:267-293).  img: fp32 [B][4][h][w]; out: uint16 [B][2h][2w].  p = clip(x, 0, 1) by
+ * comparisons; t = (double)p * (white - bl[c]) + bl[c] in fp64; the code is t truncated toward zero, at channel c's Bayer position; a NaN
+ * gives code 0.  bl: black_level_per_channel, four ints in HOST memory, read during the call; 0 <= bl[c] <= white <= 65535. */
+int nd_raw_to_bayer_u16(const float* img, uint16_t* out, const int32_t* bl, int white, int B, int h, int w, void* stream);
 /* (cout, cin) row-major (Linear / 1x1 conv weight) -> [cinP/4][coutP][4]; `unshuffle_c` > 0
  * permutes K from (c p1 p2) to (p1 p2 c) for a pixel-unshuffled input with c = unshuffle_c. */
 int64_t nd_pack_pointwise_weight_floats(int cin, int cout);

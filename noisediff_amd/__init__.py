@@ -2,7 +2,8 @@
 __version__ = "0.1.0"
 
 __all__ = ["GaussianDiffusion", "NoiseDiffNet", "UNet_PosEmbV2", "UNet_PosEmbV2_NoPosition", "UNet_PosEmbV2_CameraCond", "LSID",
-           "TrainableNoiseDiffNet", "TrainableLSID", "__version__"]
+           "TrainableNoiseDiffNet", "TrainableLSID", "pack_raw", "load_pair", "to_bayer", "RealBatchBuilder", "PoissonGaussianBatchBuilder",
+           "__version__"]
 
 
 def __getattr__(name):
@@ -22,4 +23,7 @@ def __getattr__(name):
     if name == "TrainableLSID":
         from .lsid_train import TrainableLSID
         return TrainableLSID
+    if name in ("pack_raw", "load_pair", "to_bayer", "RealBatchBuilder", "PoissonGaussianBatchBuilder"):
+        from . import raw
+        return getattr(raw, name)
     raise AttributeError(name)

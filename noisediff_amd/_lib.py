@@ -61,6 +61,14 @@ class Chain(C.Structure):
                 ("ldo", C.c_int32)]
 
 
+class RawSample(C.Structure):
+    _fields_ = [("frame", C.c_int32), ("frame_clean", C.c_int32), ("x0", C.c_int32), ("y0", C.c_int32), ("flip", C.c_int32),
+                ("branch", C.c_int32), ("iso", C.c_float), ("ratio", C.c_float), ("blc", C.c_float), ("reserved", C.c_int32),
+                ("k", C.c_double), ("sd", C.c_double), ("ratio64", C.c_double)]
+
+
+RAW_PACK, RAW_PACK_SHADED, RAW_TRAIN_REAL = 0, 1, 2       # enum nd_raw_mode
+RAW_RESCALE, RAW_CLIP = 1, 2
 CHAIN_RES_NONE, CHAIN_RES_INPUT, CHAIN_RES_INPUT_RAW = 0, 1, 2
 
 
@@ -202,6 +210,9 @@ SIGNATURES = {
     "nd_denoise_batch_f32": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, vp, vp, vp, u64, i64, i32, vp, vp, vp, vp, i32, i32, i32, i32, vp]),
     "nd_philox_poisson_f32": (i32, [vp, vp, u64, i64, i32, i32, i64, vp]),
     "nd_pack_darkshading_f32": (i32, [vp, vp, i32, i32, vp]),
+    "nd_raw_pack_u16_f32": (i32, [vp, i32, i32, i32, vp, vp, vp, vp, i32, i32, vp, i32, i32, f32, f32, vp, vp, i32, i32, i32, vp]),
+    "nd_raw_poisson_gaussian_f32": (i32, [vp, i32, i32, i32, vp, vp, u64, i64, i32, vp, vp, vp, vp, f32, f32, vp, vp, i32, i32, i32, vp]),
+    "nd_raw_to_bayer_u16": (i32, [vp, vp, C.POINTER(C.c_int32), i32, i32, i32, i32, vp]),
 }
 
 _UNCHECKED = {"nd_version", "nd_last_error", "nd_stream_device", "nd_conv3x3_wgrad_form", "nd_adam_chunk_elements", "nd_conv7x7_c4_wgrad_workspace_floats", "nd_conv3x3_stat_slots", "nd_conv3x3_tiling_id", "nd_pack_conv3x3_weight_floats",

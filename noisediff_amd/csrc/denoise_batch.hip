@@ -27,83 +27,11 @@
 
 #pragma clang fp contract(off)
 
+#include "philox_poisson.h"          // philox_poisson(lam, seed, elem, sample, draw): the draw described above, shared with raw.hip
+
 namespace {
 
 constexpr int DB_THREADS = 256;
-constexpr int PO_INV_MAX = 200;           // steps of the inversion search: P(k > 200 | lam < 10) = 0 in fp64; a bound for u above the rounded sum
-constexpr int PO_MAX_ATTEMPTS = 64;       // rejection attempts: each accepts with probability > 0.75
-
-__device__ __forceinline__ float db_clip(float v, float lo, float hi) { return v < lo ? lo : (v > hi ? hi : v); }     // NaN passes through
-
-__device__ __forceinline__ double po_uniform(uint32_t w) { return ((double)w + 0.5) * (1.0 / 4294967296.0); }
-
-// One Poisson(lam) count as a double.  elem / sample / draw are the counter words; see the head of the file.  Inlined: as a call it takes
-// the calling convention's worst-case registers and spills to scratch.
-__device__ __forceinline__ double philox_poisson(double lam, uint64_t seed, uint32_t elem, uint32_t sample, uint32_t draw) {
-    if (!(lam > 0.0)) return lam == 0.0 ? 0.0 : __builtin_nan("");
-    if (!(lam <= 1.7976931348623157e308)) return __builtin_nan("");
-    const uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
-    if (lam < 10.0) {
-        uint32_t c[4] = {elem, sample, draw, 0u};
-        Philox::gen(c, k0, k1);
-        const double u = po_uniform(c[0]);
-        double p = exp(-lam), s = p, k = 0.0;
-        while (u > s && k < (double)PO_INV_MAX) {
-            k += 1.0;
-            p *= lam / k;
-            s += p;
-        }
-        return k;
-    }
-    const double sl = sqrt(lam), ll = log(lam);
-    const double b = 0.931 + 2.53 * sl, a = -0.059 + 0.02483 * b;
-    const double lia = log(1.1239 + 1.1328 / (b - 3.4)), vr = 0.9277 - 3.6224 / (b - 2.0);
-    uint32_t c[4] = {0u, 0u, 0u, 0u};
-    for (int t = 0; t < PO_MAX_ATTEMPTS; ++t) {
-        if ((t & 1) == 0) {
-            c[0] = elem;  c[1] = sample;  c[2] = draw;  c[3] = (uint32_t)(t >> 1);
-            Philox::gen(c, k0, k1);
-        }
-        const double U = po_uniform(c[2 * (t & 1)]) - 0.5, V = po_uniform(c[2 * (t & 1) + 1]);
-        const double us = 0.5 - fabs(U);
-        const double k = floor((2.0 * a / us + b) * U + lam + 0.43);
-        if (us >= 0.07 && V <= vr) return k;
-        if (k < 0.0 || (us < 0.013 && V > us)) continue;
-        const double lhs = log(V) + lia - log(a / (us * us) + b);
-        const double rhs = -lam + k * ll - lgamma(k + 1.0);
-        if (lhs <= rhs) return k;
-    }
-    return __builtin_nan("");
-}
-
-// V consecutive floats from p, by the widest load p's alignment allows (p is 4-byte aligned at least)
-template <int V>
-__device__ __forceinline__ void db_load(const float* p, float (&r)[V]) {
-    static_assert(V == 2 || V == 4, "two or four columns per thread");
-    const uintptr_t a = (uintptr_t)p;
-    if constexpr (V == 4) {
-        if ((a & 15u) == 0) {
-            const f32x4 t = nd_ld4(p);
-            r[0] = t[0];  r[1] = t[1];  r[2] = t[2];  r[3] = t[3];
-            return;
-        }
-    }
-    if ((a & 7u) == 0) {
-#pragma unroll
-        for (int i = 0; i < V; i += 2) {
-            const f32x2 t = *reinterpret_cast<const f32x2*>(p + i);
-            r[i] = t[0];  r[i + 1] = t[1];
-        }
-    } else {
-#pragma unroll
-        for (int i = 0; i < V; ++i) r[i] = p[i];
-    }
-}
-template <int V>
-__device__ __forceinline__ void db_store(float* p, const float (&r)[V]) {      // p is V * 4-byte aligned: checked on the host
-    if constexpr (V == 4) nd_st4(p, f32x4{r[0], r[1], r[2], r[3]});
-    else *reinterpret_cast<f32x2*>(p) = f32x2{r[0], r[1]};
-}
 
 struct DbArgs {
     const float* noise;  const float* clean;
@@ -139,40 +67,40 @@ __global__ __launch_bounds__(DB_THREADS) void denoise_batch_kernel(DbArgs A) {
         float nanv[V];
 #pragma unroll
         for (int i = 0; i < V; ++i) nanv[i] = __builtin_nanf("");
-        db_store<V>(A.noisy + o, nanv);
-        db_store<V>(A.clean_out + o, nanv);
-        if (A.counts_out) db_store<V>(A.counts_out + o, nanv);
+        nd_store_v<V>(A.noisy + o, nanv);
+        nd_store_v<V>(A.clean_out + o, nanv);
+        if (A.counts_out) nd_store_v<V>(A.counts_out + o, nanv);
         return;
     }
     const int ys = s.cy + (s.flip ? h - 1 - y : y), xs = s.cx + x;
     const size_t src = (((size_t)b * 4 + c) * P + ys) * P + xs;
     float nz[V], cl[V], v[V], g[V];
-    db_load<V>(A.noise + src, nz);
-    db_load<V>(A.clean + src, cl);
+    nd_load_v<V>(A.noise + src, nz);
+    nd_load_v<V>(A.clean + src, cl);
 #pragma unroll
     for (int i = 0; i < V; ++i) {
-        const float n = db_clip(nz[i], -1.0f, 1.0f);
-        v[i] = db_clip(n + cl[i], 0.0f, 1.0f);
-        g[i] = db_clip(cl[i], 0.0f, 1.0f);
+        const float n = nd_clip(nz[i], -1.0f, 1.0f);
+        v[i] = nd_clip(n + cl[i], 0.0f, 1.0f);
+        g[i] = nd_clip(cl[i], 0.0f, 1.0f);
     }
     if (shading) {
         const size_t m = ((size_t)c * A.Hm + (s.y0 + ys)) * A.Wm + (s.x0 + xs);
         const int pair = s.branch ? 0 : 2;                  // iso > 1600: the high-ISO maps
         float dk[V], dbv[V];
-        db_load<V>(A.ds[pair] + m, dk);
-        db_load<V>(A.ds[pair + 1] + m, dbv);
+        nd_load_v<V>(A.ds[pair] + m, dk);
+        nd_load_v<V>(A.ds[pair + 1] + m, dbv);
 #pragma unroll
         for (int i = 0; i < V; ++i) {
             float im = v[i] / s.ratio;
             im = im * 15871.0f + 512.0f;
-            im = db_clip(im, 0.0f, 16383.0f);
+            im = nd_clip(im, 0.0f, 16383.0f);
             const float dark = (dk[i] * s.iso + dbv[i]) + s.blc;
             im = im - dark;
             im = im - 512.0f;
             im = im < 0.0f ? 0.0f : im;
             im = im / 15871.0f;
             im = im * s.ratio;
-            v[i] = db_clip(im, 0.0f, 1.0f);
+            v[i] = nd_clip(im, 0.0f, 1.0f);
         }
     }
     float wbc = 0.0f, K = 0.0f;
@@ -188,7 +116,7 @@ __global__ __launch_bounds__(DB_THREADS) void denoise_batch_kernel(DbArgs A) {
     for (int i = 0; i < V; ++i) cnt[i] = 0.0f;
     if (sna) {
         if (A.counts_in) {
-            db_load<V>(A.counts_in + o, cnt);
+            nd_load_v<V>(A.counts_in + o, cnt);
         } else {
             uint64_t seed = A.seed;
             int64_t first = A.first_sample;
@@ -212,9 +140,9 @@ __global__ __launch_bounds__(DB_THREADS) void denoise_batch_kernel(DbArgs A) {
             g[i] = g[i] + dy;
         }
     }
-    db_store<V>(A.noisy + o, v);
-    db_store<V>(A.clean_out + o, g);
-    if (A.counts_out) db_store<V>(A.counts_out + o, cnt);
+    nd_store_v<V>(A.noisy + o, v);
+    nd_store_v<V>(A.clean_out + o, g);
+    if (A.counts_out) nd_store_v<V>(A.counts_out + o, cnt);
 }
 
 __global__ __launch_bounds__(DB_THREADS) void philox_poisson_kernel(const float* __restrict__ rate, float* __restrict__ out, uint64_t seed,

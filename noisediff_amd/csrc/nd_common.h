@@ -118,6 +118,40 @@ __device__ __forceinline__ float nd_act(float v, int act) {
 __device__ __forceinline__ f32x4 nd_ld4(const float* p) { return *reinterpret_cast<const f32x4*>(p); }
 __device__ __forceinline__ void nd_st4(float* p, f32x4 v) { *reinterpret_cast<f32x4*>(p) = v; }
 
+__device__ __forceinline__ float nd_clip(float v, float lo, float hi) { return v < lo ? lo : (v > hi ? hi : v); }       // NaN passes through
+
+// V = 1, 2 or 4 consecutive floats from p, by the widest load p's alignment allows (p is 4-byte aligned at least)
+template <int V>
+__device__ __forceinline__ void nd_load_v(const float* p, float (&r)[V]) {
+    static_assert(V == 1 || V == 2 || V == 4, "one, two or four columns per thread");
+    const uintptr_t a = (uintptr_t)p;
+    if constexpr (V == 4) {
+        if ((a & 15u) == 0) {
+            const f32x4 t = nd_ld4(p);
+            r[0] = t[0];  r[1] = t[1];  r[2] = t[2];  r[3] = t[3];
+            return;
+        }
+    }
+    if constexpr (V >= 2) {
+        if ((a & 7u) == 0) {
+#pragma unroll
+            for (int i = 0; i < V; i += 2) {
+                const f32x2 t = *reinterpret_cast<const f32x2*>(p + i);
+                r[i] = t[0];  r[i + 1] = t[1];
+            }
+            return;
+        }
+    }
+#pragma unroll
+    for (int i = 0; i < V; ++i) r[i] = p[i];
+}
+template <int V>
+__device__ __forceinline__ void nd_store_v(float* p, const float (&r)[V]) {      // p is V * 4-byte aligned: the caller's host side checks it
+    if constexpr (V == 4) nd_st4(p, f32x4{r[0], r[1], r[2], r[3]});
+    else if constexpr (V == 2) *reinterpret_cast<f32x2*>(p) = f32x2{r[0], r[1]};
+    else p[0] = r[0];
+}
+
 __device__ __forceinline__ f32x4 nd_silu4(f32x4 v) {
     f32x4 r;
     r.x = nd_silu(v.x); r.y = nd_silu(v.y); r.z = nd_silu(v.z); r.w = nd_silu(v.w);

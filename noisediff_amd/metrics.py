@@ -8,7 +8,8 @@ For each SID / ELD frame the reference runs ``net(noisy).clamp(0, 1)``, ``Illumi
   illumination correction is fused into the read of ``est``;
 - ``IlluminanceCorrect``: the reference's module, ``forward(predict, source)``;
 - ``quality_assess(X, Y, data_range=255)``: the reference's function, same arguments and return dict of floats;
-- ``evaluate(net, noisy, clean)``: a whole ``test_denoising.py`` frame (steps 1-4) for a batch, one host read at the end.
+- ``evaluate(net, noisy, clean)``: a whole ``test_denoising.py`` frame (steps 1-4) for a batch, one host read at the end;
+- ``evaluate_raw(net, short, long, iso, ratio, shading)``: the same from the uint16 Bayer pair (``raw.load_pair``, then ``evaluate``).
 
 The numerical contract (clip keeping NaN, fp64 accumulation, the interior crop, the fp32 scale) is in DESIGN.md, "Scoring the denoiser".
 Deterministic: a repeated call gives the same bits and an image's results do not depend on the batch it is in.  CPU tensors raise
@@ -163,3 +164,11 @@ def evaluate(net: nn.Module, noisy: torch.Tensor, clean: torch.Tensor, correct_i
         r = quality(est * data_range, _f32(clean) * data_range, data_range)       # the kernel clips both to [0, data_range]
     v = torch.stack([r["PSNR"], r["SSIM"], r["MSE"]]).cpu().numpy()
     return {"PSNR": v[0], "SSIM": v[1], "MSE": v[2]}
+
+
+def evaluate_raw(net: nn.Module, short, long, iso: int, ratio: float, shading=None, correct_illum: bool = True) -> Dict[str, np.ndarray]:
+    """A ``test_denoising.py`` frame from its uint16 Bayer pair: ``raw.load_pair(short, long, iso, ratio, shading)`` (load_image, :86-114, with
+    ``shading`` for --correct_darkshading) followed by ``evaluate``.  short, long: (2H, 2W) numpy uint16 or 16-bit integer device tensors."""
+    from .raw import load_pair
+    noisy, clean = load_pair(short, long, iso, ratio, shading)
+    return evaluate(net, noisy, clean, correct_illum=correct_illum)
