@@ -433,6 +433,24 @@ int nd_raw_poisson_gaussian_f32(const uint16_t* frames, int N, int H2, int W2, c
  * comparisons; t = (double)p * (white - bl[c]) + bl[c] in fp64; the code is t truncated toward zero, at channel c's Bayer position; a NaN
  * gives code 0.  bl: black_level_per_channel, four ints in HOST memory, read during the call; 0 <= bl[c] <= white <= 65535. */
 int nd_raw_to_bayer_u16(const float* img, uint16_t* out, const int32_t* bl, int white, int B, int h, int w, void* stream);
+/* The sample of the diffusion sets (dataloader/dataset.py: SonyTrainDataset.__getitem__ :106-145, NoiseImageGenerationDataset :242-281,
+ * GenDarkFrameDataset :376-414) for a batch of windows.  noise, noisy, clean: fp32 NCHW [B][4][h][w]; coord: [B][2][h][w].  Row b of `table`
+ * gives the short exposure (frame), the long one (frame_clean), x0, y0 and ratio; flip, branch, iso, blc, k, sd and ratio64 are not read.
+ * Output position (y, x) is packed pixel (Y, X) = (y0 + y, x0 + x); x and x' are the short and the long frame's codes as (float), H = H2 / 2,
+ * W = W2 / 2, wb = white - black.  One IEEE fp32 operation per step:
+ *   sv = x - black; sv = sv < 0 ? 0 : sv; sv = sv / wb; noisy = clip(sv * ratio, 0, 1) by comparisons (a NaN passes through);
+ *   g = x' - black; g = g < 0 ? 0 : g; clean = g / wb   -- not clipped: gt_norm is not, and a code above white gives more than 1;
+ *   noise = noisy - clean;
+ *   coord[0] = (float)Y / (float)(H - 1); coord[1] = (float)X / (float)(W - 1)   -- util.make_coord(H, W, rescale=True) channels first:
+ *   the row, then the column, over the WHOLE frame's H and W.
+ * Each output may be NULL and is then neither computed nor written; one at least is given.  `frame` is validated and read only for noise or
+ * noisy, `frame_clean` only for noise or clean; with coord alone frames may be NULL and N is ignored (the dark-frame set).  A row whose window
+ * leaves the frame, or whose needed frame index is outside [0, N), gives NaN in every requested output of its sample and reads nothing.
+ * Every refusal is ND_E_BADARG, before any device call: odd sides, a packed side below 2 (the coordinates divide by H - 1 and W - 1), h, w or
+ * B <= 0, h > H, w > W, a NULL table, no output, NULL frames with noise, noisy or clean requested, frames or an output not 4-byte aligned.
+ * A thread takes 4, 2 or 1 packed columns: the widest that w and the given outputs' alignment allow. */
+int nd_raw_diffusion_batch_f32(const uint16_t* frames, int N, int H2, int W2, const nd_raw_sample* table, float black, float white, float* noise,
+                               float* noisy, float* clean, float* coord, int B, int h, int w, void* stream);
 /* (cout, cin) row-major (Linear / 1x1 conv weight) -> [cinP/4][coutP][4]; `unshuffle_c` > 0
  * permutes K from (c p1 p2) to (p1 p2 c) for a pixel-unshuffled input with c = unshuffle_c. */
 int64_t nd_pack_pointwise_weight_floats(int cin, int cout);

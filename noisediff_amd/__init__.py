@@ -3,7 +3,7 @@ __version__ = "0.1.0"
 
 __all__ = ["GaussianDiffusion", "NoiseDiffNet", "UNet_PosEmbV2", "UNet_PosEmbV2_NoPosition", "UNet_PosEmbV2_CameraCond", "LSID",
            "TrainableNoiseDiffNet", "TrainableLSID", "pack_raw", "load_pair", "to_bayer", "RealBatchBuilder", "PoissonGaussianBatchBuilder",
-           "__version__"]
+           "DiffusionBatchBuilder", "GenerationBatchBuilder", "balanced_sample_list", "__version__"]
 
 
 def __getattr__(name):
@@ -26,4 +26,7 @@ def __getattr__(name):
     if name in ("pack_raw", "load_pair", "to_bayer", "RealBatchBuilder", "PoissonGaussianBatchBuilder"):
         from . import raw
         return getattr(raw, name)
+    if name in ("DiffusionBatchBuilder", "GenerationBatchBuilder", "balanced_sample_list"):
+        from . import diffusion_data
+        return getattr(diffusion_data, name)
     raise AttributeError(name)

@@ -213,6 +213,7 @@ SIGNATURES = {
     "nd_raw_pack_u16_f32": (i32, [vp, i32, i32, i32, vp, vp, vp, vp, i32, i32, vp, i32, i32, f32, f32, vp, vp, i32, i32, i32, vp]),
     "nd_raw_poisson_gaussian_f32": (i32, [vp, i32, i32, i32, vp, vp, u64, i64, i32, vp, vp, vp, vp, f32, f32, vp, vp, i32, i32, i32, vp]),
     "nd_raw_to_bayer_u16": (i32, [vp, vp, C.POINTER(C.c_int32), i32, i32, i32, i32, vp]),
+    "nd_raw_diffusion_batch_f32": (i32, [vp, i32, i32, i32, vp, f32, f32, vp, vp, vp, vp, i32, i32, i32, vp]),
 }
 
 _UNCHECKED = {"nd_version", "nd_last_error", "nd_stream_device", "nd_conv3x3_wgrad_form", "nd_adam_chunk_elements", "nd_conv7x7_c4_wgrad_workspace_floats", "nd_conv3x3_stat_slots", "nd_conv3x3_tiling_id", "nd_pack_conv3x3_weight_floats",

@@ -3,11 +3,12 @@
 // The reference starts every test_denoising.py frame and every RealSony / Poisson-Gaussian training sample from a uint16 Bayer frame with a
 // dozen whole-frame numpy passes on the host (utils/raw_util.py pack_raw :17-35, pack_raw_withdarkshading :112-139; test_denoising.py
 // load_image :86-114; dataloader/dataset_denoising.py :232-265, :332-360) and ends a visualised frame with postprocess_bayer (:267-293).
-// Here the frames stay on the device as uint16 and three kernels do the arithmetic:
+// Here the frames stay on the device as uint16 and four kernels do the arithmetic:
 //
 //   raw_pack_kernel<V, MODE>   windows of frames -> fp32 NCHW (B, 4, h, w), MODE = ND_RAW_PACK / ND_RAW_PACK_SHADED / ND_RAW_TRAIN_REAL
 //   raw_pg_kernel<V>           the same windows with Poisson-Gaussian noise drawn per element (apply_noise)
 //   raw_bayer_kernel<V>        fp32 (B, 4, h, w) -> uint16 (B, 2h, 2w)
+//   raw_diffusion_kernel<V>    the diffusion sets' sample (dataloader/dataset.py): noise, noisy, clean (B, 4, h, w) and coord (B, 2, h, w), any subset
 //
 // The arithmetic of each is listed step by step in include/noisediff_hip.h.  Every fp32 and fp64 operation is a single IEEE operation in the
 // order written there: contraction to fma is off for this file, so numpy repeats it bit for bit.
@@ -337,6 +338,109 @@ void rw_launch_pack(int V, dim3 grid, hipStream_t st, const RawArgs& A) {
     else hipLaunchKernelGGL((raw_pack_kernel<1, MODE>), grid, dim3(RW_THREADS), 0, st, A);
 }
 
+struct DiffusionArgs {
+    const uint16_t* frames;             // null when only coord is asked for
+    const nd_raw_sample* table;         // [B]
+    float* noise;  float* noisy;  float* clean;  float* coord;      // each may be null: neither computed nor written
+    int N, H, W, h, w;                  // H, W: the packed frame
+    float black, white;
+};
+
+// The diffusion sets' sample (dataloader/dataset.py SonyTrainDataset / NoiseImageGenerationDataset / GenDarkFrameDataset): noisy and clean from the
+// short and the long exposure of one window, their difference, and the window's coordinates within the whole frame.  Threads as in raw_pack_kernel:
+// thread i of block row blockIdx.y = sample b takes packed columns V (i mod (w / V)) .. + V - 1 of output row i / (w / V), all four channels.
+template <int V>
+__global__ __launch_bounds__(RW_THREADS) void raw_diffusion_kernel(DiffusionArgs A) {
+    const int b = blockIdx.y;
+    const int h = A.h, w = A.w, wv = w / V;
+    const size_t t = (size_t)blockIdx.x * RW_THREADS + threadIdx.x;
+    if (t >= (size_t)h * wv) return;
+    const int y = (int)(t / wv), x = (int)(t - (size_t)y * wv) * V;
+    const nd_raw_sample s = A.table[b];
+    const size_t plane = (size_t)h * w;
+    const size_t px = (size_t)y * w + x;
+    const size_t o4 = (size_t)b * 4 * plane + px, o2 = (size_t)b * 2 * plane + px;
+    const bool need_short = A.noise || A.noisy, need_long = A.noise || A.clean;
+
+    // rw_window_ok's frame test is applied to each frame this launch reads, and to none when it reads none
+    nd_raw_sample win = s;
+    bool ok = true;
+    if (need_long) {
+        win.frame = s.frame_clean;
+        ok = rw_window_ok(win, A.N, A.H, A.W, h, w);
+    }
+    win.frame = need_short ? s.frame : 0;
+    ok = ok && rw_window_ok(win, need_short ? A.N : 1, A.H, A.W, h, w);
+    if (!ok) {
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+            if (A.noise) rw_store_nan<V>(A.noise + o4 + c * plane);
+            if (A.noisy) rw_store_nan<V>(A.noisy + o4 + c * plane);
+            if (A.clean) rw_store_nan<V>(A.clean + o4 + c * plane);
+            if (c < 2 && A.coord) rw_store_nan<V>(A.coord + o2 + c * plane);
+        }
+        return;
+    }
+    const int Y = s.y0 + y, X = s.x0 + x;
+    const size_t W2 = 2 * (size_t)A.W;
+    const size_t cell = (2 * (size_t)Y) * W2 + 2 * (size_t)X;
+    uint32_t st[V], sb[V], lt[V], lb[V];
+#pragma unroll
+    for (int i = 0; i < V; ++i) st[i] = sb[i] = lt[i] = lb[i] = 0u;
+    if (need_short) {
+        const uint16_t* src = A.frames + (size_t)s.frame * (2 * (size_t)A.H) * W2 + cell;
+        rw_load_pairs<V>(src, st);
+        rw_load_pairs<V>(src + W2, sb);
+    }
+    if (need_long) {
+        const uint16_t* src = A.frames + (size_t)s.frame_clean * (2 * (size_t)A.H) * W2 + cell;
+        rw_load_pairs<V>(src, lt);
+        rw_load_pairs<V>(src + W2, lb);
+    }
+    const float black = A.black, wb = A.white - black;
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+        float ny[V], cl[V];
+#pragma unroll
+        for (int i = 0; i < V; ++i) ny[i] = cl[i] = 0.0f;
+        if (need_short) {
+#pragma unroll
+            for (int i = 0; i < V; ++i) {
+                float sv = rw_code(st[i], sb[i], c) - black;
+                sv = sv < 0.0f ? 0.0f : sv;
+                sv = sv / wb;
+                ny[i] = nd_clip(sv * s.ratio, 0.0f, 1.0f);
+            }
+        }
+        if (need_long) {
+#pragma unroll
+            for (int i = 0; i < V; ++i) {
+                const float g = rw_code(lt[i], lb[i], c) - black;
+                cl[i] = (g < 0.0f ? 0.0f : g) / wb;                             // gt_norm is not clipped: a code above white gives more than 1
+            }
+        }
+        if (A.noise) {
+            float nz[V];
+#pragma unroll
+            for (int i = 0; i < V; ++i) nz[i] = ny[i] - cl[i];
+            nd_store_v<V>(A.noise + o4 + c * plane, nz);
+        }
+        if (A.noisy) nd_store_v<V>(A.noisy + o4 + c * plane, ny);
+        if (A.clean) nd_store_v<V>(A.clean + o4 + c * plane, cl);
+    }
+    if (A.coord) {                                                              // make_coord(H, W, rescale=True): row, then column, over the whole frame
+        float cy[V], cx[V];
+        const float row = (float)Y / (float)(A.H - 1), wm = (float)(A.W - 1);
+#pragma unroll
+        for (int i = 0; i < V; ++i) {
+            cy[i] = row;
+            cx[i] = (float)(X + i) / wm;
+        }
+        nd_store_v<V>(A.coord + o2, cy);
+        nd_store_v<V>(A.coord + o2 + plane, cx);
+    }
+}
+
 }  // namespace
 
 extern "C" int nd_raw_pack_u16_f32(const uint16_t* frames, int N, int H2, int W2, const float* ds_k_high, const float* ds_b_high,
@@ -418,5 +522,34 @@ extern "C" int nd_raw_to_bayer_u16(const float* img, uint16_t* out, const int32_
     if (V == 4) hipLaunchKernelGGL(raw_bayer_kernel<4>, grid, dim3(RW_THREADS), 0, (hipStream_t)stream, A);
     else if (V == 2) hipLaunchKernelGGL(raw_bayer_kernel<2>, grid, dim3(RW_THREADS), 0, (hipStream_t)stream, A);
     else hipLaunchKernelGGL(raw_bayer_kernel<1>, grid, dim3(RW_THREADS), 0, (hipStream_t)stream, A);
+    return nd_launch_status(who);
+}
+
+extern "C" int nd_raw_diffusion_batch_f32(const uint16_t* frames, int N, int H2, int W2, const nd_raw_sample* table, float black, float white,
+                                          float* noise, float* noisy, float* clean, float* coord, int B, int h, int w, void* stream) {
+    const char* who = "nd_raw_diffusion_batch_f32";
+    const bool reads = noise || noisy || clean;
+    ND_REQUIRE(table, ND_E_BADARG, "%s: null table", who);
+    ND_REQUIRE(reads || coord, ND_E_BADARG, "%s: give at least one of noise, noisy, clean and coord", who);
+    ND_REQUIRE(frames || !reads, ND_E_BADARG, "%s: noise, noisy and clean need the frames; only coord is made without them", who);
+    ND_REQUIRE(!reads || N > 0, ND_E_BADARG, "%s: N must be positive", who);
+    ND_REQUIRE(H2 > 0 && W2 > 0 && H2 % 2 == 0 && W2 % 2 == 0, ND_E_BADARG, "%s: a Bayer frame has even, positive sides; got %d x %d", who, H2, W2);
+    ND_REQUIRE(H2 >= 4 && W2 >= 4, ND_E_BADARG, "%s: the coordinates divide by H - 1 and W - 1: the packed frame %d x %d needs sides of 2 at least", who,
+               H2 / 2, W2 / 2);
+    ND_REQUIRE(h > 0 && w > 0 && B > 0 && B <= 65535, ND_E_BADARG, "%s: h, w and B (<= 65535) must be positive", who);
+    ND_REQUIRE(h <= H2 / 2 && w <= W2 / 2, ND_E_BADARG, "%s: the window %d x %d does not fit the packed frame %d x %d", who, h, w, H2 / 2, W2 / 2);
+    ND_REQUIRE(white > black && black >= 0.0f && white <= 65535.0f, ND_E_BADARG, "%s: need 0 <= black < white <= 65535", who);
+    const uintptr_t out_bits = (uintptr_t)noise | (uintptr_t)noisy | (uintptr_t)clean | (uintptr_t)coord;
+    ND_REQUIRE(((uintptr_t)frames & 3u) == 0 && (out_bits & 3u) == 0 && ((uintptr_t)table & 7u) == 0, ND_E_BADARG,
+               "%s: frames and outputs must be 4-byte aligned, the table 8-byte", who);
+    DiffusionArgs A;
+    A.frames = frames;  A.table = table;  A.noise = noise;  A.noisy = noisy;  A.clean = clean;  A.coord = coord;
+    A.N = reads ? N : 0;  A.H = H2 / 2;  A.W = W2 / 2;  A.h = h;  A.w = w;  A.black = black;  A.white = white;
+    const int V = rw_width(w, out_bits);
+    const size_t threads = (size_t)h * (w / V);
+    const dim3 grid((unsigned)((threads + RW_THREADS - 1) / RW_THREADS), (unsigned)B);
+    if (V == 4) hipLaunchKernelGGL(raw_diffusion_kernel<4>, grid, dim3(RW_THREADS), 0, (hipStream_t)stream, A);
+    else if (V == 2) hipLaunchKernelGGL(raw_diffusion_kernel<2>, grid, dim3(RW_THREADS), 0, (hipStream_t)stream, A);
+    else hipLaunchKernelGGL(raw_diffusion_kernel<1>, grid, dim3(RW_THREADS), 0, (hipStream_t)stream, A);
     return nd_launch_status(who);
 }
