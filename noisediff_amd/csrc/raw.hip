@@ -18,6 +18,7 @@
 // on the host) and reads 2V codes = 4V bytes from each Bayer row with the widest load the address allows: a window origin is any integer,
 // so a 16-byte row start is the common case and not a promise.  No LDS; grid (tiles, B).
 #include "nd_common.h"
+#include <type_traits>
 
 #pragma clang fp contract(off)
 
@@ -321,6 +322,21 @@ int rw_width(int w, uintptr_t bits) {
     return 1;
 }
 
+// launch(std::integral_constant<int, V>) for V = 4, 2 or 1: the one place a width chosen at run time becomes a kernel's template argument
+template <class F>
+void rw_dispatch(int V, F launch) {
+    if (V == 4) launch(std::integral_constant<int, 4>());
+    else if (V == 2) launch(std::integral_constant<int, 2>());
+    else launch(std::integral_constant<int, 1>());
+}
+
+dim3 rw_grid(size_t threads, int B) { return dim3((unsigned)((threads + RW_THREADS - 1) / RW_THREADS), (unsigned)B); }
+
+int rw_check_levels(const char* who, float black, float white) {
+    ND_REQUIRE(white > black && black >= 0.0f && white <= 65535.0f, ND_E_BADARG, "%s: need 0 <= black < white <= 65535", who);
+    return 0;
+}
+
 int rw_check_frames(const char* who, const void* frames, int N, int H2, int W2, int B, int h, int w) {
     ND_REQUIRE(N > 0 && H2 > 0 && W2 > 0 && h > 0 && w > 0 && B > 0 && B <= 65535, ND_E_BADARG, "%s: N, H2, W2, h, w and B (<= 65535) must be positive",
                who);
@@ -329,13 +345,6 @@ int rw_check_frames(const char* who, const void* frames, int N, int H2, int W2, 
     ND_REQUIRE((int64_t)4 * h * w < (1ll << 32), ND_E_SHAPE, "%s: 4 * h * w must fit the 32-bit element counter", who);
     ND_REQUIRE(((uintptr_t)frames & 3u) == 0, ND_E_ALIGN, "%s: frames must be 4-byte aligned", who);
     return 0;
-}
-
-template <int MODE>
-void rw_launch_pack(int V, dim3 grid, hipStream_t st, const RawArgs& A) {
-    if (V == 4) hipLaunchKernelGGL((raw_pack_kernel<4, MODE>), grid, dim3(RW_THREADS), 0, st, A);
-    else if (V == 2) hipLaunchKernelGGL((raw_pack_kernel<2, MODE>), grid, dim3(RW_THREADS), 0, st, A);
-    else hipLaunchKernelGGL((raw_pack_kernel<1, MODE>), grid, dim3(RW_THREADS), 0, st, A);
 }
 
 struct DiffusionArgs {
@@ -455,7 +464,7 @@ extern "C" int nd_raw_pack_u16_f32(const uint16_t* frames, int N, int H2, int W2
     ND_REQUIRE(nmaps == 0 || nmaps == 4, ND_E_BADARG, "%s: give all four dark-shading planes or none", who);
     ND_REQUIRE(nmaps == 4 || mode != ND_RAW_PACK_SHADED, ND_E_BADARG, "%s: ND_RAW_PACK_SHADED needs the dark-shading planes", who);
     ND_REQUIRE(nmaps == 0 || mode != ND_RAW_PACK, ND_E_BADARG, "%s: ND_RAW_PACK takes no dark-shading planes", who);
-    ND_REQUIRE(white > black && black >= 0.0f && white <= 65535.0f, ND_E_BADARG, "%s: need 0 <= black < white <= 65535", who);
+    if (int r = rw_check_levels(who, black, white)) return r;
     if (int r = rw_check_frames(who, frames, N, H2, W2, B, h, w)) return r;
     ND_REQUIRE(nmaps == 0 || (map_h >= h && map_w >= w), ND_E_SHAPE, "%s: shading planes %d x %d are smaller than the window", who, map_h, map_w);
     ND_REQUIRE(((uintptr_t)table & 7u) == 0 && (((uintptr_t)ds_k_high | (uintptr_t)ds_b_high | (uintptr_t)ds_k_low | (uintptr_t)ds_b_low) & 3u) == 0,
@@ -469,11 +478,12 @@ extern "C" int nd_raw_pack_u16_f32(const uint16_t* frames, int N, int H2, int W2
     A.N = N;  A.H = H2 / 2;  A.W = W2 / 2;  A.Hm = map_h;  A.Wm = map_w;  A.h = h;  A.w = w;
     A.flags = flags;  A.black = black;  A.white = white;
     const int V = rw_width(w, out_bits);
-    const size_t threads = (size_t)h * (w / V);
-    const dim3 grid((unsigned)((threads + RW_THREADS - 1) / RW_THREADS), (unsigned)B);
-    if (mode == ND_RAW_PACK) rw_launch_pack<ND_RAW_PACK>(V, grid, (hipStream_t)stream, A);
-    else if (mode == ND_RAW_PACK_SHADED) rw_launch_pack<ND_RAW_PACK_SHADED>(V, grid, (hipStream_t)stream, A);
-    else rw_launch_pack<ND_RAW_TRAIN_REAL>(V, grid, (hipStream_t)stream, A);
+    rw_dispatch(V, [&](auto v) {
+        const auto kernel = mode == ND_RAW_PACK          ? raw_pack_kernel<v(), ND_RAW_PACK>
+                            : mode == ND_RAW_PACK_SHADED ? raw_pack_kernel<v(), ND_RAW_PACK_SHADED>
+                                                         : raw_pack_kernel<v(), ND_RAW_TRAIN_REAL>;
+        hipLaunchKernelGGL(kernel, rw_grid((size_t)h * (w / V), B), dim3(RW_THREADS), 0, (hipStream_t)stream, A);
+    });
     return nd_launch_status(who);
 }
 
@@ -484,7 +494,7 @@ extern "C" int nd_raw_poisson_gaussian_f32(const uint16_t* frames, int N, int H2
     const char* who = "nd_raw_poisson_gaussian_f32";
     ND_REQUIRE(frames && table && noisy && clean_out, ND_E_BADARG, "%s: null pointer", who);
     ND_REQUIRE(draw >= 0, ND_E_BADARG, "%s: draw index %d is negative", who, draw);
-    ND_REQUIRE(white > black && black >= 0.0f && white <= 65535.0f, ND_E_BADARG, "%s: need 0 <= black < white <= 65535", who);
+    if (int r = rw_check_levels(who, black, white)) return r;
     if (int r = rw_check_frames(who, frames, N, H2, W2, B, h, w)) return r;
     ND_REQUIRE(((uintptr_t)table & 7u) == 0 && ((uintptr_t)rng & 7u) == 0, ND_E_ALIGN, "%s: table and rng must be 8-byte aligned", who);
     const uintptr_t bits = (uintptr_t)noisy | (uintptr_t)clean_out | (uintptr_t)counts_out | (uintptr_t)normals_out | (uintptr_t)counts_in |
@@ -497,11 +507,7 @@ extern "C" int nd_raw_poisson_gaussian_f32(const uint16_t* frames, int N, int H2
     A.N = N;  A.H = H2 / 2;  A.W = W2 / 2;  A.h = h;  A.w = w;  A.black = black;  A.white = white;
     const uintptr_t out_bits = (uintptr_t)noisy | (uintptr_t)clean_out | (uintptr_t)counts_out | (uintptr_t)normals_out;
     const int V = rw_width(w, out_bits);
-    const size_t threads = (size_t)4 * h * w / V;
-    const dim3 grid((unsigned)((threads + RW_THREADS - 1) / RW_THREADS), (unsigned)B);
-    if (V == 4) hipLaunchKernelGGL(raw_pg_kernel<4>, grid, dim3(RW_THREADS), 0, (hipStream_t)stream, A);
-    else if (V == 2) hipLaunchKernelGGL(raw_pg_kernel<2>, grid, dim3(RW_THREADS), 0, (hipStream_t)stream, A);
-    else hipLaunchKernelGGL(raw_pg_kernel<1>, grid, dim3(RW_THREADS), 0, (hipStream_t)stream, A);
+    rw_dispatch(V, [&](auto v) { hipLaunchKernelGGL(raw_pg_kernel<v()>, rw_grid((size_t)4 * h * w / V, B), dim3(RW_THREADS), 0, (hipStream_t)stream, A); });
     return nd_launch_status(who);
 }
 
@@ -517,11 +523,7 @@ extern "C" int nd_raw_to_bayer_u16(const float* img, uint16_t* out, const int32_
     A.img = img;  A.out = out;  A.white = white;  A.h = h;  A.w = w;
     for (int c = 0; c < 4; ++c) A.bl[c] = bl[c];
     const int V = rw_width(w, (uintptr_t)out);
-    const size_t threads = (size_t)h * (w / V);
-    const dim3 grid((unsigned)((threads + RW_THREADS - 1) / RW_THREADS), (unsigned)B);
-    if (V == 4) hipLaunchKernelGGL(raw_bayer_kernel<4>, grid, dim3(RW_THREADS), 0, (hipStream_t)stream, A);
-    else if (V == 2) hipLaunchKernelGGL(raw_bayer_kernel<2>, grid, dim3(RW_THREADS), 0, (hipStream_t)stream, A);
-    else hipLaunchKernelGGL(raw_bayer_kernel<1>, grid, dim3(RW_THREADS), 0, (hipStream_t)stream, A);
+    rw_dispatch(V, [&](auto v) { hipLaunchKernelGGL(raw_bayer_kernel<v()>, rw_grid((size_t)h * (w / V), B), dim3(RW_THREADS), 0, (hipStream_t)stream, A); });
     return nd_launch_status(who);
 }
 
@@ -538,7 +540,7 @@ extern "C" int nd_raw_diffusion_batch_f32(const uint16_t* frames, int N, int H2,
                H2 / 2, W2 / 2);
     ND_REQUIRE(h > 0 && w > 0 && B > 0 && B <= 65535, ND_E_BADARG, "%s: h, w and B (<= 65535) must be positive", who);
     ND_REQUIRE(h <= H2 / 2 && w <= W2 / 2, ND_E_BADARG, "%s: the window %d x %d does not fit the packed frame %d x %d", who, h, w, H2 / 2, W2 / 2);
-    ND_REQUIRE(white > black && black >= 0.0f && white <= 65535.0f, ND_E_BADARG, "%s: need 0 <= black < white <= 65535", who);
+    if (int r = rw_check_levels(who, black, white)) return r;
     const uintptr_t out_bits = (uintptr_t)noise | (uintptr_t)noisy | (uintptr_t)clean | (uintptr_t)coord;
     ND_REQUIRE(((uintptr_t)frames & 3u) == 0 && (out_bits & 3u) == 0 && ((uintptr_t)table & 7u) == 0, ND_E_BADARG,
                "%s: frames and outputs must be 4-byte aligned, the table 8-byte", who);
@@ -546,10 +548,6 @@ extern "C" int nd_raw_diffusion_batch_f32(const uint16_t* frames, int N, int H2,
     A.frames = frames;  A.table = table;  A.noise = noise;  A.noisy = noisy;  A.clean = clean;  A.coord = coord;
     A.N = reads ? N : 0;  A.H = H2 / 2;  A.W = W2 / 2;  A.h = h;  A.w = w;  A.black = black;  A.white = white;
     const int V = rw_width(w, out_bits);
-    const size_t threads = (size_t)h * (w / V);
-    const dim3 grid((unsigned)((threads + RW_THREADS - 1) / RW_THREADS), (unsigned)B);
-    if (V == 4) hipLaunchKernelGGL(raw_diffusion_kernel<4>, grid, dim3(RW_THREADS), 0, (hipStream_t)stream, A);
-    else if (V == 2) hipLaunchKernelGGL(raw_diffusion_kernel<2>, grid, dim3(RW_THREADS), 0, (hipStream_t)stream, A);
-    else hipLaunchKernelGGL(raw_diffusion_kernel<1>, grid, dim3(RW_THREADS), 0, (hipStream_t)stream, A);
+    rw_dispatch(V, [&](auto v) { hipLaunchKernelGGL(raw_diffusion_kernel<v()>, rw_grid((size_t)h * (w / V), B), dim3(RW_THREADS), 0, (hipStream_t)stream, A); });
     return nd_launch_status(who);
 }

@@ -10,7 +10,8 @@ the even-aligned crop :120-130), the flip of ``Trainer.prepare`` (models/trainer
 - ``BatchBuilder(crop, patch, shading)``: ``build(noise, clean, xy, iso, ratio, crop_xy=, flip=, wb=, K=, seed=, first_sample=, draw=)`` ->
   ``(noisy, clean_out)``, fp32 NCHW ``(B, 4, crop, crop)``; ``random_params`` draws crops, the flip and the augmentation as the reference does;
   ``capture_inputs`` / ``update`` / ``launch`` split a call into its device parameter block, the host write of that block and the bare launch,
-  so the launch can sit in a captured training-step graph and replay with new parameters;
+  so the launch can sit in a captured training-step graph and replay with new parameters (the block and the scaffolding of these calls are
+  ``_batch.ParamBlock`` and ``_batch.BlockBuilder``, shared with ``raw`` and ``diffusion_data``); ``plane_ptrs`` hands a launch the planes;
 - ``philox_poisson(rate, seed, first_sample, draw)``: the counter-based Poisson draw alone;
 - ``sna_white_balance`` / ``sna_white_balance_from_draws`` / ``sna_gain``: the augmentation's host-side parameters (plain Python, not timed).
 
@@ -26,6 +27,7 @@ import numpy as np
 import torch
 
 from . import _lib as L
+from ._batch import BlockBuilder, ParamBlock, check_headroom, check_positive, need_gpu, per_sample, rng_key, write_rng
 from ._host import _stream
 
 WHITE_MINUS_BLACK = 15871            # 16383 - 512: the Sony sensor's white point minus its black level
@@ -34,6 +36,7 @@ HIGH_ISO = 1600                      # above it the high-ISO pair of dark-shadin
 TABLE_ISOS = (50, 64, 80, 100, 125, 160, 200, 250, 320, 400, 500, 640, 800, 1000, 1250, 1600, 2000, 2500, 3200, 4000, 5000, 6400, 8000, 10000,
               12800, 16000, 20000, 25600)
 _RNG_WORDS, _TABLE_WORDS, _SNA_WORDS = 8, 12, 8      # 32-bit words: the {seed, first_sample, draw} triple (padded), nd_denoise_sample, wb[4] + K
+_WHAT = "denoise_data runs on the HIP library"       # need_gpu's half of the "no CPU path" message
 
 
 # ----------------------------------------------------------------------------- host-side parameters of the augmentation
@@ -83,15 +86,6 @@ def sna_white_balance(B: int) -> torch.Tensor:
 
 # ----------------------------------------------------------------------------- device helpers
 
-def _need_gpu(*ts: torch.Tensor) -> torch.device:
-    dev = ts[0].device
-    if dev.type != "cuda":
-        raise L.HipError(f"denoise_data runs on the HIP library only; tensor is on {dev} and there is no CPU path")
-    if any(t.device != dev for t in ts):
-        raise ValueError("all tensors must be on one device")
-    return dev
-
-
 def _f32(t: torch.Tensor) -> torch.Tensor:
     return t.to(torch.float32).contiguous()
 
@@ -101,7 +95,7 @@ def philox_poisson(rate: torch.Tensor, seed: int = 0, first_sample: int = 0, dra
     (B, ...) on a GPU; element i of sample b is keyed by (seed, i, first_sample + b, draw), so a sample's counts do not depend on B."""
     if not isinstance(rate, torch.Tensor) or rate.dim() < 1 or rate.numel() == 0:
         raise ValueError("rate must be a non-empty (B, ...) tensor")
-    dev = _need_gpu(rate)
+    dev = need_gpu(rate, what=_WHAT)
     r = _f32(rate)
     out = torch.empty_like(r)
     B = r.shape[0]
@@ -142,35 +136,33 @@ class DarkShading:
         return self.blc_mean[int(iso)]
 
 
-class BatchInputs:
+def plane_ptrs(shading: Optional[DarkShading], device: torch.device, other: str = "frames"):
+    """([k_high, b_high, k_low, b_low] as pointers, H, W) of the planes on ``device``; four NULLs and 0, 0 for None."""
+    if shading is None:
+        return [None] * 4, 0, 0
+    if shading.device != device:
+        raise ValueError(f"the shading planes are on {shading.device}, the {other} on {device}")
+    return [shading.k_high.data_ptr(), shading.b_high.data_ptr(), shading.k_low.data_ptr(), shading.b_low.data_ptr()], shading.H, shading.W
+
+
+class BatchInputs(ParamBlock):
     """The device parameter block of one ``BatchBuilder.launch``: the {seed, first_sample, draw} triple, the per-sample table and the
     augmentation columns in ONE int32 buffer, written by ``BatchBuilder.update`` with one copy.  A captured launch reads it at replay."""
+    DTYPE, HEAD, PER_SAMPLE = np.int32, _RNG_WORDS, _TABLE_WORDS + _SNA_WORDS
 
     def __init__(self, B: int, device: torch.device):
-        self.B = int(B)
-        self.device = device
-        self.block = torch.zeros(_RNG_WORDS + self.B * (_TABLE_WORDS + _SNA_WORDS), dtype=torch.int32, device=device)
-        self.host = np.zeros(self.block.numel(), dtype=np.int32)
-        self.use_sna = False
-        self.use_rng = True
+        super().__init__(B, device, self.DTYPE, self.HEAD, self.PER_SAMPLE)
 
-    @property
-    def rng_ptr(self) -> int:
-        return self.block.data_ptr()
-
-    @property
-    def table_ptr(self) -> int:
-        return self.block.data_ptr() + 4 * _RNG_WORDS
-
-    @property
-    def sna_ptr(self) -> int:
-        return self.block.data_ptr() + 4 * (_RNG_WORDS + self.B * _TABLE_WORDS)
+    rng_ptr = property(lambda self: self.ptr(0))
+    table_ptr = property(lambda self: self.ptr(_RNG_WORDS))
+    sna_ptr = property(lambda self: self.ptr(_RNG_WORDS + self.B * _TABLE_WORDS))
 
 
-class BatchBuilder:
+class BatchBuilder(BlockBuilder):
     """Builds (noisy, clean) training batches of ``crop`` x ``crop`` from ``patch`` x ``patch`` generated patches.
 
     shading: a ``DarkShading`` (``--sub_darkshading``) or None.  The reference's hard-coded 512 * 2 shading window is ``patch`` here."""
+    Inputs = BatchInputs
 
     def __init__(self, crop: int, patch: int, shading: Optional[DarkShading] = None):
         crop, patch = int(crop), int(patch)
@@ -207,15 +199,13 @@ class BatchBuilder:
         crop_xy = np.asarray(crop_xy, dtype=np.int64).reshape(-1, 2)
         iso = np.asarray(iso, dtype=np.int64).reshape(-1)
         ratio = np.asarray(ratio, dtype=np.float64).reshape(-1)
-        flip = np.zeros(B, np.int64) if flip is None else np.broadcast_to(np.asarray(flip, dtype=np.int64).reshape(-1), (B,))
+        flip = per_sample(0 if flip is None else flip, B, np.int64)
         if not (len(xy) == len(crop_xy) == len(iso) == len(ratio) == B):
             raise ValueError(f"xy, crop_xy, iso and ratio must have B={B} rows")
         if (crop_xy % 2).any() or (crop_xy < 0).any() or (crop_xy > P - c).any():
             raise ValueError(f"crop offsets must be even and in [0, {P - c}]; got {crop_xy.tolist()}")
-        if not (ratio > 0).all() or not np.isfinite(ratio).all():
-            raise ValueError(f"ratio must be positive and finite; got {ratio.tolist()}")
-        if int(draw) < 0 or int(draw) >= 2 ** 31:
-            raise ValueError(f"draw must be in [0, 2**31); got {draw}")
+        check_positive(ratio, "ratio")
+        write_rng(host[:_RNG_WORDS], seed, first_sample, draw)
         blc = np.zeros(B)
         if self.shading is not None:
             if (xy < 0).any() or (xy[:, 0] > self.shading.W - P).any() or (xy[:, 1] > self.shading.H - P).any():
@@ -223,9 +213,6 @@ class BatchBuilder:
             blc = np.array([self.shading.black_level(i) for i in iso])
         if (np.abs(xy) >= 2 ** 31).any():
             raise ValueError("patch origin out of range")
-        rng = host[:_RNG_WORDS].view(np.int64)
-        rng[0] = np.array(int(seed) & 0xFFFFFFFFFFFFFFFF, dtype=np.uint64).view(np.int64)
-        rng[1], rng[2] = int(first_sample), int(draw)
         t = host[_RNG_WORDS:_RNG_WORDS + B * _TABLE_WORDS].reshape(B, _TABLE_WORDS)
         t[:, 0:2], t[:, 2:4], t[:, 4], t[:, 5] = xy, crop_xy, flip != 0, iso > HIGH_ISO
         tf = t.view(np.float32)
@@ -237,17 +224,15 @@ class BatchBuilder:
         wb = (wb.detach().cpu().numpy() if isinstance(wb, torch.Tensor) else np.asarray(wb)).astype(np.float32).reshape(-1, 4)
         if K is None:
             raise ValueError("wb needs K (sna_gain)")
-        K = np.broadcast_to(np.asarray(K, dtype=np.float64).reshape(-1), (B,))
+        K = per_sample(K, B)
         if len(wb) != B:
             raise ValueError(f"wb must be (B={B}, 4)")
         if not (wb >= 0).all():
             raise ValueError("white-balance gains must be non-negative")
         K32 = K.astype(np.float32)
-        if not (K32 > 0).all() or not np.isfinite(K32).all():
-            raise ValueError(f"the gain K must be positive and finite; got {K.tolist()}")
+        check_positive(K32, "the gain K", got=K)
         top = WHITE_MINUS_BLACK * wb.max(axis=1).astype(np.float64) / (ratio.astype(np.float32).astype(np.float64) * K32.astype(np.float64))
-        if (top >= 2.0 ** 24).any():
-            raise ValueError(f"15871 * max(wb) / (ratio * K) = {top.max():.4g} reaches 2**24: Poisson counts would not stay exact in fp32")
+        check_headroom(top, "15871 * max(wb) / (ratio * K)")
         s[:, 0:4], s[:, 4] = wb, K32
         return True
 
@@ -256,25 +241,13 @@ class BatchBuilder:
         """Validate one step's parameters on the host (no device is touched): ValueError for K <= 0, negative gains, odd or out-of-range crop
         offsets, a patch outside the shading planes, or 15871 max(wb) / (ratio K) >= 2**24.  Returns (the parameter block as the device will
         read it, whether the augmentation is on)."""
-        host = np.zeros(_RNG_WORDS + int(B) * (_TABLE_WORDS + _SNA_WORDS), dtype=np.int32)
-        return host, self._host_block(host, int(B), xy, iso, ratio, crop_xy, flip, wb, K, seed, first_sample, draw)
-
-    def capture_inputs(self, B: int, device) -> BatchInputs:
-        """A persistent device parameter block for batches of B: ``update`` writes it, ``launch`` reads it (also from inside a graph)."""
-        device = torch.device(device)
-        if device.type != "cuda":
-            raise L.HipError(f"the batch is built on a GPU; got device {device} and there is no CPU path")
-        if int(B) < 1:
-            raise ValueError("B must be positive")
-        return BatchInputs(B, device)
+        return self._check(B, xy, iso, ratio, crop_xy, flip, wb, K, seed, first_sample, draw)
 
     def update(self, inputs: BatchInputs, xy, iso, ratio, crop_xy, flip=None, wb=None, K=None, seed: int = 0, first_sample: int = 0,
                draw: int = 0) -> BatchInputs:
         """Write one step's parameters into the device block: host validation, then ONE host-to-device copy on the current stream.  A captured
         ``launch`` keeps the choice between augmentation and none that was in force at capture: switch it off per sample with zero gains."""
-        inputs.use_sna = self._host_block(inputs.host, inputs.B, xy, iso, ratio, crop_xy, flip, wb, K, seed, first_sample, draw)
-        inputs.block.copy_(torch.from_numpy(inputs.host))
-        return inputs
+        return self._update(inputs, xy, iso, ratio, crop_xy, flip, wb, K, seed, first_sample, draw)
 
     # ------------------------------------------------------------------ the launch
     def _check_images(self, noise: torch.Tensor, clean: torch.Tensor) -> int:
@@ -291,26 +264,19 @@ class BatchBuilder:
         """The one kernel launch, on the current stream, reading ``inputs``: no allocation when ``noisy`` and ``clean_out`` are given, no
         synchronisation, capturable.  noise, clean: fp32 contiguous (B, 4, patch, patch)."""
         B = self._check_images(noise, clean)
-        dev = _need_gpu(noise, clean)
+        dev = need_gpu(noise, clean, what=_WHAT)
         if B != inputs.B or dev != inputs.device:
             raise ValueError(f"the parameter block is for B={inputs.B} on {inputs.device}; got B={B} on {dev}")
         if noise.dtype != torch.float32 or clean.dtype != torch.float32 or not noise.is_contiguous() or not clean.is_contiguous():
             raise ValueError("launch takes fp32 contiguous tensors (the builder's call converts)")
         shape = (B, 4, self.crop, self.crop)
-        noisy = torch.empty(shape, dtype=torch.float32, device=dev) if noisy is None else noisy
-        clean_out = torch.empty(shape, dtype=torch.float32, device=dev) if clean_out is None else clean_out
-        for name, t in (("noisy", noisy), ("clean_out", clean_out), ("counts", counts), ("counts_out", counts_out)):
-            if t is not None and (tuple(t.shape) != shape or t.dtype != torch.float32 or not t.is_contiguous() or t.device != dev):
-                raise ValueError(f"{name} must be fp32 contiguous {shape} on {dev}")
-        sh = self.shading
-        if sh is not None and sh.device != dev:
-            raise ValueError(f"the shading planes are on {sh.device}, the batch on {dev}")
-        maps = [None] * 4 if sh is None else [sh.k_high.data_ptr(), sh.b_high.data_ptr(), sh.k_low.data_ptr(), sh.b_low.data_ptr()]
-        host = inputs.host[:_RNG_WORDS].view(np.int64)
-        L.call("nd_denoise_batch_f32", noise.data_ptr(), clean.data_ptr(), *maps, 0 if sh is None else sh.H, 0 if sh is None else sh.W,
-               inputs.table_ptr, inputs.sna_ptr if inputs.use_sna else None, inputs.rng_ptr if inputs.use_rng else None,
-               int(host[0]) & 0xFFFFFFFFFFFFFFFF, int(host[1]), int(host[2]), L.ptr(counts), L.ptr(counts_out), noisy.data_ptr(),
-               clean_out.data_ptr(), B, self.patch, self.crop, self.crop, _stream(dev))
+        noisy, clean_out = self._output("noisy", noisy, shape, dev), self._output("clean_out", clean_out, shape, dev)
+        self._output("counts", counts, shape, dev, make=False)
+        self._output("counts_out", counts_out, shape, dev, make=False)
+        maps, mh, mw = plane_ptrs(self.shading, dev, "batch")
+        L.call("nd_denoise_batch_f32", noise.data_ptr(), clean.data_ptr(), *maps, mh, mw, inputs.table_ptr,
+               inputs.sna_ptr if inputs.use_sna else None, inputs.rng_ptr if inputs.use_rng else None, *rng_key(inputs.host[:_RNG_WORDS]),
+               L.ptr(counts), L.ptr(counts_out), noisy.data_ptr(), clean_out.data_ptr(), B, self.patch, self.crop, self.crop, _stream(dev))
         return noisy, clean_out
 
     def __call__(self, noise: torch.Tensor, clean: torch.Tensor, xy, iso, ratio, crop_xy, flip=None, wb=None, K=None, seed: int = 0,
@@ -323,12 +289,9 @@ class BatchBuilder:
         host, use_sna = self.check(B, xy, iso, ratio, crop_xy, flip, wb, K, seed, first_sample, draw)
         if counts is not None and (not isinstance(counts, torch.Tensor) or tuple(counts.shape) != (B, 4, self.crop, self.crop)):
             raise ValueError(f"counts must be a (B, 4, {self.crop}, {self.crop}) tensor")
-        dev = _need_gpu(noise, clean) if counts is None else _need_gpu(noise, clean, counts)
+        dev = need_gpu(noise, clean, what=_WHAT) if counts is None else need_gpu(noise, clean, counts, what=_WHAT)
         counts = None if counts is None else _f32(counts)
-        inputs = BatchInputs(B, dev)
-        inputs.use_rng = False                              # an eager call passes the key as arguments; a captured one reads the device triple
-        inputs.host[:], inputs.use_sna = host, use_sna
-        inputs.block.copy_(torch.from_numpy(inputs.host))
+        inputs = self._eager_inputs(B, host, dev, use_rng=False, use_sna=use_sna)
         used = torch.empty(B, 4, self.crop, self.crop, dtype=torch.float32, device=dev) if return_counts else None
         noisy, clean_out = self.launch(inputs, _f32(noise), _f32(clean), counts=counts, counts_out=used)
         return (noisy, clean_out, used) if return_counts else (noisy, clean_out)

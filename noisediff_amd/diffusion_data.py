@@ -12,7 +12,8 @@ exposure and builds the whole grid again (``NoiseImageGenerationDataset.__getite
   (coordinates only, ``clean_img`` zeros);
 - ``balanced_sample_list(pairs)``: the resampling of ``SonyTrainDataset.__init__`` (plain Python).
 
-Both builders have ``check`` / ``capture_inputs`` / ``update`` / ``launch`` / ``__call__`` as ``raw.RealBatchBuilder`` has them.  The
+Both builders have ``check`` / ``capture_inputs`` / ``update`` / ``launch`` / ``__call__`` as ``raw.RealBatchBuilder`` has them (they
+derive from ``raw._WindowBuilder``, a ``_batch.BlockBuilder`` over a ``raw.RawInputs`` block).  The
 ``(iso, ratio) -> iso_ratio_idx`` table belongs to the checkpoint and stays with the caller: the builders take indices.  The numerical contract
 is in DESIGN.md section 13: every output equals the reference's bit for bit.  CPU tensors raise ``HipError``; there is no fallback.
 """
@@ -25,8 +26,9 @@ import torch
 
 from . import _lib as L
 from . import io
+from ._batch import check_frames, cuda_device
 from ._host import _stream
-from .raw import BLACK, WHITE, ROW, RawInputs, _RNG_BYTES, _WindowBuilder, _default_device, frame_shape, frames_on_device
+from .raw import BLACK, WHITE, RawInputs, _WindowBuilder, _default_device, frame_shape, frames_on_device
 
 TRAIN_KEYS = ("noise", "noisy_img", "clean_img", "coord")        # the reference's names, in the entry point's argument order
 _CHANNELS = {"noise": 4, "noisy_img": 4, "clean_img": 4, "coord": 2, "position": 2}
@@ -52,32 +54,13 @@ class _DiffusionLaunch(_WindowBuilder):
     """The launch the two builders share: named outputs, the ones not asked for passed as NULL."""
 
     def _outputs(self, inputs: RawInputs, dev: torch.device, names: Sequence[str], out: Optional[Dict[str, torch.Tensor]]) -> Dict[str, torch.Tensor]:
-        res = {}
-        for name in names:
-            shape = (inputs.B, _CHANNELS[name], self.crop, self.crop)
-            t = None if out is None else out.get(name)
-            if t is None:
-                t = torch.empty(shape, dtype=torch.float32, device=dev)
-            elif tuple(t.shape) != shape or t.dtype != torch.float32 or not t.is_contiguous() or t.device != dev:
-                raise ValueError(f"{name} must be fp32 contiguous {shape} on {dev}")
-            res[name] = t
-        return res
+        return {name: self._output(name, None if out is None else out.get(name), (inputs.B, _CHANNELS[name], self.crop, self.crop), dev)
+                for name in names}
 
     def _launch(self, inputs: RawInputs, frames: Optional[torch.Tensor], shape, ptrs: Sequence[Optional[int]]) -> None:
         N, H2, W2 = shape
         L.call("nd_raw_diffusion_batch_f32", L.ptr(frames), N, H2, W2, inputs.table_ptr, self.black, self.white, *ptrs, inputs.B, self.crop,
                self.crop, _stream(inputs.device))
-
-    def _device_frames(self, inputs: RawInputs, frames) -> torch.Tensor:
-        f, _, _ = self._frames_and_outputs(inputs, frames, {})
-        return f
-
-    @staticmethod
-    def _fresh_inputs(host: np.ndarray, B: int, dev: torch.device) -> RawInputs:
-        inputs = RawInputs(B, dev)
-        inputs.host[:] = host
-        inputs.block.copy_(torch.from_numpy(inputs.host))
-        return inputs
 
 
 class DiffusionBatchBuilder(_DiffusionLaunch):
@@ -107,23 +90,18 @@ class DiffusionBatchBuilder(_DiffusionLaunch):
         long = np.asarray(long, dtype=np.int64).reshape(-1)
         if len(long) != B:
             raise ValueError(f"long must have B={B} entries")
-        if (long < 0).any() or (long >= N).any():
-            raise ValueError(f"frame indices must be in [0, {N}); got {long.tolist()}")
+        check_frames(long, N)
         rows["frame_clean"], rows["ratio"] = long, self._ratio(ratio, B)
 
     def check(self, B: int, shape, short, long, xy, ratio) -> np.ndarray:
         """Validate one step's parameters on the host (no device is touched): ValueError for odd frame sides or a packed side below 2, a
         window outside the frame, a frame index outside [0, N), ratio <= 0 or not finite.  shape: the frames' (N, H2, W2).  Returns the
         parameter block as the device will read it."""
-        host = np.zeros(_RNG_BYTES + int(B) * ROW.itemsize, dtype=np.uint8)
-        self._host_block(host, int(B), shape, short, long, xy, ratio)
-        return host
+        return self._check(B, shape, short, long, xy, ratio)[0]
 
     def update(self, inputs: RawInputs, shape, short, long, xy, ratio) -> RawInputs:
         """Write one step's parameters into the device block: host validation, then ONE host-to-device copy on the current stream."""
-        self._host_block(inputs.host, inputs.B, shape, short, long, xy, ratio)
-        inputs.block.copy_(torch.from_numpy(inputs.host))
-        return inputs
+        return self._update(inputs, shape, short, long, xy, ratio)
 
     def launch(self, inputs: RawInputs, frames: torch.Tensor, out: Optional[Dict[str, torch.Tensor]] = None,
                want: Sequence[str] = ("noise", "clean_img", "coord")) -> Dict[str, torch.Tensor]:
@@ -146,7 +124,7 @@ class DiffusionBatchBuilder(_DiffusionLaunch):
         B = len(np.asarray(short).reshape(-1))
         host = self.check(B, tuple(frames.shape), short, long, xy, ratio)
         f = frames_on_device(frames)
-        batch = self.launch(self._fresh_inputs(host, B, f.device), f, want=want)
+        batch = self.launch(self._eager_inputs(B, host, f.device), f, want=want)
         if iso_ratio_idx is not None:
             batch["iso_ratio_idx"] = _index_tensor(iso_ratio_idx, B, f.device)
         return batch
@@ -200,15 +178,11 @@ class GenerationBatchBuilder(_DiffusionLaunch):
         """Validate one batch's parameters on the host (no device is touched): ValueError for odd frame sides or a packed side below 2, a patch
         outside the frame, a frame index outside [0, N).  shape: the frames' (N, H2, W2), or with dark_frame the packed (H, W), where
         ``frame`` is ignored.  Returns the parameter block as the device will read it."""
-        host = np.zeros(_RNG_BYTES + int(B) * ROW.itemsize, dtype=np.uint8)
-        self._host_block(host, int(B), shape, frame, xy)
-        return host
+        return self._check(B, shape, frame, xy)[0]
 
     def update(self, inputs: RawInputs, shape, frame, xy) -> RawInputs:
         """Write one batch's parameters into the device block: host validation, then ONE host-to-device copy on the current stream."""
-        self._host_block(inputs.host, inputs.B, shape, frame, xy)
-        inputs.block.copy_(torch.from_numpy(inputs.host))
-        return inputs
+        return self._update(inputs, shape, frame, xy)
 
     def launch(self, inputs: RawInputs, frames, out: Optional[Dict[str, torch.Tensor]] = None) -> Dict[str, torch.Tensor]:
         """The one kernel launch, on the current stream, reading ``inputs``: no allocation when ``out`` holds clean_img and position, no
@@ -234,16 +208,14 @@ class GenerationBatchBuilder(_DiffusionLaunch):
         B = len(coords)
         if self.dark_frame:
             host = self.check(B, frames, None, xy)
-            dev = _default_device() if device is None else torch.device(device)
-            if dev.type != "cuda":
-                raise L.HipError(f"the batch is built on a GPU; got device {dev} and there is no CPU path")
-            batch: Dict[str, object] = dict(self.launch(self._fresh_inputs(host, B, dev), frames))
+            dev = _default_device() if device is None else cuda_device(device)
+            batch: Dict[str, object] = dict(self.launch(self._eager_inputs(B, host, dev), frames))
             batch["clean_img"] = torch.zeros(B, 4, self.crop, self.crop, dtype=torch.float32, device=dev)
         else:
             host = self.check(B, tuple(frames.shape), frame, xy)
             f = frames_on_device(frames)
             dev = f.device
-            batch = dict(self.launch(self._fresh_inputs(host, B, dev), f))
+            batch = dict(self.launch(self._eager_inputs(B, host, dev), f))
         batch["iso_ratio_idx"] = _index_tensor(iso_ratio_idx, B, dev)
         batch["image_coord"] = [io.image_coord(x, y) for x, y in coords.tolist()]
         return batch

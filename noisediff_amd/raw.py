@@ -12,7 +12,7 @@ as **uint16** and each of these is one launch of ``csrc/raw.hip``:
 - ``to_bayer(img, black_level_per_channel, white=16383)``: (B, 4, h, w) fp32 -> (B, 2h, 2w) uint16, the write half of ``postprocess_bayer``;
 - ``RealBatchBuilder(crop, shading=None)`` and ``PoissonGaussianBatchBuilder(crop)``: a training batch ``(noisy, clean)`` of crop windows
   from resident frames, with ``check`` / ``capture_inputs`` / ``update`` / ``launch`` / ``__call__`` and ``random_params`` as
-  ``denoise_data.BatchBuilder`` has them;
+  ``denoise_data.BatchBuilder`` has them (one ``_batch.BlockBuilder`` under all of them; the parameter block is ``RawInputs``);
 - ``poisson_gaussian_params(K, VAR)``: the per-sample gain and variance of ``apply_noise`` (plain Python, not timed).
 
 Frames are numpy uint16 arrays (copied to the device as uint16) or device tensors of a 16-bit integer dtype (torch's ``uint16`` support is
@@ -29,27 +29,20 @@ import numpy as np
 import torch
 
 from . import _lib as L
+from ._batch import BlockBuilder, ParamBlock, check_frames, check_headroom, check_positive, need_gpu, per_sample, rng_key, write_rng
 from ._host import _stream
-from .denoise_data import HIGH_ISO, DarkShading
+from .denoise_data import HIGH_ISO, DarkShading, plane_ptrs as _plane_ptrs
 
 BLACK, WHITE = 512, 16383            # the Sony sensor's black level and white point
 _RNG_BYTES = 32                      # the {seed, first_sample, draw} triple as int64, padded
 ROW = np.dtype([("frame", "<i4"), ("frame_clean", "<i4"), ("x0", "<i4"), ("y0", "<i4"), ("flip", "<i4"), ("branch", "<i4"), ("iso", "<f4"),
                 ("ratio", "<f4"), ("blc", "<f4"), ("reserved", "<i4"), ("k", "<f8"), ("sd", "<f8"), ("ratio64", "<f8")])      # nd_raw_sample
 assert ROW.itemsize == C.sizeof(L.RawSample) == 64
+_WHAT = "raw frames are processed on the HIP library"              # need_gpu's half of the "no CPU path" message
 _U16 = tuple(t for t in (torch.int16, getattr(torch, "uint16", None)) if t is not None)
 
 
 # ----------------------------------------------------------------------------- frames
-
-def _need_gpu(*ts: torch.Tensor) -> torch.device:
-    dev = ts[0].device
-    if dev.type != "cuda":
-        raise L.HipError(f"raw frames are processed on the HIP library only; tensor is on {dev} and there is no CPU path")
-    if any(t.device != dev for t in ts):
-        raise ValueError("all tensors must be on one device")
-    return dev
-
 
 def _default_device() -> torch.device:
     if not torch.cuda.is_available():
@@ -82,16 +75,8 @@ def frames_on_device(frames, device=None) -> torch.Tensor:
     shape = frame_shape(frames.shape)
     if frames.dtype not in _U16:
         raise TypeError(f"raw frames are a 16-bit integer tensor (uint16, or its storage as int16); got {frames.dtype}")
-    _need_gpu(frames)
+    need_gpu(frames, what=_WHAT)
     return frames.contiguous().reshape(shape)
-
-
-def _plane_ptrs(shading: Optional[DarkShading], dev: torch.device):
-    if shading is None:
-        return [None] * 4, 0, 0
-    if shading.device != dev:
-        raise ValueError(f"the shading planes are on {shading.device}, the frames on {dev}")
-    return [shading.k_high.data_ptr(), shading.b_high.data_ptr(), shading.k_low.data_ptr(), shading.b_low.data_ptr()], shading.H, shading.W
 
 
 def _table(dev: torch.device, rows: np.ndarray) -> torch.Tensor:
@@ -137,7 +122,7 @@ def load_pair(short, long, iso: int, ratio: float, shading: Optional[DarkShading
     g = frames_on_device(long, s.device)
     if s.shape[0] != 1 or g.shape != s.shape:
         raise ValueError(f"short and long must be one frame each, of one shape; got {tuple(s.shape)} and {tuple(g.shape)}")
-    _need_gpu(s, g)
+    need_gpu(s, g, what=_WHAT)
     _, H2, W2 = s.shape
     h, w = H2 // 2, W2 // 2
     if shading is not None and (shading.H < h or shading.W < w):
@@ -164,7 +149,7 @@ def to_bayer(img: torch.Tensor, black_level_per_channel: Sequence[int], white: i
     bl = [int(b) for b in black_level_per_channel]
     if len(bl) != 4 or not all(0 <= b <= int(white) for b in bl) or not 0 < int(white) <= 65535:
         raise ValueError(f"need four black levels in [0, white] and white in (0, 65535]; got {bl}, white={white}")
-    dev = _need_gpu(img)
+    dev = need_gpu(img, what=_WHAT)
     x = img.to(torch.float32).contiguous()
     B, _, h, w = x.shape
     if out is None:
@@ -193,28 +178,21 @@ def poisson_gaussian_params(K: float, VAR: float) -> Tuple[float, float]:
     return one(K), one(VAR)
 
 
-class RawInputs:
+class RawInputs(ParamBlock):
     """The device parameter block of one builder launch: the {seed, first_sample, draw} triple and the per-sample table (nd_raw_sample rows) in
     ONE byte buffer, written by ``update`` with one copy.  A captured launch reads it at replay."""
+    DTYPE, HEAD, PER_SAMPLE = np.uint8, _RNG_BYTES, ROW.itemsize
 
     def __init__(self, B: int, device: torch.device):
-        self.B = int(B)
-        self.device = device
-        self.block = torch.zeros(_RNG_BYTES + self.B * ROW.itemsize, dtype=torch.uint8, device=device)
-        self.host = np.zeros(self.block.numel(), dtype=np.uint8)
-        self.use_rng = True
+        super().__init__(B, device, self.DTYPE, self.HEAD, self.PER_SAMPLE)
 
-    @property
-    def rng_ptr(self) -> int:
-        return self.block.data_ptr()
-
-    @property
-    def table_ptr(self) -> int:
-        return self.block.data_ptr() + _RNG_BYTES
+    rng_ptr = property(lambda self: self.ptr(0))
+    table_ptr = property(lambda self: self.ptr(_RNG_BYTES))
 
 
-class _WindowBuilder:
-    """What the two builders share: crop windows of resident frames, one table row per sample."""
+class _WindowBuilder(BlockBuilder):
+    """What the builders of crop windows share: resident frames, one table row per sample."""
+    Inputs = RawInputs
 
     def __init__(self, crop: int, black: float = BLACK, white: float = WHITE):
         crop = int(crop)
@@ -246,11 +224,10 @@ class _WindowBuilder:
             raise ValueError(f"the crop {c} does not fit the packed frame {H2 // 2} x {W2 // 2}")
         frame = np.asarray(frame, dtype=np.int64).reshape(-1)
         xy = np.asarray(xy, dtype=np.int64).reshape(-1, 2)
-        flip = np.zeros(B, np.int64) if flip is None else np.broadcast_to(np.asarray(flip, dtype=np.int64).reshape(-1), (B,))
+        flip = per_sample(0 if flip is None else flip, B, np.int64)
         if not (len(frame) == len(xy) == B):
             raise ValueError(f"frame indices and xy must have B={B} rows")
-        if (frame < 0).any() or (frame >= N).any():
-            raise ValueError(f"frame indices must be in [0, {N}); got {frame.tolist()}")
+        check_frames(frame, N)
         if (xy < 0).any() or (xy[:, 0] > W2 // 2 - c).any() or (xy[:, 1] > H2 // 2 - c).any():
             raise ValueError(f"a {c} x {c} window at {xy.tolist()} leaves the packed frame {H2 // 2} x {W2 // 2}")
         rows = host[_RNG_BYTES:].view(ROW)
@@ -260,32 +237,17 @@ class _WindowBuilder:
 
     @staticmethod
     def _ratio(ratio, B: int) -> np.ndarray:
-        ratio = np.broadcast_to(np.asarray(ratio, dtype=np.float64).reshape(-1), (B,))
-        if not (ratio > 0).all() or not np.isfinite(ratio).all():
-            raise ValueError(f"ratio must be positive and finite; got {ratio.tolist()}")
+        ratio = per_sample(ratio, B)
+        check_positive(ratio, "ratio")
         return ratio
 
-    def capture_inputs(self, B: int, device) -> RawInputs:
-        """A persistent device parameter block for batches of B: ``update`` writes it, ``launch`` reads it (also from inside a graph)."""
-        device = torch.device(device)
-        if device.type != "cuda":
-            raise L.HipError(f"the batch is built on a GPU; got device {device} and there is no CPU path")
-        if int(B) < 1:
-            raise ValueError("B must be positive")
-        return RawInputs(B, device)
-
-    def _frames_and_outputs(self, inputs: RawInputs, frames, shape_of: Dict[str, Optional[torch.Tensor]]):
+    def _device_frames(self, inputs: RawInputs, frames) -> torch.Tensor:
         if not isinstance(frames, torch.Tensor):
             raise TypeError("launch takes the frames as a device tensor (frames_on_device copies a numpy array once)")
         f = frames_on_device(frames)
-        dev = f.device
-        if dev != inputs.device:
-            raise ValueError(f"the parameter block is on {inputs.device}, the frames on {dev}")
-        shape = (inputs.B, 4, self.crop, self.crop)
-        for name, t in shape_of.items():
-            if t is not None and (tuple(t.shape) != shape or t.dtype != torch.float32 or not t.is_contiguous() or t.device != dev):
-                raise ValueError(f"{name} must be fp32 contiguous {shape} on {dev}")
-        return f, dev, shape
+        if f.device != inputs.device:
+            raise ValueError(f"the parameter block is on {inputs.device}, the frames on {f.device}")
+        return f
 
 
 class RealBatchBuilder(_WindowBuilder):
@@ -302,13 +264,10 @@ class RealBatchBuilder(_WindowBuilder):
 
     def _host_block(self, host: np.ndarray, B: int, shape, short, long, xy, iso, ratio, flip) -> None:
         rows = self._rows(host, B, shape, short, xy, flip)
-        N = frame_shape(shape)[0]
-        long = np.asarray(long, dtype=np.int64).reshape(-1)
-        iso = np.asarray(iso, dtype=np.int64).reshape(-1)
+        long, iso = (np.asarray(v, dtype=np.int64).reshape(-1) for v in (long, iso))
         if not (len(long) == len(iso) == B):
             raise ValueError(f"long and iso must have B={B} entries")
-        if (long < 0).any() or (long >= N).any():
-            raise ValueError(f"frame indices must be in [0, {N}); got {long.tolist()}")
+        check_frames(long, frame_shape(shape)[0])
         sh = self.shading
         if sh is not None:
             if (rows["x0"] > sh.W - self.crop).any() or (rows["y0"] > sh.H - self.crop).any():
@@ -319,23 +278,19 @@ class RealBatchBuilder(_WindowBuilder):
     def check(self, B: int, shape, short, long, xy, iso, ratio, flip=None) -> np.ndarray:
         """Validate one step's parameters on the host (no device is touched): ValueError for odd frame sides, a window outside the frame or
         the planes, a frame index >= N, ratio <= 0.  shape: the frames' (N, H2, W2).  Returns the parameter block as the device will read it."""
-        host = np.zeros(_RNG_BYTES + int(B) * ROW.itemsize, dtype=np.uint8)
-        self._host_block(host, int(B), shape, short, long, xy, iso, ratio, flip)
-        return host
+        return self._check(B, shape, short, long, xy, iso, ratio, flip)[0]
 
     def update(self, inputs: RawInputs, shape, short, long, xy, iso, ratio, flip=None) -> RawInputs:
         """Write one step's parameters into the device block: host validation, then ONE host-to-device copy on the current stream."""
-        self._host_block(inputs.host, inputs.B, shape, short, long, xy, iso, ratio, flip)
-        inputs.block.copy_(torch.from_numpy(inputs.host))
-        return inputs
+        return self._update(inputs, shape, short, long, xy, iso, ratio, flip)
 
     def launch(self, inputs: RawInputs, frames: torch.Tensor, noisy: Optional[torch.Tensor] = None,
                clean_out: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
         """The one kernel launch, on the current stream, reading ``inputs``: no allocation when ``noisy`` and ``clean_out`` are given, no
         synchronisation, capturable.  frames: (N, H2, W2) 16-bit integers on the device."""
-        f, dev, shape = self._frames_and_outputs(inputs, frames, {"noisy": noisy, "clean_out": clean_out})
-        noisy = torch.empty(shape, dtype=torch.float32, device=dev) if noisy is None else noisy
-        clean_out = torch.empty(shape, dtype=torch.float32, device=dev) if clean_out is None else clean_out
+        f = self._device_frames(inputs, frames)
+        dev, shape = f.device, (inputs.B, 4, self.crop, self.crop)
+        noisy, clean_out = self._output("noisy", noisy, shape, dev), self._output("clean_out", clean_out, shape, dev)
         maps, mh, mw = _plane_ptrs(self.shading, dev)
         N, H2, W2 = f.shape
         L.call("nd_raw_pack_u16_f32", f.data_ptr(), N, H2, W2, *maps, mh, mw, inputs.table_ptr, L.RAW_TRAIN_REAL, 0, self.black, self.white,
@@ -348,10 +303,7 @@ class RealBatchBuilder(_WindowBuilder):
         B = len(np.asarray(short).reshape(-1))
         host = self.check(B, tuple(frames.shape), short, long, xy, iso, ratio, flip)
         f = frames_on_device(frames)
-        inputs = RawInputs(B, f.device)
-        inputs.host[:] = host
-        inputs.block.copy_(torch.from_numpy(inputs.host))
-        return self.launch(inputs, f)
+        return self.launch(self._eager_inputs(B, host, f.device), f)
 
 
 class PoissonGaussianBatchBuilder(_WindowBuilder):
@@ -361,50 +313,37 @@ class PoissonGaussianBatchBuilder(_WindowBuilder):
 
     def _host_block(self, host: np.ndarray, B: int, shape, frame, xy, ratio, k, var, flip, seed: int, first_sample: int, draw: int) -> None:
         rows = self._rows(host, B, shape, frame, xy, flip)
-        ratio = self._ratio(ratio, B)
-        k = np.broadcast_to(np.asarray(k, dtype=np.float64).reshape(-1), (B,))
-        var = np.broadcast_to(np.asarray(var, dtype=np.float64).reshape(-1), (B,))
-        if not (k > 0).all() or not np.isfinite(k).all():
-            raise ValueError(f"the gain k must be positive and finite; got {k.tolist()}")
+        ratio, k, var = self._ratio(ratio, B), per_sample(k, B), per_sample(var, B)
+        check_positive(k, "the gain k")
         if not (var >= 0).all() or not np.isfinite(var).all():
             raise ValueError(f"the variance must be non-negative and finite; got {var.tolist()}")
-        if int(draw) < 0 or int(draw) >= 2 ** 31:
-            raise ValueError(f"draw must be in [0, 2**31); got {draw}")
-        top = (self.white - self.black) / (ratio * k)
-        if (top >= 2.0 ** 24).any():
-            raise ValueError(f"(white - black) / (ratio * k) = {top.max():.4g} reaches 2**24: Poisson counts would not stay exact in fp32")
+        write_rng(host[:_RNG_BYTES], seed, first_sample, draw)
+        check_headroom((self.white - self.black) / (ratio * k), "(white - black) / (ratio * k)")
         rows["ratio"], rows["k"], rows["sd"], rows["ratio64"] = ratio, k, np.sqrt(var), ratio
-        rng = host[:_RNG_BYTES].view(np.int64)
-        rng[0] = np.array(int(seed) & 0xFFFFFFFFFFFFFFFF, dtype=np.uint64).view(np.int64)
-        rng[1], rng[2] = int(first_sample), int(draw)
 
     def check(self, B: int, shape, frame, xy, ratio, k, var, flip=None, seed: int = 0, first_sample: int = 0, draw: int = 0) -> np.ndarray:
         """Validate one step's parameters on the host (no device is touched): ValueError for odd frame sides, a window outside the frame, a
         frame index >= N, k <= 0, var < 0, ratio <= 0 or (white - black) / (ratio k) >= 2**24.  Returns the parameter block."""
-        host = np.zeros(_RNG_BYTES + int(B) * ROW.itemsize, dtype=np.uint8)
-        self._host_block(host, int(B), shape, frame, xy, ratio, k, var, flip, seed, first_sample, draw)
-        return host
+        return self._check(B, shape, frame, xy, ratio, k, var, flip, seed, first_sample, draw)[0]
 
     def update(self, inputs: RawInputs, shape, frame, xy, ratio, k, var, flip=None, seed: int = 0, first_sample: int = 0,
                draw: int = 0) -> RawInputs:
         """Write one step's parameters into the device block: host validation, then ONE host-to-device copy on the current stream."""
-        self._host_block(inputs.host, inputs.B, shape, frame, xy, ratio, k, var, flip, seed, first_sample, draw)
-        inputs.block.copy_(torch.from_numpy(inputs.host))
-        return inputs
+        return self._update(inputs, shape, frame, xy, ratio, k, var, flip, seed, first_sample, draw)
 
     def launch(self, inputs: RawInputs, frames: torch.Tensor, noisy: Optional[torch.Tensor] = None, clean_out: Optional[torch.Tensor] = None,
                counts: Optional[torch.Tensor] = None, normals: Optional[torch.Tensor] = None, counts_out: Optional[torch.Tensor] = None,
                normals_out: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
         """The one kernel launch, on the current stream, reading ``inputs``: no allocation when ``noisy`` and ``clean_out`` are given, no
         synchronisation, capturable.  counts / normals replace the draws; counts_out / normals_out receive what was used."""
-        f, dev, shape = self._frames_and_outputs(inputs, frames, {"noisy": noisy, "clean_out": clean_out, "counts": counts, "normals": normals,
-                                                                  "counts_out": counts_out, "normals_out": normals_out})
-        noisy = torch.empty(shape, dtype=torch.float32, device=dev) if noisy is None else noisy
-        clean_out = torch.empty(shape, dtype=torch.float32, device=dev) if clean_out is None else clean_out
+        f = self._device_frames(inputs, frames)
+        dev, shape = f.device, (inputs.B, 4, self.crop, self.crop)
+        noisy, clean_out = self._output("noisy", noisy, shape, dev), self._output("clean_out", clean_out, shape, dev)
+        for name, t in (("counts", counts), ("normals", normals), ("counts_out", counts_out), ("normals_out", normals_out)):
+            self._output(name, t, shape, dev, make=False)
         N, H2, W2 = f.shape
-        key = inputs.host[:_RNG_BYTES].view(np.int64)
         L.call("nd_raw_poisson_gaussian_f32", f.data_ptr(), N, H2, W2, inputs.table_ptr, inputs.rng_ptr if inputs.use_rng else None,
-               int(key[0]) & 0xFFFFFFFFFFFFFFFF, int(key[1]), int(key[2]), L.ptr(counts), L.ptr(normals), L.ptr(counts_out), L.ptr(normals_out),
+               *rng_key(inputs.host[:_RNG_BYTES]), L.ptr(counts), L.ptr(normals), L.ptr(counts_out), L.ptr(normals_out),
                self.black, self.white, noisy.data_ptr(), clean_out.data_ptr(), inputs.B, self.crop, self.crop, _stream(dev))
         return noisy, clean_out
 
@@ -417,10 +356,7 @@ class PoissonGaussianBatchBuilder(_WindowBuilder):
         host = self.check(B, tuple(frames.shape), frame, xy, ratio, k, var, flip, seed, first_sample, draw)
         f = frames_on_device(frames)
         dev = f.device
-        inputs = RawInputs(B, dev)
-        inputs.use_rng = False                              # an eager call passes the key as arguments; a captured one reads the device triple
-        inputs.host[:] = host
-        inputs.block.copy_(torch.from_numpy(inputs.host))
+        inputs = self._eager_inputs(B, host, dev, use_rng=False)
         given = [None if t is None else t.to(torch.float32).contiguous() for t in (counts, normals)]
         used = [torch.empty(B, 4, self.crop, self.crop, dtype=torch.float32, device=dev) for _ in range(2)] if return_draws else [None, None]
         noisy, clean = self.launch(inputs, f, counts=given[0], normals=given[1], counts_out=used[0], normals_out=used[1])
