@@ -344,6 +344,41 @@ int nd_illum_scale_f32(const float* pred, const float* source, int source_batch,
 /* out = k32[b] * clamp(pred, 0, 1) in fp32: IlluminanceCorrect's output.  out may alias pred. */
 int nd_illum_apply_f32(const float* pred, const float* k32, float* out, int B, int C, int H, int W, void* stream);
 
+/* ------------------------------------------------------------------ scoring of generated noise (utils/util.py:185-255, utils/raw_util.py:161-189)
+ * The KL-divergence yardstick of the noise-generation literature (get_histogram, kl_div_forward / _inverse / _sym / kl_div_3, the 66-bin
+ * edges of kldiv_patch_set) and the signal-dependence check (sliding_window, compute_poisson_lambda_by_patch).  A repeated call gives the
+ * same bits, a set's (image's) result does not depend on the other sets of the call, the workspace is the caller's and the outputs need
+ * no zeroing.  Argument errors: ND_E_BADARG (null pointer, non-positive size, misaligned pointer, q_sets) or ND_E_SHAPE (n_bins).
+ *
+ * nd_histogram_f32: np.histogram(x[s], edges)[0] for each of the S sets of n fp32 values (x: [S][n], contiguous, 4-byte aligned).  edges:
+ * n_edges = n_bins + 1 doubles on the device, 1 <= n_bins <= 4096; counts: int64 [S][n_bins]; both 8-byte aligned.  v is counted in bin i
+ * when edges[i] <= (double)v < edges[i + 1], the last bin also takes v == edges[n_bins]; NaN, +-inf and values outside
+ * [edges[0], edges[n_bins]] are counted nowhere.  The comparison is in double against the edges as given (np.arange's edges are not
+ * round).  The edges must be finite and STRICTLY increasing: numpy also accepts repeated edges, this library does not, and it cannot
+ * check a device array -- that is the caller's contract (noisediff_amd.noise_stats checks the host array it uploads).  Two launches:
+ * every workgroup counts into a uint32 histogram in LDS (integer LDS atomics: the order does not matter) and stores it to the workspace,
+ * the second launch sums a set's partials in a fixed order.  A workgroup takes nd_histogram_chunk_elements() elements per trip.
+ * Workspace: nd_histogram_workspace_bytes(S, n, n_bins) bytes, 4-byte aligned.  S <= 65535, n <= 2^40. */
+int     nd_histogram_chunk_elements(void);
+int64_t nd_histogram_workspace_bytes(int S, int64_t n, int n_bins);
+int nd_histogram_f32(const float* x, int S, int64_t n, const double* edges, int n_edges, int64_t* counts, void* workspace, void* stream);
+/* kl_div_3 (:199-227) of S pairs of histograms, everything in fp64, one workgroup per set, fixed summation order: with p = p_counts / n_p and
+ * q = q_counts / n_q (n: the element count np.prod(data.shape) of get_histogram, dropped values included, not the sum of the counts),
+ * out[s] = { sum p log(p / q), sum q log(q / p), their mean } over the bins with p > 0 and q > 0; no such bin gives 0.0.  p_counts: int64
+ * [S][n_bins]; q_counts: [q_sets][n_bins] with q_sets 1 (one histogram for every set) or S; out: fp64 [S][3].
+ * nd_kl_div_hist_f64: the same for hists that are already fp64 fractions; a bin whose p or q is NaN or inf is dropped, as the reference does. */
+int nd_kl_div_f64(const int64_t* p_counts, const int64_t* q_counts, int64_t n_p, int64_t n_q, int n_bins, int S, int q_sets, double* out,
+                  void* stream);
+int nd_kl_div_hist_f64(const double* p, const double* q, int n_bins, int S, int q_sets, double* out, void* stream);
+/* compute_poisson_lambda_by_patch (:161-189) for an fp32 NCHW image: per pixel the mean and the unbiased standard deviation (divisor 8) of
+ * its 3 x 3 window with ZERO padding (F.unfold(3, padding 1) + torch.std_mean), both formed in fp32 from the nine values in two passes.
+ * std, mean: fp32 [B][C][H][W], either may be NULL and is then not written.  fit: fp64 [B * C][7] = { N = H W, sum m, sum s, sum m m,
+ * sum m s, slope, intercept }, the sums over the fp32 m and s of every pixel accumulated in fp64 in a fixed order, slope =
+ * (N sum ms - sum m sum s) / (N sum mm - (sum m)^2) and intercept = (sum s - slope sum m) / N: LinearRegression().fit(mean, std)'s coef_
+ * and intercept_.  A zero denominator gives NaN for both.  H, W >= 1.  Workspace: nd_patch_std_mean_workspace_bytes(B, C, H, W) bytes, 8-byte aligned. */
+int64_t nd_patch_std_mean_workspace_bytes(int B, int C, int H, int W);
+int nd_patch_std_mean_f32(const float* x, float* std, float* mean, double* fit, void* workspace, int B, int C, int H, int W, void* stream);
+
 /* ------------------------------------------------------------------ the denoiser's training batch (dataset_denoising.py:80-168, trainer_denoising.py:100-166,207-217)
  * nd_denoise_batch_f32: ONE launch from generated noise patches to the (noisy, clean) pair TrainableLSID takes.  noise, clean: fp32 NCHW
  * [B][4][patch][patch]; noisy, clean_out: [B][4][crop_h][crop_w].  Per output element (c, y, x), with the row of `table` for its sample:

@@ -3,7 +3,9 @@ __version__ = "0.1.0"
 
 __all__ = ["GaussianDiffusion", "NoiseDiffNet", "UNet_PosEmbV2", "UNet_PosEmbV2_NoPosition", "UNet_PosEmbV2_CameraCond", "LSID",
            "TrainableNoiseDiffNet", "TrainableLSID", "pack_raw", "load_pair", "to_bayer", "RealBatchBuilder", "PoissonGaussianBatchBuilder",
-           "DiffusionBatchBuilder", "GenerationBatchBuilder", "balanced_sample_list", "__version__"]
+           "DiffusionBatchBuilder", "GenerationBatchBuilder", "balanced_sample_list", "kld_edges", "get_histogram",
+           "histogram_counts", "kl_div_forward", "kl_div_inverse", "kl_div_sym", "kl_div_3", "noise_kld", "patch_std_mean", "poisson_lambda_by_patch",
+           "__version__"]
 
 
 def __getattr__(name):
@@ -29,4 +31,8 @@ def __getattr__(name):
     if name in ("DiffusionBatchBuilder", "GenerationBatchBuilder", "balanced_sample_list"):
         from . import diffusion_data
         return getattr(diffusion_data, name)
+    if name in ("kld_edges", "get_histogram", "histogram_counts", "kl_div_forward", "kl_div_inverse", "kl_div_sym", "kl_div_3", "noise_kld",
+                "patch_std_mean", "poisson_lambda_by_patch"):
+        from . import noise_stats
+        return getattr(noise_stats, name)
     raise AttributeError(name)

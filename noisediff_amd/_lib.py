@@ -207,6 +207,13 @@ SIGNATURES = {
     "nd_illum_scale_workspace_bytes": (i64, [i32, i32, i32, i32]),
     "nd_illum_scale_f32": (i32, [vp, vp, i32, vp, vp, vp, i32, i32, i32, i32, vp]),
     "nd_illum_apply_f32": (i32, [vp, vp, vp, i32, i32, i32, i32, vp]),
+    "nd_histogram_chunk_elements": (i32, []),
+    "nd_histogram_workspace_bytes": (i64, [i32, i64, i32]),
+    "nd_histogram_f32": (i32, [vp, i32, i64, vp, i32, vp, vp, vp]),
+    "nd_kl_div_f64": (i32, [vp, vp, i64, i64, i32, i32, i32, vp, vp]),
+    "nd_kl_div_hist_f64": (i32, [vp, vp, i32, i32, i32, vp, vp]),
+    "nd_patch_std_mean_workspace_bytes": (i64, [i32, i32, i32, i32]),
+    "nd_patch_std_mean_f32": (i32, [vp, vp, vp, vp, vp, i32, i32, i32, i32, vp]),
     "nd_denoise_batch_f32": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, vp, vp, vp, u64, i64, i32, vp, vp, vp, vp, i32, i32, i32, i32, vp]),
     "nd_philox_poisson_f32": (i32, [vp, vp, u64, i64, i32, i32, i64, vp]),
     "nd_pack_darkshading_f32": (i32, [vp, vp, i32, i32, vp]),
@@ -221,7 +228,8 @@ _UNCHECKED = {"nd_version", "nd_last_error", "nd_stream_device", "nd_conv3x3_wgr
               "nd_pack_conv3x3_wino_weight_floats", "nd_pack_conv3x3_wino4_weight_floats", "nd_conv3x3_wino4_splitk_plan", "nd_conv3x3_wino4_16_splitk_plan", "nd_conv3x3_wino4_splitk_workspace_floats", "nd_token_sum_workspace_floats", "nd_cond_step_lds_bytes", "nd_conv3x3_wgrad_workspace_floats",
               "nd_groupnorm_train_workspace_floats", "nd_linear_wgrad_workspace_floats",
               "nd_layernorm_train_workspace_floats", "nd_groupnorm_silu_train_workspace_floats", "nd_conv3x3_wgrad_cat_workspace_floats",
-              "nd_convt2x2_wgrad_workspace_floats", "nd_image_quality_workspace_bytes", "nd_illum_scale_workspace_bytes"}
+              "nd_convt2x2_wgrad_workspace_floats", "nd_image_quality_workspace_bytes", "nd_illum_scale_workspace_bytes",
+              "nd_histogram_chunk_elements", "nd_histogram_workspace_bytes", "nd_patch_std_mean_workspace_bytes"}
 
 _lib: Optional[C.CDLL] = None
 

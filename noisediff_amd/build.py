@@ -18,7 +18,7 @@ CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(CSRC, "build")
 LIB = os.path.join(HERE, "libnoisediff_hip.so")
 SOURCES = ["runtime", "conv3x3", "conv3x3_wino", "conv3x3_wino2", "conv3x3_wino4", "conv3x3_wgrad", "linear_wgrad", "pointwise", "pwchain", "norm", "norm_train", "small", "sampler",
-           "attention", "linattn", "adam", "lsid_train", "quality", "denoise_batch", "raw"]
+           "attention", "linattn", "adam", "lsid_train", "quality", "denoise_batch", "raw", "noise_stats"]
 ARCH = "gfx950"
 # -amdgpu-mfma-vgpr-form: keep MFMA accumulators in VGPRs (gfx950 has a unified file); without it hipcc 7.2 parks
 # them in AGPRs and wraps every v_mfma_f32_32x32x2_f32 in v_accvgpr_read/write copies (8 VALU per MFMA, measured)
@@ -90,5 +90,32 @@ def build(force: bool = False, verbose: bool = False) -> str:
     return LIB
 
 
+def build_variant(name: str, defines, out: str) -> str:
+    """One source of SOURCES compiled with extra -D defines and linked with the runtime alone into ``out``: a library that holds that source's
+    entry points only, for tools that time a compile-time variant of a kernel next to the shipped one (tools/noise_stats_bench.py --variants).
+    The in-tree library and its objects are not touched.
+
+        python -m noisediff_amd.build --variant noise_stats ND_HIST_VARIANT=1 out/libnoise_stats_v1.so"""
+    if name not in SOURCES or name == "runtime":
+        raise ValueError(f"{name} is not a source of the library")
+    build()                                                      # the runtime object (nd_set_error, the device queries)
+    hipcc = _hipcc()
+    srcname, flags = SPECIAL.get(name, (name, FLAGS))
+    out = os.path.abspath(out)
+    os.makedirs(os.path.dirname(out), exist_ok=True)
+    obj = out + ".o"
+    for cmd in ([hipcc, *flags, *[f"-D{d}" for d in defines], "-c", os.path.join(CSRC, srcname + ".hip"), "-o", obj],
+                [hipcc, "-shared", "-fPIC", f"--offload-arch={ARCH}", "-o", out, obj, os.path.join(OBJ, "runtime.o")]):
+        r = subprocess.run(cmd, capture_output=True, text=True)
+        if r.returncode != 0:
+            raise RuntimeError(f"hipcc failed: {' '.join(cmd)}\n{r.stdout}\n{r.stderr}")
+    os.remove(obj)
+    return out
+
+
 if __name__ == "__main__":
-    print(build(force="--force" in sys.argv, verbose=True))
+    if "--variant" in sys.argv:
+        i = sys.argv.index("--variant")
+        print(build_variant(sys.argv[i + 1], sys.argv[i + 2:-1], sys.argv[-1]))
+    else:
+        print(build(force="--force" in sys.argv, verbose=True))
