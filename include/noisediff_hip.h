@@ -379,6 +379,65 @@ int nd_kl_div_hist_f64(const double* p, const double* q, int n_bins, int S, int 
 int64_t nd_patch_std_mean_workspace_bytes(int B, int C, int H, int W);
 int nd_patch_std_mean_f32(const float* x, float* std, float* mean, double* fit, void* workspace, int B, int C, int H, int W, void* stream);
 
+/* ------------------------------------------------------------------ noise level function (utils/raw_util.py:248-322)
+ * get_poisson_lambda, get_poisson_lambda_all_images and get_regression_result_all_images: the noisy pixels grouped by the clean value they
+ * sit on, the unbiased std of every group, and sklearn's TheilSenRegressor of std on clean value.  Nothing allocates, frees, synchronises or
+ * reads on the host inside an entry point, so each can be captured; argument errors are ND_E_BADARG before any device call.
+ *
+ * The table: uint64 [n_levels][4] = { count, sum q, low and high 64 bits of sum q^2 }, q = rint(noisy * 2^30) + 2^32 (unsigned, below
+ * 2^33); counters: uint64 [2].  Both 8-byte aligned; nd_level_table_bytes(n_levels) is the table's size.  nd_level_moments_reset zeroes
+ * both (one plain launch).  1 <= n_levels <= 2^24, 0 < scale <= 2^24.
+ *
+ * nd_level_moments_f32 ADDS n elements (1 <= n <= 2^31 - 1; clean, noisy: fp32, 4-byte aligned, any length, vector loads when both start
+ * on 16 bytes) to the table.  The level of an element is l = rint(clean * scale) in fp32; it is on the grid when 0 <= l < n_levels and
+ * fabsf(clean - (float)l / (float)scale) < 1e-6f, the reference's own membership test applied to the value the packer produces for code l
+ * (scale = white - black = 15871, n_levels = 15872 for the Sony frames).  Two deviations from the reference: an element off the grid adds 1
+ * to counters[0] and is left out (the reference opens a group of its own for such a value); an on-grid element whose noisy is NaN, +-inf or
+ * |noisy| >= 4 adds 1 to counters[1] and is left out (the reference turns the level's std into a NaN and then drops the level).  Every sum
+ * is formed by 64-bit INTEGER atomic adds, the high word of sum q^2 taking the carry of the low one (old + v < old on the value the atomic
+ * returns): integer adds commute, so the table is exact and does not depend on the order of the elements, on the split into calls or on
+ * the batch.  A wave whose 256 elements of a trip share one level adds them in registers and issues the atomics from one lane.  A table may
+ * take 2^31 - 1 elements in total (about 178 SID frames): within that n sum q^2 - (sum q)^2 fits 128 bits.  The entry point cannot see the
+ * total without a synchronisation: the caller counts what it adds (noisediff_amd.noise_level.LevelMoments raises before the launch that
+ * would pass the limit).
+ *
+ * nd_level_stats_f64: per level count (int64), mean = (sum q / n - 2^32) 2^-30 and std = sqrt((n sum q^2 - (sum q)^2) / n / (n - 1)) 2^-30
+ * (fp64 [n_levels] each): the integer part exactly in 128-bit arithmetic, one correctly rounded conversion, two IEEE divisions.  n < 2
+ * gives a NaN std, as torch.std does, n == 0 also a NaN mean.
+ *
+ * nd_level_curve_f64: the fit's input.  The "unique values" are the levels with count >= 1 in ascending order, U of them; with
+ * below_median = 1 the first (U - 1) / 2 + 1 are kept (value <= torch.median(unique), the lower median), else all; levels whose std is NaN
+ * are dropped; x[i] = (double)((float)l / (float)scale), y[i] = std[l], compacted in level order; *m (device int32) = their number.  x, y:
+ * fp64 [n_levels], NaN past m.
+ *
+ * nd_theil_sen_f64: TheilSenRegressor().fit for one feature.  A pair (i, j) of curve points gives slope = (y_j - y_i) / (x_j - x_i) and
+ * intercept = y_i - slope x_i; the fit is the spatial median of these points exactly as sklearn's _spatial_median and
+ * _modified_weiszfeld_step define it: start at the mean; a step forms d = P - old, the mask |d| >= DBL_EPSILON, in_X = (a point was masked
+ * out), qn = |sum d / |d||, dir = sum(P / |d|) / sum(1 / |d|) when qn > DBL_EPSILON (else dir = 1, qn = 1),
+ * new = max(0, 1 - in_X / qn) dir + min(1, in_X / qn) old, and stops when sum (old - new)^2 < tol^2; if no step stops it, the new of step
+ * max_iter is the result.  pairs == NULL (n_pairs = 0): all m (m - 1) / 2 pairs i < j, x strictly increasing (the curve is); else the
+ * n_pairs >= 1 pairs of the int32 [n_pairs][2] table (an index outside [0, m) gives a NaN point).  *m is read on the device and clamped to
+ * [0, max_m]; x, y hold max_m values (1 <= max_m <= 2^24).  out: fp64 [4] = { intercept, slope, steps taken, pairs used }.  m == 0 gives
+ * (0, 0) as the reference returns, m == 1 without a table gives NaN (the reference raises); a pair with equal x is a NaN or infinite point
+ * and the result is then not finite (the caller's contract).  All arithmetic is fp64, no pair is stored (a step recomputes them), every
+ * sum has a fixed order (per-workgroup partials in workspace slots, the slots summed in order; the grid is a constant, so the bits
+ * depend on x, y, m and the table alone).  2 + 2 max_iter
+ * plain launches; once the device's done flag is set the remaining ones exit at their first instruction.  1 <= max_iter <= 65536, tol >= 0.
+ * Workspace: nd_theil_sen_workspace_bytes(max_m, n_pairs) bytes, 8-byte aligned, needs no zeroing.
+ * DEVIATION from the reference: above 141 points sklearn fits a random subset of 10 000 pairs (max_subpopulation, random_state=None) and
+ * its result changes from run to run; this library fits ALL pairs and is repeatable.  The pair table lets a caller fit any subset,
+ * sklearn's own included. */
+int64_t nd_level_table_bytes(int n_levels);
+int nd_level_moments_reset(uint64_t* table, int n_levels, uint64_t* counters, void* stream);
+int nd_level_moments_f32(const float* clean, const float* noisy, int64_t n, float scale, int n_levels, uint64_t* table, uint64_t* counters,
+                         void* stream);
+int nd_level_stats_f64(const uint64_t* table, int n_levels, int64_t* count, double* mean, double* std, void* stream);
+int nd_level_curve_f64(const int64_t* count, const double* std, int n_levels, float scale, int below_median, double* x, double* y, int32_t* m,
+                       void* stream);
+int64_t nd_theil_sen_workspace_bytes(int max_m, int64_t n_pairs);
+int nd_theil_sen_f64(const double* x, const double* y, const int32_t* m, int max_m, const int32_t* pairs, int64_t n_pairs, int max_iter,
+                     double tol, double* out, void* workspace, void* stream);
+
 /* ------------------------------------------------------------------ the denoiser's training batch (dataset_denoising.py:80-168, trainer_denoising.py:100-166,207-217)
  * nd_denoise_batch_f32: ONE launch from generated noise patches to the (noisy, clean) pair TrainableLSID takes.  noise, clean: fp32 NCHW
  * [B][4][patch][patch]; noisy, clean_out: [B][4][crop_h][crop_w].  Per output element (c, y, x), with the row of `table` for its sample:

@@ -5,6 +5,7 @@ __all__ = ["GaussianDiffusion", "NoiseDiffNet", "UNet_PosEmbV2", "UNet_PosEmbV2_
            "TrainableNoiseDiffNet", "TrainableLSID", "pack_raw", "load_pair", "to_bayer", "RealBatchBuilder", "PoissonGaussianBatchBuilder",
            "DiffusionBatchBuilder", "GenerationBatchBuilder", "balanced_sample_list", "kld_edges", "get_histogram",
            "histogram_counts", "kl_div_forward", "kl_div_inverse", "kl_div_sym", "kl_div_3", "noise_kld", "patch_std_mean", "poisson_lambda_by_patch",
+           "LevelMoments", "level_curve", "theil_sen", "get_poisson_lambda", "get_poisson_lambda_all_images", "get_regression_result_all_images",
            "__version__"]
 
 
@@ -35,4 +36,8 @@ def __getattr__(name):
                 "patch_std_mean", "poisson_lambda_by_patch"):
         from . import noise_stats
         return getattr(noise_stats, name)
+    if name in ("LevelMoments", "level_curve", "theil_sen", "get_poisson_lambda", "get_poisson_lambda_all_images",
+                "get_regression_result_all_images"):
+        from . import noise_level
+        return getattr(noise_level, name)
     raise AttributeError(name)

@@ -214,6 +214,13 @@ SIGNATURES = {
     "nd_kl_div_hist_f64": (i32, [vp, vp, i32, i32, i32, vp, vp]),
     "nd_patch_std_mean_workspace_bytes": (i64, [i32, i32, i32, i32]),
     "nd_patch_std_mean_f32": (i32, [vp, vp, vp, vp, vp, i32, i32, i32, i32, vp]),
+    "nd_level_table_bytes": (i64, [i32]),
+    "nd_level_moments_reset": (i32, [vp, i32, vp, vp]),
+    "nd_level_moments_f32": (i32, [vp, vp, i64, f32, i32, vp, vp, vp]),
+    "nd_level_stats_f64": (i32, [vp, i32, vp, vp, vp, vp]),
+    "nd_level_curve_f64": (i32, [vp, vp, i32, f32, i32, vp, vp, vp, vp]),
+    "nd_theil_sen_workspace_bytes": (i64, [i32, i64]),
+    "nd_theil_sen_f64": (i32, [vp, vp, vp, i32, vp, i64, i32, f64, vp, vp, vp]),
     "nd_denoise_batch_f32": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, vp, vp, vp, u64, i64, i32, vp, vp, vp, vp, i32, i32, i32, i32, vp]),
     "nd_philox_poisson_f32": (i32, [vp, vp, u64, i64, i32, i32, i64, vp]),
     "nd_pack_darkshading_f32": (i32, [vp, vp, i32, i32, vp]),
@@ -229,7 +236,8 @@ _UNCHECKED = {"nd_version", "nd_last_error", "nd_stream_device", "nd_conv3x3_wgr
               "nd_groupnorm_train_workspace_floats", "nd_linear_wgrad_workspace_floats",
               "nd_layernorm_train_workspace_floats", "nd_groupnorm_silu_train_workspace_floats", "nd_conv3x3_wgrad_cat_workspace_floats",
               "nd_convt2x2_wgrad_workspace_floats", "nd_image_quality_workspace_bytes", "nd_illum_scale_workspace_bytes",
-              "nd_histogram_chunk_elements", "nd_histogram_workspace_bytes", "nd_patch_std_mean_workspace_bytes"}
+              "nd_histogram_chunk_elements", "nd_histogram_workspace_bytes", "nd_patch_std_mean_workspace_bytes", "nd_level_table_bytes",
+              "nd_theil_sen_workspace_bytes"}
 
 _lib: Optional[C.CDLL] = None
 
