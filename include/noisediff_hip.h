@@ -759,6 +759,39 @@ int nd_rmsnorm_nhwc_f32(const float* x, int ldx, const float* g, float* out, int
 /* out = RMSNorm(x) * g + res: LinearAttention's closing RMSNorm (Diffusion_arch.py:213-216) with the residual of the per-stage wiring */
 int nd_rmsnorm_add_nhwc_f32(const float* x, int ldx, const float* g, const float* res, int ldr, float* out, int ldo, int B, int HW, int C, void* stream);
 
+/* ------------------------------------------------------------------ training the attention modules (forward with saved state, backward)
+ * fp32, fixed summation order, no atomics: a repeated call gives the same bits and a sample's result does not depend on its batch.
+ * dqkv has qkv's layout ([B][N][q | k | v thirds]): it is the gradient of to_qkv's output as it stands.  All 3 * heads * dh channels of every
+ * token are written (not accumulated: no clearing needed); floats beyond them in a row of ld_dqkv are left untouched.  dh must be 32
+ * (ND_E_SHAPE otherwise), any N >= 1; all strides multiples of 4 floats, pointers 16-byte aligned. */
+
+/* nd_attention_mfma_f32 (same kernel body, `out` bit for bit the same) that also writes lse[b][h][i] = m_i + log(l_i) of the scaled scores
+ * (models/attend.py:101-116), fp32 [B][heads][N]: what the backward recomputes the probabilities from. */
+int nd_attention_train_forward_f32(const float* qkv, int ld_qkv, float* out, int ld_out, float* lse,
+                                   int B, int N, int heads, int dh, void* stream);
+/* Backward of Attention's core (Diffusion_arch.py:255-266), flash-style on the exact-fp32 matrix instruction: delta_i = sum_d dO_i O_i,
+ * P = exp(S - lse) recomputed per tile (no N x N tensor), dV = P^T dO, dP = dO V^T, dS = P (.) (dP - delta), dQ = scale dS K, dK = scale dS^T Q.
+ * Three launches: delta; a pass whose workgroups own key tiles (dK, dV); a pass whose workgroups own query tiles (dQ).
+ * `workspace`: nd_attention_backward_workspace_floats(B, N, heads) floats.  Grid limits: B, heads <= 65535, B * N * heads < 2^38 (ND_E_SHAPE). */
+int64_t nd_attention_backward_workspace_floats(int B, int N, int heads);
+int nd_attention_backward_f32(const float* qkv, int ld_qkv, const float* out, int ld_out, const float* dout, int ld_dout, const float* lse,
+                              float* dqkv, int ld_dqkv, float* workspace, int B, int N, int heads, int dh, void* stream);
+/* Backward of LinearAttention's core (Diffusion_arch.py:218-235).  `fwd_workspace`: the workspace nd_linear_attention_f32 left for the SAME
+ * qkv (the key statistics and the per-chunk context partials) -- the saved state of the forward.  With q~ = softmax_d(q), s = dh^-1/2,
+ * k^ = softmax_n(k), ctx = k^ v^T:  dctx = s q~ dout^T;  dq = q~ (.) (t - sum_d q~ t), t = s ctx dout;  dv = dctx^T k^;
+ * dk = k^ (.) (dctx v - r), r[d] = sum_e dctx[d][e] ctx[d][e].  Two passes over N (per-chunk partials of dctx reduced in chunk order, then
+ * the three gradients per pixel), O(N dh^2).  `workspace`: nd_linear_attention_backward_workspace_floats(B, N, heads) floats. */
+int64_t nd_linear_attention_backward_workspace_floats(int B, int N, int heads);
+int nd_linear_attention_backward_f32(const float* qkv, int ld_qkv, const float* dout, int ld_dout, const float* fwd_workspace, float* dqkv,
+                                     int ld_dqkv, float* workspace, int B, int N, int heads, int dh, void* stream);
+/* Backward of RMSNorm (Diffusion_arch.py:84-90; forward nd_rmsnorm_nhwc_f32 / nd_rmsnorm_add_nhwc_f32), the norm recomputed from x:
+ * dx [B][HW][C] and dg [C] (per-workgroup partials, then fp64 in a fixed order).  Where |x| < 1e-12 the clamp makes the norm a constant and
+ * dx = g dy sqrt(C) / 1e-12, as autograd of F.normalize gives it (no 0/0).  The residual of the _add form receives dy itself: no kernel.
+ * C % 4 == 0, C <= 1024.  `workspace`: nd_rmsnorm_backward_workspace_floats(B * HW, C) floats. */
+int64_t nd_rmsnorm_backward_workspace_floats(int64_t npix, int C);
+int nd_rmsnorm_backward_f32(const float* dy, int lddy, const float* x, int ldx, const float* g, float* dx, int lddx, float* dg, float* workspace,
+                            int B, int HW, int C, void* stream);
+
 /* ------------------------------------------------------------------ optimizer step of the training path
  * torch.optim.Adam's update (the reference's optimizer: models/trainer_diffusion.py:94; L2 weight decay added to the gradient, no amsgrad)
  * for all parameters of a group in ONE launch -- PyTorch's foreach form makes ~10 passes over the parameters.  `items_dev`: n_items records

@@ -176,6 +176,13 @@ SIGNATURES = {
     "nd_sampler_step_ddim_f32": (i32, [vp, vp, vp, i64, C.POINTER(SamplerState), i32, u64, i64, i32, i32, i32, vp]),
     "nd_philox_normal_f32": (i32, [vp, u64, i64, i32, i32, i32, i32, vp]),
     "nd_attention_mfma_f32": (i32, [vp, i32, vp, i32, i32, i32, i32, i32, vp]),
+    "nd_attention_train_forward_f32": (i32, [vp, i32, vp, i32, vp, i32, i32, i32, i32, vp]),
+    "nd_attention_backward_workspace_floats": (i64, [i32, i32, i32]),
+    "nd_attention_backward_f32": (i32, [vp, i32, vp, i32, vp, i32, vp, vp, i32, vp, i32, i32, i32, i32, vp]),
+    "nd_linear_attention_backward_workspace_floats": (i64, [i32, i32, i32]),
+    "nd_linear_attention_backward_f32": (i32, [vp, i32, vp, i32, vp, vp, i32, vp, i32, i32, i32, i32, vp]),
+    "nd_rmsnorm_backward_workspace_floats": (i64, [i64, i32]),
+    "nd_rmsnorm_backward_f32": (i32, [vp, i32, vp, i32, vp, vp, i32, vp, vp, i32, i32, i32, vp]),
     "nd_linear_attention_workspace_floats": (i64, [i32, i32, i32]),
     "nd_linear_attention_f32": (i32, [vp, i32, vp, i32, vp, i32, i32, i32, i32, vp]),
     "nd_rmsnorm_nhwc_f32": (i32, [vp, i32, vp, vp, i32, i32, i32, i32, vp]),
@@ -237,7 +244,8 @@ _UNCHECKED = {"nd_version", "nd_last_error", "nd_stream_device", "nd_conv3x3_wgr
               "nd_layernorm_train_workspace_floats", "nd_groupnorm_silu_train_workspace_floats", "nd_conv3x3_wgrad_cat_workspace_floats",
               "nd_convt2x2_wgrad_workspace_floats", "nd_image_quality_workspace_bytes", "nd_illum_scale_workspace_bytes",
               "nd_histogram_chunk_elements", "nd_histogram_workspace_bytes", "nd_patch_std_mean_workspace_bytes", "nd_level_table_bytes",
-              "nd_theil_sen_workspace_bytes"}
+              "nd_theil_sen_workspace_bytes", "nd_attention_backward_workspace_floats", "nd_linear_attention_backward_workspace_floats",
+              "nd_rmsnorm_backward_workspace_floats"}
 
 _lib: Optional[C.CDLL] = None
 

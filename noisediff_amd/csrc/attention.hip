@@ -16,8 +16,11 @@ namespace {
 
 constexpr int DH = 32, KT = 64, LDK = DH + 4;
 
+// LSE: the training forward -- the same body, plus lse[b][h][i] = m_i + log(l_i) of the scaled scores for the backward's recomputation of P
+// (attn_train.hip).  The arithmetic of `out` is the same instruction sequence in both instantiations: the two entries agree bit for bit.
+template <bool LSE>
 __global__ __launch_bounds__(256) void attention_kernel(const float* __restrict__ qkv, int ldq, float* __restrict__ out, int ldo,
-                                                        int N, int heads, float scale) {
+                                                        float* __restrict__ lse, int N, int heads, float scale) {
     __shared__ __attribute__((aligned(16))) float Ks[KT * LDK];
     __shared__ __attribute__((aligned(16))) float Vs[KT * DH];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, half = lane >> 5, col = lane & 31;
@@ -107,6 +110,7 @@ __global__ __launch_bounds__(256) void attention_kernel(const float* __restrict_
         float* op = out + ((size_t)b * N + qi) * ldo + h * DH;
 #pragma unroll
         for (int r = 0; r < 16; ++r) op[nd_acc_row(r, lane)] = o[r] * inv;
+        if (LSE && half == 0) lse[((size_t)b * heads + h) * N + qi] = m_run + logf(l_run);
     }
 }
 
@@ -119,7 +123,20 @@ extern "C" int nd_attention_mfma_f32(const float* qkv, int ld_qkv, float* out, i
     ND_REQUIRE(ld_qkv >= 3 * heads * dh && ld_qkv % 4 == 0 && ld_out >= heads * dh, ND_E_SHAPE, "nd_attention_mfma: strides");
     ND_REQUIRE(nd_aligned16(qkv), ND_E_ALIGN, "nd_attention_mfma: alignment");
     ND_REQUIRE(B <= 65535 && heads <= 65535, ND_E_SHAPE, "nd_attention_mfma: grid too large");
-    hipLaunchKernelGGL(attention_kernel, dim3(nd_cdiv(N, 128), heads, B), dim3(256), 0, (hipStream_t)stream, qkv, ld_qkv, out, ld_out,
-                       N, heads, 1.0f / sqrtf((float)dh));
+    hipLaunchKernelGGL(attention_kernel<false>, dim3(nd_cdiv(N, 128), heads, B), dim3(256), 0, (hipStream_t)stream, qkv, ld_qkv, out, ld_out,
+                       (float*)nullptr, N, heads, 1.0f / sqrtf((float)dh));
     return nd_launch_status("nd_attention_mfma_f32");
+}
+
+extern "C" int nd_attention_train_forward_f32(const float* qkv, int ld_qkv, float* out, int ld_out, float* lse, int B, int N, int heads, int dh,
+                                              void* stream) {
+    ND_REQUIRE(qkv && out && lse, ND_E_BADARG, "nd_attention_train_forward: null pointer");
+    ND_REQUIRE(B > 0 && N > 0 && heads > 0, ND_E_BADARG, "nd_attention_train_forward: non-positive size");
+    ND_REQUIRE(dh == 32, ND_E_SHAPE, "nd_attention_train_forward: dim_head=%d (only 32 is built)", dh);
+    ND_REQUIRE(ld_qkv >= 3 * heads * dh && ld_qkv % 4 == 0 && ld_out >= heads * dh, ND_E_SHAPE, "nd_attention_train_forward: strides");
+    ND_REQUIRE(nd_aligned16(qkv), ND_E_ALIGN, "nd_attention_train_forward: alignment");
+    ND_REQUIRE(B <= 65535 && heads <= 65535, ND_E_SHAPE, "nd_attention_train_forward: grid too large");
+    hipLaunchKernelGGL(attention_kernel<true>, dim3(nd_cdiv(N, 128), heads, B), dim3(256), 0, (hipStream_t)stream, qkv, ld_qkv, out, ld_out,
+                       lse, N, heads, 1.0f / sqrtf((float)dh));
+    return nd_launch_status("nd_attention_train_forward_f32");
 }

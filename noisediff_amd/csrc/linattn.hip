@@ -14,7 +14,7 @@
 namespace {
 
 constexpr int DH = 32;
-constexpr int CHUNK = 2048;      // pixels per partial-context workgroup
+constexpr int CHUNK = ND_LA_CHUNK;      // pixels per partial-context workgroup
 
 // 1. kstat[b][h][d] = {max_n k, sum_n exp(k - max)}
 __global__ __launch_bounds__(256) void la_kstat_kernel(const float* __restrict__ qkv, int ldq, float* __restrict__ kstat, int N, int heads) {

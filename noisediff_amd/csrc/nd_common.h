@@ -7,6 +7,7 @@
 #include "../../include/noisediff_hip.h"
 
 #define ND_WAVE 64
+constexpr int ND_LA_CHUNK = 2048;      // pixels per partial-context workgroup of LinearAttention: linattn.hip writes the chunks' partials, attn_train.hip reads them
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x2 __attribute__((ext_vector_type(2)));

@@ -20,7 +20,8 @@ the channels_last tensors once per pass, where PyTorch's NCHW group norm first c
 blocks the norms cost more than the convolutions before this.  ``LinearFunction`` (third slice) keeps the output and the data
 gradient of token Linears / 1x1 convolutions on the library GEMM and takes their weight and bias gradient -- a reduction over up to
 10^6 tokens that library GEMMs run at a tenth of HBM speed -- to nd_linear_wgrad_f32 (linear_wgrad.hip); ``LayerNormFunction``:
-nn.LayerNorm over token channels forward and backward (norm_train.hip).  Activations and attention stay on PyTorch's own ROCm kernels for now.
+nn.LayerNorm over token channels forward and backward (norm_train.hip).  ``attention_core`` / ``linear_attention_core`` / ``rms_norm``: the cores of
+Attention and LinearAttention and their RMSNorm, forward and backward (attn_train.hip).  Activations stay on PyTorch's own ROCm kernels.
 
 There is no fallback: a CPU tensor or a missing library raises.
 """
@@ -966,6 +967,147 @@ def layer_norm(x: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor, eps: f
     if weight is None or bias is None or not _layer_norm_ok(x.shape[-1]) or weight.shape != (x.shape[-1],):
         raise ValueError(f"layer_norm: x {tuple(x.shape)}: needs affine parameters and C = 64, 128 or a multiple of 256 up to 1024")
     return LayerNormFunction.apply(x, weight, bias, eps)
+
+
+# ---- the attention modules (Diffusion_arch.py:84-90, 198-266): cores and RMSNorm forward and backward on the library (attention.hip, linattn.hip,
+#      norm.hip, attn_train.hip).  fp32, fixed summation order: a repeated step gives the same bits, and every launch can be captured.
+ATTN_DIM_HEAD = 32          # the head width the attention kernels are built for
+
+
+def _check_qkv(op: str, qkv: torch.Tensor, heads: int) -> None:
+    if qkv.dim() != 4 or heads <= 0 or qkv.shape[1] != 3 * heads * ATTN_DIM_HEAD:
+        raise ValueError(f"{op}: qkv {tuple(qkv.shape)} is not (B, 3 * {heads} heads * {ATTN_DIM_HEAD}, H, W)")
+
+
+class AttentionCoreFunction(torch.autograd.Function):
+    """softmax(q k^T / sqrt(dh)) v per (sample, head) on to_qkv's output as it stands (Attention.forward with Attend's explicit path: Diffusion_arch.py:255-266,
+    models/attend.py:101-116): nd_attention_train_forward_f32 (the sampling path's kernel, plus the log-sum-exp rows) and the flash-style
+    nd_attention_backward_f32, whose dqkv has qkv's layout."""
+
+    @staticmethod
+    def forward(ctx, qkv, heads):
+        qn = _nhwc(qkv)
+        _need_gpu(qn)
+        B, C3, H, W = qn.shape
+        hid, N = C3 // 3, H * W
+        with _on(qn.device):
+            out = _empty((B, hid, H, W), qn.device, memory_format=torch.channels_last)
+            lse = _empty((B, heads, N), qn.device)
+            L.call("nd_attention_train_forward_f32", qn.data_ptr(), C3, out.data_ptr(), hid, lse.data_ptr(), B, N, heads, hid // heads, _stream(qn.device))
+        ctx.save_for_backward(qn, out, lse)
+        ctx.heads = heads
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_out):
+        qn, out, lse = ctx.saved_tensors
+        g = _nhwc(grad_out)
+        B, C3, H, W = qn.shape
+        hid, N, heads = C3 // 3, H * W, ctx.heads
+        with _on(qn.device):
+            dqkv = torch.empty_like(qn, memory_format=torch.channels_last)
+            ws = _workspace("nd_attention_backward_workspace_floats", qn.device, B, N, heads)
+            L.call("nd_attention_backward_f32", qn.data_ptr(), C3, out.data_ptr(), hid, g.data_ptr(), hid, lse.data_ptr(), dqkv.data_ptr(), C3, ws.data_ptr(),
+                   B, N, heads, hid // heads, _stream(qn.device))
+        return dqkv, None
+
+
+def attention_core(qkv: torch.Tensor, heads: int = 4) -> torch.Tensor:
+    """Differentiable full-attention core on the HIP library: qkv (B, 3 * heads * 32, H, W), q | k | v thirds as ``to_qkv`` emits them, -> (B, heads * 32, H, W);
+    channels_last in and out."""
+    _check_qkv("attention_core", qkv, heads)
+    return AttentionCoreFunction.apply(qkv, heads)
+
+
+class LinearAttentionCoreFunction(torch.autograd.Function):
+    """LinearAttention's core (Diffusion_arch.py:218-235): nd_linear_attention_f32, whose workspace (the key statistics and the per-chunk context
+    partials) is the saved state of nd_linear_attention_backward_f32."""
+
+    @staticmethod
+    def forward(ctx, qkv, heads):
+        qn = _nhwc(qkv)
+        _need_gpu(qn)
+        B, C3, H, W = qn.shape
+        hid, N = C3 // 3, H * W
+        with _on(qn.device):
+            out = _empty((B, hid, H, W), qn.device, memory_format=torch.channels_last)
+            ws = _workspace("nd_linear_attention_workspace_floats", qn.device, B, N, heads)
+            L.call("nd_linear_attention_f32", qn.data_ptr(), C3, out.data_ptr(), hid, ws.data_ptr(), B, N, heads, hid // heads, _stream(qn.device))
+        ctx.save_for_backward(qn, ws)
+        ctx.heads = heads
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_out):
+        qn, fwd_ws = ctx.saved_tensors
+        g = _nhwc(grad_out)
+        B, C3, H, W = qn.shape
+        hid, N, heads = C3 // 3, H * W, ctx.heads
+        with _on(qn.device):
+            dqkv = torch.empty_like(qn, memory_format=torch.channels_last)
+            ws = _workspace("nd_linear_attention_backward_workspace_floats", qn.device, B, N, heads)
+            L.call("nd_linear_attention_backward_f32", qn.data_ptr(), C3, g.data_ptr(), hid, fwd_ws.data_ptr(), dqkv.data_ptr(), C3, ws.data_ptr(),
+                   B, N, heads, hid // heads, _stream(qn.device))
+        return dqkv, None
+
+
+def linear_attention_core(qkv: torch.Tensor, heads: int = 4) -> torch.Tensor:
+    """Differentiable LinearAttention core on the HIP library: the shapes of ``attention_core``."""
+    _check_qkv("linear_attention_core", qkv, heads)
+    return LinearAttentionCoreFunction.apply(qkv, heads)
+
+
+def _rms_norm_ok(C_: int) -> bool:
+    return C_ % 4 == 0 and 0 < C_ <= 1024
+
+
+class RMSNormFunction(torch.autograd.Function):
+    """RMSNorm (Diffusion_arch.py:84-90): F.normalize(x, dim=1) * g * sqrt(C) (+ res, added in the forward kernel) on nd_rmsnorm(_add)_nhwc_f32 and
+    nd_rmsnorm_backward_f32; the residual's gradient is the output's."""
+
+    @staticmethod
+    def forward(ctx, x, g, res):
+        xn = _nhwc(x)
+        _need_gpu(xn)
+        B, C_, H, W = xn.shape
+        g32 = g.detach().float().reshape(-1).contiguous()
+        with _on(xn.device):
+            y = torch.empty_like(xn, memory_format=torch.channels_last)
+            if res is None:
+                L.call("nd_rmsnorm_nhwc_f32", xn.data_ptr(), C_, g32.data_ptr(), y.data_ptr(), C_, B, H * W, C_, _stream(xn.device))
+            else:
+                rn = _nhwc(res)
+                L.call("nd_rmsnorm_add_nhwc_f32", xn.data_ptr(), C_, g32.data_ptr(), rn.data_ptr(), C_, y.data_ptr(), C_, B, H * W, C_, _stream(xn.device))
+        ctx.save_for_backward(xn, g)
+        ctx.has_res = res is not None
+        return y
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_out):
+        xn, g = ctx.saved_tensors
+        gn = _nhwc(grad_out)
+        B, C_, H, W = xn.shape
+        g32 = g.detach().float().reshape(-1).contiguous()
+        with _on(xn.device):
+            dx = torch.empty_like(xn, memory_format=torch.channels_last)
+            dg = _empty(C_, xn.device)
+            ws = _workspace("nd_rmsnorm_backward_workspace_floats", xn.device, B * H * W, C_)
+            L.call("nd_rmsnorm_backward_f32", gn.data_ptr(), C_, xn.data_ptr(), C_, g32.data_ptr(), dx.data_ptr(), C_, dg.data_ptr(), ws.data_ptr(),
+                   B, H * W, C_, _stream(xn.device))
+        return dx, dg.view(g.shape), (grad_out if ctx.has_res else None)
+
+
+def rms_norm(x: torch.Tensor, g: torch.Tensor, res: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Differentiable RMSNorm over the channels of a 4-D tensor on the HIP library: ``g`` (1, C, 1, 1) as the reference stores it (C % 4 == 0, C <= 1024);
+    ``res`` (x's shape) is added in the forward kernel."""
+    if x.dim() != 4 or not _rms_norm_ok(x.shape[1]) or g.numel() != x.shape[1]:
+        raise ValueError(f"rms_norm: x {tuple(x.shape)} / g {tuple(g.shape)}: needs a 4-D input, C a multiple of 4 up to 1024 and C gains")
+    if res is not None and res.shape != x.shape:
+        raise ValueError(f"rms_norm: res {tuple(res.shape)} does not match x {tuple(x.shape)}")
+    return RMSNormFunction.apply(x, g, res)
 
 
 def _eligible_layer_norm(m: nn.Module) -> bool:

@@ -7,8 +7,8 @@
 The graph is the reference network's (models/archs/Diffusion_arch.py:447-646) written as one functional forward
 over a flat parameter table; parameters are registered under the reference's own dotted names, so ``state_dict()`` is
 interchangeable with the reference class and with ``noisediff_amd.NoiseDiffNet``.  ``.hip()`` routes every 3x3 convolution and
-GroupNorm / LayerNorm through the HIP library forward and backward and the weight / bias gradients of the Linears and 1x1 convolutions
-(noisediff_amd/train.py); everything else is PyTorch.  Parity: the
+GroupNorm / LayerNorm through the HIP library forward and backward, the weight / bias gradients of the Linears and 1x1 convolutions, and the
+cores and RMSNorms of the optional attention modules (noisediff_amd/train.py); everything else is PyTorch.  Parity: the
 forward against the reference's golden activations and loss / gradients against tests/golden/training.npz (tests/test_trainable.py).
 """
 from __future__ import annotations
@@ -226,32 +226,59 @@ class _Ops:
 
 
     # ---- the attention modules the reference defines next to the network (Diffusion_arch.py:84-90,198-266): BASELINE config 4's mid-block Attention and
-    #      upstream's per-stage LinearAttention / Attention wiring.  Plain differentiable PyTorch around the library's 1x1 convolutions.
-    def rms_norm(self, name: str, x: torch.Tensor) -> torch.Tensor:
-        """RMSNorm (:84-90): F.normalize over the channels * g * sqrt(C)."""
-        return F.normalize(x, dim=1) * self.p[name + ".g"] * (x.shape[1] ** 0.5)
+    #      upstream's per-stage LinearAttention / Attention wiring.  On the library (train.rms_norm / attention_core / linear_attention_core) around its 1x1
+    #      convolutions; the PyTorch expressions where it cannot run, and then said so in FALLBACKS.
+    def rms_norm(self, name: str, x: torch.Tensor, res: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """RMSNorm (:84-90): F.normalize over the channels * g * sqrt(C) (+ res: in the library's forward kernel)."""
+        g = self.p[name + ".g"]
+        if self.hip and x.is_cuda:
+            if train._rms_norm_ok(x.shape[1]):
+                return train.rms_norm(x, g, res)
+            self._left_library(name, "rms_norm", f"C = {x.shape[1]}: outside the library's RMSNorm (C <= 1024, C % 4 == 0)")
+        y = F.normalize(x, dim=1) * g * (x.shape[1] ** 0.5)
+        return y if res is None else y + res
 
-    def attention(self, name: str, x: torch.Tensor) -> torch.Tensor:
-        """Attention (:237-266) with Attend's explicit path (models/attend.py:101-116): RMSNorm -> to_qkv -> softmax(q k^T / sqrt(d)) v -> to_out."""
-        b, c, h, w = x.shape
-        q, k, v = (t.reshape(b, HEADS, -1, h * w).transpose(-1, -2) for t in self.conv(name + ".to_qkv", self.rms_norm(name + ".norm", x)).chunk(3, dim=1))   # b h (xy) d
-        out = F.scaled_dot_product_attention(q, k, v)                            # scale d^-1/2, no mask, no dropout
-        return self.conv(name + ".to_out", out.transpose(-1, -2).reshape(b, -1, h, w))
+    def _attn_core_on_library(self, name: str, op: str, qkv: torch.Tensor) -> bool:
+        if not (self.hip and qkv.is_cuda):
+            return False
+        if qkv.shape[1] == 3 * HEADS * train.ATTN_DIM_HEAD:
+            return True
+        self._left_library(name, op, f"head width {qkv.shape[1] // (3 * HEADS)}: the library's attention kernels are built for {train.ATTN_DIM_HEAD}")
+        return False
 
-    def linear_attention(self, name: str, x: torch.Tensor) -> torch.Tensor:
-        """LinearAttention (:198-235): q softmax over d (scaled), k softmax over the pixels, context = k v^T, out = context^T q -> to_out.0 -> RMSNorm."""
+    def attention(self, name: str, x: torch.Tensor, res: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """Attention (:237-266) with Attend's explicit path (models/attend.py:101-116): RMSNorm -> to_qkv -> softmax(q k^T / sqrt(d)) v -> to_out (+ res:
+        in the epilogue of the library's 1x1 kernel)."""
         b, c, h, w = x.shape
-        q, k, v = (t.reshape(b, HEADS, -1, h * w) for t in self.conv(name + ".to_qkv", self.rms_norm(name + ".norm", x)).chunk(3, dim=1))    # b h d (xy)
-        q = q.softmax(dim=-2) * (q.shape[2] ** -0.5)
-        k = k.softmax(dim=-1)
-        ctx = torch.einsum("bhdn,bhen->bhde", k, v)
-        out = torch.einsum("bhde,bhdn->bhen", ctx, q).reshape(b, -1, h, w)
-        return self.rms_norm(name + ".to_out.1", self.conv(name + ".to_out.0", out))
+        qkv = self.conv(name + ".to_qkv", self.rms_norm(name + ".norm", x))
+        if self._attn_core_on_library(name, "attention", qkv):
+            out = train.attention_core(qkv, HEADS)
+        else:
+            q, k, v = (t.reshape(b, HEADS, -1, h * w).transpose(-1, -2) for t in qkv.chunk(3, dim=1))   # b h (xy) d
+            out = F.scaled_dot_product_attention(q, k, v)                        # scale d^-1/2, no mask, no dropout
+            out = out.transpose(-1, -2).reshape(b, -1, h, w)
+        return self.conv(name + ".to_out", out, res=res)
+
+    def linear_attention(self, name: str, x: torch.Tensor, res: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """LinearAttention (:198-235): q softmax over d (scaled), k softmax over the pixels, context = k v^T, out = context^T q -> to_out.0 -> RMSNorm
+        (+ res: in the closing norm's kernel)."""
+        b, c, h, w = x.shape
+        qkv = self.conv(name + ".to_qkv", self.rms_norm(name + ".norm", x))
+        if self._attn_core_on_library(name, "linear_attention", qkv):
+            out = train.linear_attention_core(qkv, HEADS)
+        else:
+            q, k, v = (t.reshape(b, HEADS, -1, h * w) for t in qkv.chunk(3, dim=1))    # b h d (xy)
+            q = q.softmax(dim=-2) * (q.shape[2] ** -0.5)
+            k = k.softmax(dim=-1)
+            ctx = torch.einsum("bhdn,bhen->bhde", k, v)
+            out = torch.einsum("bhde,bhdn->bhen", ctx, q).reshape(b, -1, h, w)
+        return self.rms_norm(name + ".to_out.1", self.conv(name + ".to_out.0", out), res=res)
 
     def stage_attention(self, name: str, kind, x: torch.Tensor) -> torch.Tensor:
+        """``module(x) + x``: the addition rides in the module's last kernel."""
         if not kind:
             return x
-        return (self.attention(name, x) if kind == "full" else self.linear_attention(name, x)) + x
+        return self.attention(name, x, res=x) if kind == "full" else self.linear_attention(name, x, res=x)
 
 
 def _forward(o: _Ops, x: torch.Tensor, time: torch.Tensor, condition, arch: str = "NoiseDiffNet", mid_attn: bool = False, stage_attn=None) -> torch.Tensor:
@@ -316,7 +343,7 @@ def _forward(o: _Ops, x: torch.Tensor, time: torch.Tensor, condition, arch: str 
         x = o.conv(f"{n}.{rs}", x, 1) if i == 3 else o.conv(f"{n}.{rs}.1", F.pixel_unshuffle(x, 2))
     x = o.resnet("mid_block1", x, t, GROUPS)
     if mid_attn:
-        x = o.attention("mid_attn", x) + x
+        x = o.attention("mid_attn", x, res=x)
     x = o.resnet("mid_block2", x, t, GROUPS)
     for i in range(4):
         n = f"ups.{i}"
@@ -367,7 +394,8 @@ class TrainableNoiseDiffNet(nn.Module):
             m.register_parameter(parts[-1], nn.Parameter(value))
 
     def hip(self, on: bool = True) -> "TrainableNoiseDiffNet":
-        """3x3 convolutions and GroupNorms forward and backward, Linear / 1x1 weight gradients on libnoisediff_hip (CUDA tensors only; raises without the library)."""
+        """3x3 convolutions, GroupNorms / LayerNorms and the cores and RMSNorms of the attention modules (``mid_attn`` / ``stage_attn``, head width 32) forward and
+        backward, Linears / 1x1 convolutions with their weight gradients on libnoisediff_hip (CUDA tensors only; raises without the library)."""
         if on:
             from . import _lib
             _lib.load()
