@@ -819,6 +819,64 @@ int nd_adam_step_f32(const nd_adam_item* items_dev, int n_items, const int32_t* 
 int nd_adam_step_capturable_f32(const nd_adam_item* items_dev, int n_items, const int32_t* chunks_dev, int n_chunks, float lr, float beta1, float beta2,
                                 float eps, float weight_decay, void* stream);
 
+/* ------------------------------------------------------------------ the two ends of a diffusion training step (diffusion_train.hip)
+ * GaussianDiffusion.forward / p_losses (models/denoising_diffusion_pytorch.py:481-542) around the network: timestep, noising and target in
+ * one launch; the weighted loss in two; its gradient in one.  All entries launch on the caller's stream and can be captured.
+ *
+ * Random numbers: Philox4x32-10, key = the 64-bit seed, counter = {index, global sample = first_sample + b, draw, block}.
+ *   block 1 element noise: index = quad q of the sample's elements in NHWC order, four normals for four consecutive NHWC elements;
+ *   block 2 offset noise: index = c >> 2, component c & 3, one normal per (sample, channel);
+ *   block 3 timestep: index 0, word 0 = w, t = (uint64(w) * T) >> 32 -- a timestep's probability is off 1 / T by less than 2^-32, a relative
+ *   bias below T / 2^32.  Block 0 is the sampler's, so sampling and training under one seed share no stream.  A sample's draws depend on
+ *   (seed, global sample index, draw) only: not on the batch size, its row, or the rank that holds it.
+ *
+ * nd_diffusion_noising_f32.  x0 fp32 (B, C, H, W): NCHW-contiguous (x0_channels_last = 0) or NHWC memory (1); C % 4 == 0.  noise (NHWC memory,
+ * x0's shape), offset [B][C] and t_in [B]: explicit values, or NULL to draw them; a t_in outside [0, T) is clamped (it lives in device memory).
+ * Outputs: t_out [B] always; x_t and target in NHWC memory; noise_out (NHWC, the element noise before the offset is added) and offset_out
+ * [B][C] when not NULL.  Per element, every operation rounded on its own, in the reference's order (:474-479, :490-492, :310-314, :539):
+ *   x = 2 x0 - 1 (auto_normalize);  n = noise + offset_strength * offset (offset_strength > 0);  x_t = a x + b n,  a = sqrt_alphas_cumprod[t],
+ *   b = sqrt_one_minus_alphas_cumprod[t];  target = n (objective 0), x (1), a n - b x (2).
+ * With explicit noise, offset and t_in the outputs equal the reference's bit for bit.  rng ({seed, first_sample, draw} as three int64 in device
+ * memory, or NULL) overrides the three scalars as nd_sampler_state.rng does: a captured graph draws anew on every replay once
+ * nd_diffusion_train_advance (draw += 1, one thread) follows it.  All float pointers 16-byte aligned (ND_E_ALIGN), C % 4 != 0: ND_E_SHAPE. */
+typedef struct nd_diffusion_noising {
+    const float* x0;
+    const float* noise;                             /* or NULL: drawn */
+    const float* offset;                            /* or NULL: drawn when offset_strength > 0 or offset_out is set */
+    const int64_t* t_in;                            /* or NULL: drawn */
+    const float* sqrt_alphas_cumprod;               /* [T] */
+    const float* sqrt_one_minus_alphas_cumprod;     /* [T] */
+    const int64_t* rng;                             /* or NULL */
+    int64_t* t_out;
+    float* x_t;
+    float* target;
+    float* noise_out;                               /* or NULL */
+    float* offset_out;                              /* or NULL */
+    uint64_t seed;
+    int64_t first_sample;
+    int64_t draw;                                   /* the low 32 bits are the counter word */
+    float offset_strength;
+    int32_t B, C, H, W, T;
+    int32_t objective, auto_normalize, x0_channels_last;
+} nd_diffusion_noising;
+int nd_diffusion_noising_f32(const nd_diffusion_noising* p, void* stream);
+int nd_diffusion_train_advance(int64_t* rng, void* stream);
+/* loss = mean_b( mean_elems((model_out - target)^2) * loss_weight[t_b] )  [+ mean_{b,c} |mean_hw(model_out) - mean_hw(target)| with x0_term,
+ * :524-528] on NHWC tensors [B][HW][C].  Differences and squares in fp32, every sum in fp64 in a fixed order: a sample is cut into slices of
+ * nd_diffusion_loss_slice_elements() elements, one workgroup each, whose partials go to `workspace`
+ * (nd_diffusion_loss_workspace_bytes(B, C, HW) bytes, 16-byte aligned); a second launch of one workgroup adds a sample's slices in slice order
+ * and the samples in a fixed tree.  TWO launches, no atomics and no arrival counter.  sample_loss [B] (optional) = mean_elems * loss_weight[t_b]:
+ * its bits depend on neither the batch size nor the sample's row.  t outside [0, T) is clamped.  x0_term needs C a power of two <= 256 (ND_E_SHAPE)
+ * and leaves the signs of the mean differences in the workspace, which nd_diffusion_loss_backward_f32 reads.  B <= 65535. */
+int nd_diffusion_loss_slice_elements(void);
+int64_t nd_diffusion_loss_workspace_bytes(int B, int C, int HW);
+int nd_diffusion_loss_f32(const float* model_out, const float* target, const int64_t* t, const float* loss_weight, int B, int C, int HW, int T,
+                          int x0_term, void* workspace, float* loss, float* sample_loss, void* stream);
+/* grad_out = g * ( 2 loss_weight[t_b] / (B C HW) * (model_out - target) [+ sign_{b,c} / (B C HW)] ), one pass, formed in fp64 and rounded once.
+ * g: the upstream gradient, one float in DEVICE memory (no host read).  workspace: the forward's (needed with x0_term only).  No gradient for target. */
+int nd_diffusion_loss_backward_f32(const float* model_out, const float* target, const int64_t* t, const float* loss_weight, const float* g,
+                                   const void* workspace, float* grad_out, int B, int C, int HW, int T, int x0_term, void* stream);
+
 /* ------------------------------------------------------------------ HIP graph helpers */
 int nd_stream_create(void** stream);
 int nd_stream_destroy(void* stream);

@@ -77,6 +77,14 @@ class SamplerState(C.Structure):
                 ("n_steps", C.c_int32), ("B", C.c_int32)]
 
 
+class DiffusionNoising(C.Structure):
+    _fields_ = [("x0", fptr), ("noise", fptr), ("offset", fptr), ("t_in", fptr), ("sqrt_alphas_cumprod", fptr), ("sqrt_one_minus_alphas_cumprod", fptr),
+                ("rng", fptr), ("t_out", fptr), ("x_t", fptr), ("target", fptr), ("noise_out", fptr), ("offset_out", fptr),
+                ("seed", C.c_uint64), ("first_sample", C.c_int64), ("draw", C.c_int64), ("offset_strength", C.c_float),
+                ("B", C.c_int32), ("C", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("T", C.c_int32),
+                ("objective", C.c_int32), ("auto_normalize", C.c_int32), ("x0_channels_last", C.c_int32)]
+
+
 i32, i64, u64, vp, f32, f64 = C.c_int, C.c_int64, C.c_uint64, C.c_void_p, C.c_float, C.c_double
 
 # name -> (restype, argtypes); everything include/noisediff_hip.h declares
@@ -148,6 +156,12 @@ SIGNATURES = {
     "nd_adam_chunk_elements": (i32, []),
     "nd_adam_step_f32": (i32, [vp, i32, vp, i32, f32, f32, f32, f32, vp]),
     "nd_adam_step_capturable_f32": (i32, [vp, i32, vp, i32, f32, f32, f32, f32, f32, vp]),
+    "nd_diffusion_noising_f32": (i32, [C.POINTER(DiffusionNoising), vp]),
+    "nd_diffusion_train_advance": (i32, [vp, vp]),
+    "nd_diffusion_loss_slice_elements": (i32, []),
+    "nd_diffusion_loss_workspace_bytes": (i64, [i32, i32, i32]),
+    "nd_diffusion_loss_f32": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, i32, vp, vp, vp, vp]),
+    "nd_diffusion_loss_backward_f32": (i32, [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp]),
     "nd_groupnorm_finalize_f32": (i32, [vp, vp, i32, vp, vp, vp, i32, vp, i32, i32, i32, f32, vp]),
     "nd_groupnorm_finalize_train_f32": (i32, [vp, vp, i32, vp, vp, vp, i32, vp, vp, i32, i32, i32, f32, vp]),
     "nd_layernorm_stats_f32": (i32, [vp, i32, vp, vp, i32, i32, i32, f32, vp]),
@@ -245,7 +259,7 @@ _UNCHECKED = {"nd_version", "nd_last_error", "nd_stream_device", "nd_conv3x3_wgr
               "nd_convt2x2_wgrad_workspace_floats", "nd_image_quality_workspace_bytes", "nd_illum_scale_workspace_bytes",
               "nd_histogram_chunk_elements", "nd_histogram_workspace_bytes", "nd_patch_std_mean_workspace_bytes", "nd_level_table_bytes",
               "nd_theil_sen_workspace_bytes", "nd_attention_backward_workspace_floats", "nd_linear_attention_backward_workspace_floats",
-              "nd_rmsnorm_backward_workspace_floats"}
+              "nd_rmsnorm_backward_workspace_floats", "nd_diffusion_loss_slice_elements", "nd_diffusion_loss_workspace_bytes"}
 
 _lib: Optional[C.CDLL] = None
 

@@ -11,22 +11,9 @@
 //   DDPM  {sqrt_ac, sqrt_1m_ac, sqrt_recip_ac, sqrt_recipm1_ac, post_c1, post_c2, exp(.5*post_logvar), t>0}
 //   DDIM  {sqrt_ac, sqrt_1m_ac, sqrt_recip_ac, sqrt_recipm1_ac, sqrt(ac_next), c, sigma, last(time_next<0)}
 #include "nd_common.h"
+#include "philox_normal.h"
 
 namespace {
-
-// four N(0,1) for quad `q` of sample `sample` at noise draw `step1` (0 = x_T, i+1 = i-th step)
-__device__ __forceinline__ f32x4 philox_normal4(uint64_t seed, uint32_t sample, uint32_t step1, uint32_t q) {
-    uint32_t c[4] = {q, sample, step1, 0u};
-    Philox::gen(c, (uint32_t)seed, (uint32_t)(seed >> 32));
-    const float k = 1.0f / 4294967296.0f;
-    const float u0 = ((float)c[0] + 0.5f) * k, u1 = ((float)c[1] + 0.5f) * k;
-    const float u2 = ((float)c[2] + 0.5f) * k, u3 = ((float)c[3] + 0.5f) * k;
-    const float r0 = sqrtf(-2.0f * logf(fminf(u0, 1.0f))), r1 = sqrtf(-2.0f * logf(fminf(u2, 1.0f)));
-    float s0, c0, s1, c1;
-    sincosf(6.283185307179586f * u1, &s0, &c0);
-    sincosf(6.283185307179586f * u3, &s1, &c1);
-    return (f32x4){r0 * c0, r0 * s0, r1 * c1, r1 * s1};
-}
 
 __global__ void begin_step_kernel(nd_sampler_state s) {
     const int st = *s.step;

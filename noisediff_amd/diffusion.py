@@ -3,7 +3,9 @@
 Same constructor, buffers, properties, ``.sample()`` and ``.forward()`` signatures as
 models/denoising_diffusion_pytorch.py:167-542, so ``Trainer.__init__`` / ``Trainer.test`` / ``Trainer.train``
 (models/trainer_diffusion.py:77-86,286-294,179-181) work unchanged.  The training entry points
-(``q_sample`` / ``p_losses`` / ``forward``) are plain differentiable PyTorch around ``self.model``.  ``sample`` accepts two extra
+(``q_sample`` / ``p_losses`` / ``forward``) are plain differentiable PyTorch around ``self.model``; after ``use_device_rng(seed)`` ``forward`` goes
+through ``hip_losses`` instead: timestep, noising and target in one launch from a counter-based Philox stream, the loss and its gradient on the HIP
+library (train.diffusion_noising / train.diffusion_loss).  ``sample`` accepts two extra
 keyword-only arguments for reproducibility (``noise=`` explicit draws for parity, ``seed=``
 for the device Philox stream); the reference call signature is a strict subset.
 
@@ -112,6 +114,12 @@ class GaussianDiffusion(nn.Module):
         self.auto_normalize = auto_normalize
         # rank shard bookkeeping for the device noise stream (see shard.py): global index of sample 0
         self.sample_offset = 0
+        # the training draws' device state {seed, first_sample, draw} (int64[3]) once use_device_rng() has switched forward() to hip_losses(); None: the
+        # PyTorch path.  first_sample plays sample_offset's part for training: a sample's timestep and noise depend on (seed, first_sample + row, draw)
+        # only, so rank r of `world` ranks with a per-rank batch B sets first_sample = r * B and lets draw (advanced by one per step) separate the steps
+        # -- or sets first_sample = r * B + step * world * B itself and keeps draw fixed.  Either way the shards of a global batch are disjoint.
+        self.train_rng: Optional[torch.Tensor] = None
+        self.last_t: Optional[torch.Tensor] = None      # hip_losses' timesteps of the latest step
         self._loop_cache: Dict[tuple, "_Loop"] = {}
         # p_sample_loop / ddim_sample switch THIS wrapper's sampler for one call (_as_sampler): a lock per instance, so that wrappers on other devices or
         # in other threads never wait for each other
@@ -267,6 +275,13 @@ class GaussianDiffusion(nn.Module):
     def __setstate__(self, state):
         super().__setstate__(state)
         self._sampler_switch = threading.RLock()
+        self.__dict__.setdefault("train_rng", None)     # (a wrapper pickled before the attribute existed)
+
+    def _apply(self, fn, *args, **kwargs):
+        super()._apply(fn, *args, **kwargs)
+        if self.train_rng is not None:                  # a plain attribute, not a buffer (the state dict stays the reference's): it follows .to() / .cuda() here
+            self.train_rng = fn(self.train_rng)
+        return self
 
     def release_graphs(self) -> None:
         """Destroy every captured step graph of this wrapper (they are rebuilt on demand)."""
@@ -406,8 +421,46 @@ class GaussianDiffusion(nn.Module):
             loss = loss + (model_out.mean(dim=(2, 3)) - target.mean(dim=(2, 3))).abs().mean()
         return loss
 
+    # ------------------------------------------------------------------ the same training step with its two ends on the HIP library (opt-in)
+    def use_device_rng(self, seed: Optional[int], first_sample: int = 0, draw: int = 0) -> "GaussianDiffusion":
+        """Switch ``forward`` to ``hip_losses``: timesteps, noise and offset noise come from the counter-based Philox stream keyed
+        (seed, first_sample + row, draw), held in ``train_rng`` (int64[3] on the wrapper's device) and advanced by one draw per step on the device --
+        a step is replayable from these three numbers, and a captured step draws anew on every replay.  ``use_device_rng(None)`` switches back to
+        the PyTorch path and torch's generator.  Returns ``self``."""
+        if seed is None:
+            self.train_rng = None
+            return self
+        seed = int(seed) & (2 ** 64 - 1)                # any 64-bit seed: stored as its two's-complement int64 (the kernel casts back)
+        self.train_rng = torch.tensor([seed - 2 ** 64 if seed >= 2 ** 63 else seed, int(first_sample), int(draw)], dtype=torch.int64, device=self.device)
+        return self
+
+    def hip_losses(self, img, condition, *, t=None, noise=None, offset=None):
+        """``forward`` with its ends on the HIP library: noising (one launch) -> ``self.model(x_t, t, condition)`` -> weighted loss (fp64 sums in a fixed
+        order; gradient in one pass).  ``t`` / ``noise`` / ``offset`` (B, C) given: used as they are; whatever is missing is drawn from ``train_rng``,
+        which then advances by one draw.  fp32 images with C % 4 == 0 on the GPU only: anything else raises."""
+        from . import train as TR
+        b, c, h, w = img.shape
+        assert h == self.image_size and w == self.image_size, f"height and width of image must be {self.image_size}"
+        strength = float(self.offset_noise_strength)
+        drawn = t is None or noise is None or (offset is None and strength > 0.)
+        rng = self.train_rng
+        if drawn and rng is None:
+            raise ValueError("hip_losses draws from train_rng: call use_device_rng(seed) first, or pass t, noise (and offset) explicitly")
+        t_out, x_t, target = TR.diffusion_noising(img, self.sqrt_alphas_cumprod, self.sqrt_one_minus_alphas_cumprod, objective=self.objective,
+                                                  auto_normalize=self.auto_normalize, offset_strength=strength, rng=rng, t=t, noise=noise, offset=offset)
+        self.last_t = t_out                                     # the step's timesteps, for logging and replay (a device tensor; no host read)
+        model_out = self.model(x_t, t_out, condition)
+        loss = TR.diffusion_loss(model_out, target, t_out, self.loss_weight, x0_term=self.objective == "pred_x0")
+        if drawn:
+            with TR._on(rng.device):
+                L.call("nd_diffusion_train_advance", rng.data_ptr(), TR._stream(rng.device))
+            torch.autograd.graph.increment_version(rng)         # (the kernel wrote through a raw pointer)
+        return loss
+
     def forward(self, img, condition, *args, **kwargs):
-        """Training loss for a batch: uniform random timesteps, then p_losses (:534-542)."""
+        """Training loss for a batch: uniform random timesteps, then p_losses (:534-542); after use_device_rng(): hip_losses."""
+        if self.train_rng is not None:
+            return self.hip_losses(img, condition, *args, **kwargs)
         b, _c, h, w = img.shape
         assert h == self.image_size and w == self.image_size, f"height and width of image must be {self.image_size}"
         t = torch.randint(0, self.num_timesteps, (b,), device=img.device).long()

@@ -22,6 +22,8 @@ gradient of token Linears / 1x1 convolutions on the library GEMM and takes their
 10^6 tokens that library GEMMs run at a tenth of HBM speed -- to nd_linear_wgrad_f32 (linear_wgrad.hip); ``LayerNormFunction``:
 nn.LayerNorm over token channels forward and backward (norm_train.hip).  ``attention_core`` / ``linear_attention_core`` / ``rms_norm``: the cores of
 Attention and LinearAttention and their RMSNorm, forward and backward (attn_train.hip).  Activations stay on PyTorch's own ROCm kernels.
+``diffusion_noising`` / ``diffusion_loss``: the two ends of ``GaussianDiffusion.forward`` around the network (diffusion_train.hip) -- timestep, noising and
+target in one launch from a counter-based Philox stream, the weighted loss in fp64 in a fixed order, its gradient in one pass.
 
 There is no fallback: a CPU tensor or a missing library raises.
 """
@@ -1254,7 +1256,7 @@ class Adam(torch.optim.Adam):
         if ent is not None:
             # load_state_dict (or anything else) replaced the state tensors: lay the table out again (compared by object, not by id() of a dict that
             # may have been freed and its id reused)
-            _, _, _, ms0, vs0, steps0 = ent
+            _, _, _, ms0, vs0, steps0, _ = ent
             for p, m0, v0, t0 in zip(ps, ms0, vs0, steps0):
                 st = self.state[p]
                 if st.get("exp_avg") is not m0 or st.get("exp_avg_sq") is not v0 or st.get("step") is not t0:
@@ -1292,7 +1294,10 @@ class Adam(torch.optim.Adam):
         per = int(L.load().nd_adam_chunk_elements())
         pairs = [(i, c) for i, p in enumerate(ps) for c in range((p.numel() + per - 1) // per)]
         chunks = torch.tensor(pairs, dtype=torch.int32).reshape(-1, 2).to(dev)
-        ent = self._nd_tables[key] = (items, chunks, len(pairs), ms, vs, steps)
+        # a capturable group keeps one pinned staging buffer for its first capture: pinned memory cannot be allocated while a stream captures, and the
+        # host allocator has a free block then only by luck (it hands a block back after a LATER allocation has seen its copy finished)
+        spare = [torch.empty(items.nbytes, dtype=torch.uint8).pin_memory()] if cap else []
+        ent = self._nd_tables[key] = (items, chunks, len(pairs), ms, vs, steps, spare)
         return ent
 
     def _nd_launch(self, group: dict, ps: list, ent: tuple, capturing: bool) -> None:
@@ -1304,7 +1309,7 @@ class Adam(torch.optim.Adam):
             # the learning rate is a launch argument: a captured step replays with the value it was captured with (the reference's CosineAnnealingLR
             # and its hand-written group['lr'] = ..., trainer_diffusion.py:95,104-105, do not reach a replayed graph) -- refuse a silent mismatch
             self._nd_captured_lr[id(group)] = lr
-        items, chunks, n_chunks, ms, vs, steps = ent
+        items, chunks, n_chunks, ms, vs, steps, spare = ent
         gs = [p.grad for p in ps]
         if not all(g.is_contiguous() and g.dtype == torch.float32 and not g.is_sparse for g in gs):
             gs = [g.contiguous() if not g.is_sparse and g.dtype == torch.float32 else None for g in gs]
@@ -1321,7 +1326,11 @@ class Adam(torch.optim.Adam):
             items["step_size"] = lr / (1.0 - beta1 ** ts)
             items["bias2_sqrt"] = np.sqrt(1.0 - beta2 ** ts)
         # pointers and step sizes of this step (a few KB): pinned + asynchronous, so the host keeps running ahead of the device
-        host_table = torch.from_numpy(items.view(np.uint8)).pin_memory()
+        if capturing and spare:
+            host_table = spare.pop()
+            host_table.copy_(torch.from_numpy(items.view(np.uint8)))
+        else:
+            host_table = torch.from_numpy(items.view(np.uint8)).pin_memory()
         table = host_table.to(dev, non_blocking=True)
         with _on(dev):
             if cap:
@@ -1359,3 +1368,114 @@ class Adam(torch.optim.Adam):
         for group, ps, ent in work:
             self._nd_launch(group, ps, ent, capturing)
         return loss
+
+
+# ---------------------------------------------------------------------------------------------------------------- the two ends of a diffusion training step
+def _check_ends(op: str, x: torch.Tensor, what: str) -> None:
+    _need_gpu(x)
+    if x.dim() != 4 or x.shape[1] % 4 != 0 or x.dtype != torch.float32:
+        raise ValueError(f"{op}: {what} {tuple(x.shape)} {x.dtype}: needs a 4-D fp32 tensor whose channel count is a multiple of 4 (there is no fallback)")
+
+
+def diffusion_noising(x0: torch.Tensor, sqrt_alphas_cumprod: torch.Tensor, sqrt_one_minus_alphas_cumprod: torch.Tensor, *, objective: str,
+                      auto_normalize: bool = False, offset_strength: float = 0.0, seed: int = 0, first_sample: int = 0, draw: int = 0,
+                      rng: Optional[torch.Tensor] = None, t: Optional[torch.Tensor] = None, noise: Optional[torch.Tensor] = None,
+                      offset: Optional[torch.Tensor] = None, return_draws: bool = False):
+    """``GaussianDiffusion.forward``'s timestep draw, ``normalize``, the offset noise, ``q_sample`` and the objective's target in ONE launch
+    (nd_diffusion_noising_f32): ``(t, x_t, target)``, the two images (B, C, H, W) in channels_last memory; with ``return_draws`` also the element noise
+    (before the offset is added) and the offset (B, C), so that a step can be replayed with explicit draws.  ``x0``: fp32, NCHW-contiguous or channels_last
+    (read as it lies), C % 4 == 0.  ``t`` / ``noise`` / ``offset`` given: used as they are -- the outputs are then bit for bit the reference's.  Otherwise
+    they come from the counter-based Philox stream keyed (seed, first_sample + row, draw): ``rng`` (int64[3] on the device: seed, first_sample, draw)
+    overrides the three scalars, so a captured graph draws anew on every replay.  Nothing here is differentiable: the outputs carry no gradient."""
+    _check_ends("diffusion_noising", x0, "x0")
+    B, C_, H, W = x0.shape
+    dev = x0.device
+    x0 = x0.detach()
+    if x0.is_contiguous():
+        last = 0
+    else:
+        x0, last = x0.contiguous(memory_format=torch.channels_last), 1
+    tabs = [sqrt_alphas_cumprod, sqrt_one_minus_alphas_cumprod]
+    if any(s.dtype != torch.float32 or s.device != dev or s.dim() != 1 or s.numel() != tabs[0].numel() for s in tabs):
+        raise ValueError("diffusion_noising: the two schedule tables must be fp32 vectors of one length on x0's device")
+    tabs = [s.detach().contiguous() for s in tabs]
+    p = L.DiffusionNoising()
+    keep = [x0] + tabs
+    if noise is not None:
+        if noise.shape != x0.shape:
+            raise ValueError(f"diffusion_noising: noise {tuple(noise.shape)} does not match x0 {tuple(x0.shape)}")
+        keep.append(_nhwc(noise.detach().to(dev)))
+        p.noise = keep[-1].data_ptr()
+    if offset is not None:
+        if tuple(offset.shape) != (B, C_):
+            raise ValueError(f"diffusion_noising: offset {tuple(offset.shape)} must be {(B, C_)}")
+        keep.append(offset.detach().to(dev, torch.float32).contiguous())
+        p.offset = keep[-1].data_ptr()
+    if t is not None:
+        if tuple(t.shape) != (B,):
+            raise ValueError(f"diffusion_noising: t {tuple(t.shape)} must be {(B,)}")
+        keep.append(t.detach().to(dev, torch.int64).contiguous())
+        p.t_in = keep[-1].data_ptr()
+    if rng is not None:
+        if rng.dtype != torch.int64 or rng.device != dev or rng.numel() != 3 or not rng.is_contiguous():
+            raise ValueError("diffusion_noising: rng must be a contiguous int64[3] tensor {seed, first_sample, draw} on x0's device")
+        p.rng = rng.data_ptr()
+    with _on(dev), torch.no_grad():
+        t_out = torch.empty(B, dtype=torch.int64, device=dev)
+        x_t = torch.empty((B, C_, H, W), dtype=torch.float32, device=dev, memory_format=torch.channels_last)
+        target = torch.empty_like(x_t, memory_format=torch.channels_last)
+        noise_out = torch.empty_like(x_t, memory_format=torch.channels_last) if return_draws else None
+        offset_out = _empty((B, C_), dev) if return_draws else None
+        p.x0, p.sqrt_alphas_cumprod, p.sqrt_one_minus_alphas_cumprod = x0.data_ptr(), tabs[0].data_ptr(), tabs[1].data_ptr()
+        p.t_out, p.x_t, p.target, p.noise_out, p.offset_out = t_out.data_ptr(), x_t.data_ptr(), target.data_ptr(), L.ptr(noise_out), L.ptr(offset_out)
+        p.seed, p.first_sample, p.draw, p.offset_strength = int(seed) & (2 ** 64 - 1), int(first_sample), int(draw), float(offset_strength)
+        p.B, p.C, p.H, p.W, p.T = B, C_, H, W, tabs[0].numel()
+        p.objective, p.auto_normalize, p.x0_channels_last = L.OBJECTIVES[objective], int(bool(auto_normalize)), last
+        L.call("nd_diffusion_noising_f32", C.byref(p), _stream(dev))
+    return (t_out, x_t, target, noise_out, offset_out) if return_draws else (t_out, x_t, target)
+
+
+class DiffusionLossFunction(torch.autograd.Function):
+    """``p_losses``' tail (:514-528): mean_b(mean_elems((out - target)^2) loss_weight[t_b]) [+ the mean-intensity term of pred_x0] on nd_diffusion_loss_f32
+    (fp64 sums in a fixed order) and nd_diffusion_loss_backward_f32 (one pass, the upstream gradient read on the device).  The workspace -- the slices'
+    partials and the signs the backward reads -- is a saved tensor allocated here, so a captured graph owns it."""
+
+    @staticmethod
+    def forward(ctx, model_out, target, t, loss_weight, x0_term):
+        mo, tg = _nhwc(model_out), _nhwc(target)
+        B, C_, H, W = mo.shape
+        dev = mo.device
+        t64, lw = t.to(dev, torch.int64).contiguous(), loss_weight.detach().to(dev, torch.float32).contiguous()
+        with _on(dev):
+            ws = torch.empty(int(L.call("nd_diffusion_loss_workspace_bytes", B, C_, H * W)), dtype=torch.uint8, device=dev)
+            loss = _empty((), dev)
+            L.call("nd_diffusion_loss_f32", mo.data_ptr(), tg.data_ptr(), t64.data_ptr(), lw.data_ptr(), B, C_, H * W, lw.numel(), int(x0_term),
+                   ws.data_ptr(), loss.data_ptr(), None, _stream(dev))
+        ctx.save_for_backward(mo, tg, t64, lw, ws)
+        ctx.x0_term = int(x0_term)
+        return loss
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_loss):
+        mo, tg, t64, lw, ws = ctx.saved_tensors
+        B, C_, H, W = mo.shape
+        dev = mo.device
+        g = grad_loss.to(dev, torch.float32).reshape(1).contiguous()
+        with _on(dev):
+            grad = torch.empty_like(mo, memory_format=torch.channels_last)
+            L.call("nd_diffusion_loss_backward_f32", mo.data_ptr(), tg.data_ptr(), t64.data_ptr(), lw.data_ptr(), g.data_ptr(), ws.data_ptr(), grad.data_ptr(),
+                   B, C_, H * W, lw.numel(), ctx.x0_term, _stream(dev))
+        return grad, None, None, None, None
+
+
+def diffusion_loss(model_out: torch.Tensor, target: torch.Tensor, t: torch.Tensor, loss_weight: torch.Tensor, x0_term: bool = False) -> torch.Tensor:
+    """The diffusion training loss of a batch on the HIP library, differentiable in ``model_out`` only: a ``target`` that requires grad, a CPU tensor, a
+    dtype other than fp32 or a channel count that is no multiple of 4 raises (with ``x0_term``: C a power of two up to 256)."""
+    _check_ends("diffusion_loss", model_out, "model_out")
+    _check_ends("diffusion_loss", target, "target")
+    if target.shape != model_out.shape or tuple(t.shape) != (model_out.shape[0],):
+        raise ValueError(f"diffusion_loss: model_out {tuple(model_out.shape)}, target {tuple(target.shape)}, t {tuple(t.shape)} do not belong together")
+    if target.requires_grad:
+        raise ValueError("diffusion_loss: no gradient is produced for target; detach it")
+    return DiffusionLossFunction.apply(model_out, target, t, loss_weight, bool(x0_term))

@@ -2,7 +2,8 @@
 """Training step of TrainableNoiseDiffNet(...).hip() as ONE captured graph (torch.cuda.CUDAGraph): forward + backward + Adam(capturable=True) --
 noisediff_amd.train.Adam (one launch + a counter launch; env ADAM=torch: torch.optim.Adam).
 The library's launches are queued on torch's current stream, so they are captured like any ATen kernel; replaying the graph removes the host side of the
-~300 autograd-function calls of a step (which bounds the small configurations in eager mode)."""
+~300 autograd-function calls of a step (which bounds the small configurations in eager mode).
+env ENDS=hip: gd.use_device_rng(1) -- timestep, noising, target, loss and loss gradient on the library too (diffusion_train.hip); REPLAYS=n: timed replays (8)."""
 import os, sys, time
 sys.path.insert(0, os.environ.get("ND_PKG_ROOT") or os.path.dirname(os.path.dirname(os.path.abspath(__file__))))   # ND_PKG_ROOT: another copy of the package (A/B against a saved state)
 import torch
@@ -15,6 +16,8 @@ for (B, S) in [(4, 256), (8, 128)]:
     img = synth.uniform(7, "img", (B, 4, S, S), -1.0, 1.0).to(dev)
     net = TrainableNoiseDiffNet(SimpleNamespace(dim=64)).to(dev).hip(True)
     gd = GaussianDiffusion(net, image_size=S, timesteps=1000, beta_schedule="sigmoid2", objective="pred_v").to(dev)
+    if os.environ.get("ENDS") == "hip":
+        gd.use_device_rng(1)
     opt = (torch.optim.Adam if os.environ.get("ADAM") == "torch" else HipAdam)(net.parameters(), lr=1e-4, capturable=True)
     def one():
         opt.zero_grad(set_to_none=True)
@@ -41,7 +44,8 @@ for (B, S) in [(4, 256), (8, 128)]:
     torch.cuda.synchronize()
     g.replay(); torch.cuda.synchronize()
     t0 = time.perf_counter()
-    for _ in range(8): g.replay()
+    n_rep = int(os.environ.get("REPLAYS", "8"))
+    for _ in range(n_rep): g.replay()
     torch.cuda.synchronize()
-    graphed = (time.perf_counter() - t0) / 8
+    graphed = (time.perf_counter() - t0) / n_rep
     print(f"B={B} {S}x{S}: eager {eager * 1e3:.2f} ms/step, one captured graph per step {graphed * 1e3:.2f} ms/step, loss {float(loss.detach()):.6f}", flush=True)
