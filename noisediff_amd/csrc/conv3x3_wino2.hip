@@ -201,7 +201,9 @@ __global__ __launch_bounds__(256, 1) void wino2_kernel(const Wino2Args a) {
     int par = 0;                                           // table of this tile; the next tile's is par ^ 1
     const unsigned* itab = tab;                            // pixel table of the item being staged
     // activations, like the weights, come through buffer loads (SGPR resource + scalar channel offset, 32-bit lane
-    // offset = pixel * stride + quad): cheap to issue, and a lane whose channels lie beyond the tensor reads zeros.
+    // offset = pixel * stride + quad): cheap to issue, and a lane whose channels lie beyond the tensor reads zeros.  So does a lane
+    // whose channel quad lies beyond cin in a ragged last chunk (2^31 added to its offset: out of range for any source, none wraps -- host check):
+    // the floats behind a pixel's channels -- the rest of a wider tensor -- are never read, let alone multiplied by the zero weights.
     // A K chunk never straddles the two concat sources (host check), so the source is wave-uniform per chunk.
     const long src_px = (long)a.d.B * sH * sW;
     const __amdgpu_buffer_rsrc_t rsrc0 = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(s.p0), 0, (int)(src_px * s.ld0 * 4), 0x00020000);
@@ -209,6 +211,7 @@ __global__ __launch_bounds__(256, 1) void wino2_kernel(const Wino2Args a) {
     const __amdgpu_buffer_rsrc_t rsrcm = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(MAP ? s.map : s.p0), 0, MAP ? (int)(src_px * 2 * Ctot * 4) : 0, 0x00020000);
     __amdgpu_buffer_rsrc_t irsrc = rsrc0;
     int isoff = 0, imoff = 0;                              // scalar byte offsets: channel base inside the source / the map
+    unsigned iqoff = 0;                                    // lane byte offset of this thread's channel quad in the chunk
     auto issue_begin = [&](int b_, int cb_, int par_, unsigned tilemask) {   // per chunk: channel quad of this thread
         itab = tab + (1 + par_) * STAGE_IT * 256;
         const bool sec = cb_ >= s.c0;                      // wave-uniform
@@ -229,6 +232,7 @@ __global__ __launch_bounds__(256, 1) void wino2_kernel(const Wino2Args a) {
         }
         if (MAP) imoff = cb_ * 4;
         okmask = cvalid ? tilemask : 0u;
+        iqoff = cvalid ? (unsigned)quad * 16u : 0x80000000u;
     };
     unsigned pix_r = 0, slot_r = 0;                        // table entries read one slice ahead of their use (W2_CLUMP)
     auto issue_pre = [&](int it) { pix_r = itab[it * 256]; };
@@ -236,7 +240,7 @@ __global__ __launch_bounds__(256, 1) void wino2_kernel(const Wino2Args a) {
     auto issue_one = [&](int it) {
         const unsigned pix = W2_CLUMP ? pix_r : itab[it * 256];
         // the scalar offsets are wave-uniform by construction; saying so keeps hipcc from wrapping each load in a waterfall loop
-        raw[it] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(irsrc, (unsigned)(__umul24(pix, ild4) + quad * 16),
+        raw[it] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(irsrc, (unsigned)(__umul24(pix, ild4) + iqoff),
                                                                                   __builtin_amdgcn_readfirstlane(isoff), 0));
         if (MAP) {                                         // the map has the conv's resolution (host: no upsample with MAP)
             const unsigned mo = (unsigned)(__umul24(pix, 2 * Ctot * 4) + quad * 16);
@@ -258,7 +262,7 @@ __global__ __launch_bounds__(256, 1) void wino2_kernel(const Wino2Args a) {
         if (AFF) {                                         // silu(affine(0)) != 0: the padding is applied after the activation
             const f32x4 zero = {0, 0, 0, 0};
             v = ((okmask >> it) & 1u) ? v : zero;
-        }   // otherwise out-of-image pixels were loaded as zeros (px_oob) and channels beyond cin meet zero weights
+        }   // otherwise out-of-image pixels (px_oob) and channel quads beyond cin (iqoff) were loaded as zeros
         const unsigned slot = (W2_CLUMP ? slot_r : tab[it * 256]) & 0xFFFFFu;
         nd_st4(reinterpret_cast<float*>(reinterpret_cast<char*>(dst) + slot), v);
     };
@@ -599,7 +603,8 @@ extern "C" int W2_ENTRY(const nd_conv3x3* d, void* stream) {
     {
         const long px = (long)d->B * (d->H >> (s.upsample ? 1 : 0)) * (d->W >> (s.upsample ? 1 : 0));
         const long widest = s.mode == ND_PRO_AFFINE_MAP_SILU ? 2L * (s.c0 + s.c1) : 0;
-        ND_REQUIRE(px * s.ld0 * 4 < (1L << 31) && px * s.ld1 * 4 < (1L << 31) && px * widest * 4 < (1L << 31), ND_E_SHAPE,
+        // (sources 64 KB below 2 GiB: pixel offset + channel offset + the 2^31 of an invalid channel quad stay below 2^32)
+        ND_REQUIRE(px * s.ld0 * 4 < (1L << 31) - 65536 && px * s.ld1 * 4 < (1L << 31) - 65536 && px * widest * 4 < (1L << 31), ND_E_SHAPE,
                    "nd_conv3x3_wino2: a source tensor of 2 GiB or more (use nd_conv3x3_wino_nhwc_f32)");
     }
     ND_REQUIRE(s.c1 == 0 || s.c0 % 32 == 0, ND_E_SHAPE,
