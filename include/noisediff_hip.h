@@ -818,6 +818,37 @@ int nd_adam_step_f32(const nd_adam_item* items_dev, int n_items, const int32_t* 
  * (item.step_size, item.bias2_sqrt are ignored).  Two launches. */
 int nd_adam_step_capturable_f32(const nd_adam_item* items_dev, int n_items, const int32_t* chunks_dev, int n_chunks, float lr, float beta1, float beta2,
                                 float eps, float weight_decay, void* stream);
+/* The capturable form with the learning rate read from device memory: lr = (double)*lr_dev, one float (PyTorch's tensor lr, which schedulers fill in
+ * place), read in the kernel -- a captured step follows a changed rate without a new capture.  A null lr_dev is ND_E_BADARG. */
+int nd_adam_step_capturable_lr_f32(const nd_adam_item* items_dev, int n_items, const int32_t* chunks_dev, int n_chunks, const float* lr_dev, float beta1,
+                                   float beta2, float eps, float weight_decay, void* stream);
+
+/* ------------------------------------------------------------------ shadow-model (EMA) update of a training run (ema.hip)
+ * ema_pytorch's EMA.update, the reference's self.ema.update (models/trainer_diffusion.py:63-69,191), for all tensors in one pass, decided on the
+ * device: no host read, so a captured training step can hold it.  `items_dev`: n_items records in DEVICE memory, one per (shadow, online) tensor
+ * pair; vec4 != 0 promises that both are 16-byte aligned; no_ema != 0: the pair is copied where the others are averaged.  `chunks_dev`: n_chunks
+ * pairs (item index, chunk index) of int32, one per nd_ema_chunk_elements elements of a tensor (the last chunk of a tensor may be short).
+ * State in device memory: `step_dev` one int64, `initted_dev` one byte (a torch.bool), `plan_dev` 8 bytes owned by the caller, written by every
+ * call: {int32 action; float weight}, action 0 skip, 1 copy, 2 lerp, 3 copy then lerp.  With s = *step_dev before the call (it is s + 1 after, in
+ * every case):
+ *   s % update_every != 0        skip: no tensor is touched;
+ *   s <= update_after_step       copy: ema = src for every item;
+ *   *initted_dev == 0            copy, *initted_dev = 1, then the lerp below (a no-op in value);
+ *   otherwise                    lerp with weight = 1 - decay, e = s + 1 - update_after_step - 1,
+ *                                decay = e <= 0 ? 0 : clamp(1 - (1 + e / inv_gamma)^-power, min_value, beta), in fp64, weight rounded to fp32 once;
+ *                                per element, no contraction: w < 0.5 ? ema + w (src - ema) : src - (src - ema)(1 - w)   (torch.lerp's form).
+ * Two launches (plan, apply); no reductions, no atomics: bitwise repeatable.  Null tables or state pointers, counts <= 0, beta outside [0, 1],
+ * update_every < 1 or inv_gamma <= 0 return ND_E_BADARG and launch nothing.  noisediff_amd.train.EMA is the host side. */
+typedef struct nd_ema_item {
+    float*       ema;
+    const float* src;
+    int64_t      n;
+    int32_t      vec4, no_ema;
+} nd_ema_item;
+int nd_ema_chunk_elements(void);
+int nd_ema_update_f32(const nd_ema_item* items_dev, int n_items, const int32_t* chunks_dev, int n_chunks, int64_t* step_dev, uint8_t* initted_dev,
+                      void* plan_dev, double beta, int64_t update_after_step, int64_t update_every, double inv_gamma, double power, double min_value,
+                      void* stream);
 
 /* ------------------------------------------------------------------ the two ends of a diffusion training step (diffusion_train.hip)
  * GaussianDiffusion.forward / p_losses (models/denoising_diffusion_pytorch.py:481-542) around the network: timestep, noising and target in

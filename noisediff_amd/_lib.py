@@ -36,6 +36,10 @@ class AdamItem(C.Structure):
                 ("vec4", C.c_int32), ("reserved", C.c_int32), ("step", fptr)]
 
 
+class EmaItem(C.Structure):
+    _fields_ = [("ema", fptr), ("src", fptr), ("n", C.c_int64), ("vec4", C.c_int32), ("no_ema", C.c_int32)]
+
+
 class PackItem(C.Structure):
     _fields_ = [("w", fptr), ("packed", fptr), ("cin", C.c_int32), ("cout", C.c_int32), ("transposed", C.c_int32), ("reserved", C.c_int32)]
 
@@ -156,6 +160,9 @@ SIGNATURES = {
     "nd_adam_chunk_elements": (i32, []),
     "nd_adam_step_f32": (i32, [vp, i32, vp, i32, f32, f32, f32, f32, vp]),
     "nd_adam_step_capturable_f32": (i32, [vp, i32, vp, i32, f32, f32, f32, f32, f32, vp]),
+    "nd_adam_step_capturable_lr_f32": (i32, [vp, i32, vp, i32, vp, f32, f32, f32, f32, vp]),
+    "nd_ema_chunk_elements": (i32, []),
+    "nd_ema_update_f32": (i32, [vp, i32, vp, i32, vp, vp, vp, f64, i64, i64, f64, f64, f64, vp]),
     "nd_diffusion_noising_f32": (i32, [C.POINTER(DiffusionNoising), vp]),
     "nd_diffusion_train_advance": (i32, [vp, vp]),
     "nd_diffusion_loss_slice_elements": (i32, []),
@@ -251,7 +258,7 @@ SIGNATURES = {
     "nd_raw_diffusion_batch_f32": (i32, [vp, i32, i32, i32, vp, f32, f32, vp, vp, vp, vp, i32, i32, i32, vp]),
 }
 
-_UNCHECKED = {"nd_version", "nd_last_error", "nd_stream_device", "nd_conv3x3_wgrad_form", "nd_adam_chunk_elements", "nd_conv7x7_c4_wgrad_workspace_floats", "nd_conv3x3_stat_slots", "nd_conv3x3_tiling_id", "nd_pack_conv3x3_weight_floats",
+_UNCHECKED = {"nd_version", "nd_last_error", "nd_stream_device", "nd_conv3x3_wgrad_form", "nd_adam_chunk_elements", "nd_ema_chunk_elements", "nd_conv7x7_c4_wgrad_workspace_floats", "nd_conv3x3_stat_slots", "nd_conv3x3_tiling_id", "nd_pack_conv3x3_weight_floats",
               "nd_pack_pointwise_weight_floats", "nd_linear_attention_workspace_floats", "nd_conv3x3_wino_stat_slots", "nd_conv3x3_wino4_stat_slots",
               "nd_pack_conv3x3_wino_weight_floats", "nd_pack_conv3x3_wino4_weight_floats", "nd_conv3x3_wino4_splitk_plan", "nd_conv3x3_wino4_16_splitk_plan", "nd_conv3x3_wino4_splitk_workspace_floats", "nd_token_sum_workspace_floats", "nd_cond_step_lds_bytes", "nd_conv3x3_wgrad_workspace_floats",
               "nd_groupnorm_train_workspace_floats", "nd_linear_wgrad_workspace_floats",

@@ -13,6 +13,8 @@ The reference binds its two plug-in interfaces by *import name* (SURVEY 8b):
     (``args.phase != 'train'``) and the reference's own differentiable class for training -- its 3x3 convolutions routed
     through the HIP library forward and backward (noisediff_amd/train.py; ND_TRAIN_ACCEL=0 keeps them on PyTorch) -- whose
     checkpoints load into the HIP network unchanged (same state dict).
+  * answers ``ema_pytorch`` -- which models/trainer_diffusion.py imports for its shadow model -- with a module whose ``EMA`` is
+    ``noisediff_amd.train.EMA``, but only where no other finder has the name: an installed package wins.
 ``main()`` then runs the script with ``runpy`` as ``__main__`` (same ``sys.argv``, script directory first on ``sys.path``),
 which is what ``python test_diffusion.py ...`` does.  Nothing is written to the reference tree.
 """
@@ -28,6 +30,7 @@ import types
 
 DIFFUSION_MODULE = "models.denoising_diffusion_pytorch"
 ARCH_MODULES = ("models.archs.Diffusion_arch", "models.archs.others_arch")
+EMA_MODULE = "ema_pytorch"
 HIP_CLASSES = ("NoiseDiffNet", "UNet_PosEmbV2", "UNet_PosEmbV2_NoPosition", "UNet_PosEmbV2_CameraCond")
 
 
@@ -59,6 +62,16 @@ class _DiffusionLoader(importlib.abc.Loader):
         module.__doc__ = "noisediff_amd overlay of models/denoising_diffusion_pytorch.py (see noisediff_amd/dropin.py)"
 
 
+class _EmaLoader(importlib.abc.Loader):
+    def create_module(self, spec):
+        return None
+
+    def exec_module(self, module):
+        from noisediff_amd import train
+        module.EMA = train.EMA
+        module.__doc__ = "noisediff_amd stand-in for the ema_pytorch package, which is not installed (see noisediff_amd/dropin.py)"
+
+
 class _ArchLoader(importlib.abc.Loader):
     def __init__(self, inner):
         self.inner = inner
@@ -86,6 +99,11 @@ class OverlayFinder(importlib.abc.MetaPathFinder):
                 if spec is not None and spec.loader is not None:
                     spec.loader = _ArchLoader(spec.loader)
                     return spec
+        if fullname == EMA_MODULE:
+            for finder in sys.meta_path:
+                if finder is not self and hasattr(finder, "find_spec") and finder.find_spec(fullname, path, target) is not None:
+                    return None                      # installed: the import system goes on to that finder
+            return importlib.util.spec_from_loader(fullname, _EmaLoader(), origin="noisediff_amd.dropin")
         return None
 
 

@@ -619,7 +619,7 @@ def release_packs(device: Optional[torch.device] = None) -> None:
 def invalidate_packs(device: Optional[torch.device] = None) -> None:
     """Mark every cached weight packing (of one device, or of all) stale: the next forward repacks them in one launch per kind.  Needed after writes the
     parameters' version counters do not see -- ``p.data.copy_ / lerp_ / normal_`` (ema_pytorch's shadow-model update, SID_arch's initialisation) -- and after
-    replays of a captured whole-step graph (see _PackCache)."""
+    replays of a captured whole-step graph (see _PackCache).  ``train.EMA.update()`` bumps the shadow tensors' versions itself and needs no call."""
     for idx, cache in _PACK_CACHES.items():
         if device is None or device.index == idx:
             cache.invalidate()
@@ -1212,7 +1212,9 @@ class Adam(torch.optim.Adam):
     between the two classes (``--resume_optim``); the same update in fp32 up to the rounding of one fused pass.  What the kernel does not do is refused:
     amsgrad, maximize, differentiable, sparse gradients, parameters that are not fp32 on a GPU.  ``capturable=True`` (PyTorch's flag): the step counters live on
     the device and nothing is computed on the host per step (nd_adam_step_capturable_f32) -- the form a training step captured as ONE CUDA graph needs
-    (tools/train_graph_bench.py); run one step before the capture."""
+    (tools/train_graph_bench.py); run one step before the capture.  With ``capturable=True`` the group's ``lr`` may be a one-element fp32 tensor on the
+    parameters' device (PyTorch's tensor lr, which its schedulers ``fill_`` in place): the kernel reads it there (nd_adam_step_capturable_lr_f32), so a
+    captured step follows ``set_lr`` / a scheduler without a new capture."""
 
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0, **kw):
         for k in ("amsgrad", "maximize", "differentiable", "fused"):
@@ -1225,7 +1227,7 @@ class Adam(torch.optim.Adam):
     def _nd_init_caches(self) -> None:
         """Everything the instance keeps besides torch.optim.Adam's own defaults / state / param_groups."""
         self._nd_tables: Dict[tuple, tuple] = {}     # (group index, capturable, parameter data_ptrs) -> the group's laid-out table (_nd_table)
-        self._nd_captured_lr: Dict[int, float] = {}  # id(group) -> the learning rate its captured step was recorded with
+        self._nd_captured_lr: Dict[int, object] = {} # id(group) -> the learning rate its captured step was recorded with: a float, or THE tensor it reads
         self._nd_captured: list = []                 # tables of captured steps: a replay reads them, so they live as long as the optimizer
         self._nd_keep = None                         # tables of the last step: alive until the next one (the launch is asynchronous)
 
@@ -1238,12 +1240,28 @@ class Adam(torch.optim.Adam):
 
     def check_captured_lr(self) -> None:
         """Call before replaying a captured training step: a captured ``capturable=True`` step carries the learning rate it was captured with (a launch
-        argument).  Raises if a scheduler or the caller has changed ``group['lr']`` since -- re-capture the step then."""
+        argument).  Raises if a scheduler or the caller has changed ``group['lr']`` since -- re-capture the step then.  A step captured with
+        a tensor lr reads that tensor at every replay: it passes whatever the value, while the group still holds that same tensor."""
         for group in self.param_groups:
-            lr0 = self._nd_captured_lr.get(id(group))
-            if lr0 is not None and float(group["lr"]) != lr0:
-                raise RuntimeError(f"noisediff_amd.train.Adam: the captured step was recorded with lr={lr0:g}, the group now has lr={float(group['lr']):g}: "
+            lr0, now = self._nd_captured_lr.get(id(group)), group["lr"]
+            if lr0 is None:
+                continue
+            if isinstance(lr0, torch.Tensor):
+                if now is not lr0:
+                    raise RuntimeError("noisediff_amd.train.Adam: the captured step reads its learning rate from the tensor the group held at the capture; "
+                                       "group['lr'] has been replaced since and a replay would ignore it: use set_lr() (fill_ in place), or capture the step again")
+            elif isinstance(now, torch.Tensor) or float(now) != lr0:
+                raise RuntimeError(f"noisediff_amd.train.Adam: the captured step was recorded with lr={lr0:g}, the group now has lr={float(now):g}: "
                                    "a replay would ignore the change; capture the step again")
+
+    def set_lr(self, value, group: int = 0) -> None:
+        """``param_groups[group]['lr'] = value`` (the reference's hand-written schedule, models/trainer_denoising.py:185-188) in the form a captured step
+        follows: ``fill_`` on a tensor lr, plain assignment otherwise."""
+        g = self.param_groups[group]
+        if isinstance(g["lr"], torch.Tensor):
+            g["lr"].fill_(float(value))
+        else:
+            g["lr"] = value
 
     def _nd_table(self, gi: int, group: dict, ps: list, capturing: bool) -> tuple:
         """Validate group ``gi``'s parameters ``ps`` (those with a gradient) and lay out what does not change from step to step: (nd_adam_item records
@@ -1304,11 +1322,17 @@ class Adam(torch.optim.Adam):
         """One launch for group's parameters ``ps`` over its table ``ent`` (_nd_table) with this step's gradient pointers and step sizes."""
         dev, cap = ps[0].device, bool(group.get("capturable"))
         beta1, beta2 = group["betas"]
-        lr = float(group["lr"])
+        lr_dev = group["lr"] if cap and isinstance(group["lr"], torch.Tensor) else None
+        if lr_dev is not None:
+            if lr_dev.numel() != 1 or lr_dev.dtype != torch.float32 or lr_dev.device != dev:
+                raise NotImplementedError("noisediff_amd.train.Adam(capturable=True): a tensor lr must be one fp32 element on the parameters' device")
+        else:
+            lr = float(group["lr"])                                      # (capturable=False reads a tensor lr on the host, as torch does)
         if cap and capturing:
-            # the learning rate is a launch argument: a captured step replays with the value it was captured with (the reference's CosineAnnealingLR
-            # and its hand-written group['lr'] = ..., trainer_diffusion.py:95,104-105, do not reach a replayed graph) -- refuse a silent mismatch
-            self._nd_captured_lr[id(group)] = lr
+            # a float learning rate is a launch argument: a captured step replays with the value it was captured with (the reference's CosineAnnealingLR
+            # and its hand-written group['lr'] = ..., trainer_diffusion.py:95,104-105, do not reach a replayed graph) -- refuse a silent mismatch.  A
+            # tensor lr is read by the kernel at every replay: what must not change is WHICH tensor the group holds.
+            self._nd_captured_lr[id(group)] = lr if lr_dev is None else lr_dev
         items, chunks, n_chunks, ms, vs, steps, spare = ent
         gs = [p.grad for p in ps]
         if not all(g.is_contiguous() and g.dtype == torch.float32 and not g.is_sparse for g in gs):
@@ -1333,14 +1357,17 @@ class Adam(torch.optim.Adam):
             host_table = torch.from_numpy(items.view(np.uint8)).pin_memory()
         table = host_table.to(dev, non_blocking=True)
         with _on(dev):
-            if cap:
+            if lr_dev is not None:
+                L.call("nd_adam_step_capturable_lr_f32", table.data_ptr(), len(ps), chunks.data_ptr(), n_chunks, lr_dev.data_ptr(), float(beta1), float(beta2),
+                       float(group["eps"]), float(group["weight_decay"]), _stream(dev))
+            elif cap:
                 L.call("nd_adam_step_capturable_f32", table.data_ptr(), len(ps), chunks.data_ptr(), n_chunks, lr, float(beta1), float(beta2),
                        float(group["eps"]), float(group["weight_decay"]), _stream(dev))
             else:
                 L.call("nd_adam_step_f32", table.data_ptr(), len(ps), chunks.data_ptr(), n_chunks, float(beta1), float(beta2), float(group["eps"]),
                        float(group["weight_decay"]), _stream(dev))
         if capturing:                                                    # a captured step replays with these tables: they live as long as the optimizer
-            self._nd_captured.append((table, host_table, gs))
+            self._nd_captured.append((table, host_table, gs, lr_dev))
         self._nd_keep = (table, gs)
         # the kernel wrote through raw pointers: tell autograd (and the packing caches, which compare version counters) that these tensors changed
         torch.autograd.graph.increment_version(ps)
@@ -1368,6 +1395,223 @@ class Adam(torch.optim.Adam):
         for group, ps, ent in work:
             self._nd_launch(group, ps, ent, capturing)
         return loss
+
+
+# ---------------------------------------------------------------------------------------------------------------- the shadow model of a training run
+EMA_SKIP, EMA_COPY, EMA_LERP, EMA_COPY_LERP = 0, 1, 2, 3          # the `action` of an update's plan (ema.hip)
+
+
+def ema_plan(s: int, initted: bool, beta: float, update_after_step: int, update_every: int, inv_gamma: float = 1.0, power: float = 2.0 / 3.0,
+             min_value: float = 0.0) -> tuple:
+    """What the ``update()`` call that finds the step counter at ``s`` does: ``(action, weight)`` -- ema_pytorch's rule as ema.hip's plan kernel computes
+    it, here on the host (the CPU path of ``EMA`` and the tests): fp64 arithmetic, the weight ``1 - decay`` rounded to fp32 once.  EMA_COPY_LERP sets
+    ``initted``; the counter becomes ``s + 1`` in every case."""
+    if s % update_every != 0:
+        return EMA_SKIP, 0.0
+    if s <= update_after_step:
+        return EMA_COPY, 0.0
+    e = max(s + 1 - update_after_step - 1, 0)                         # (the package reads the counter after its increment)
+    decay = 0.0 if e <= 0 else min(max(1.0 - (1.0 + e / inv_gamma) ** -power, min_value), beta)
+    return (EMA_LERP if initted else EMA_COPY_LERP), float(np.float32(1.0 - decay))
+
+
+class EMA(nn.Module):
+    """``ema_pytorch.EMA`` as the reference uses it (models/trainer_diffusion.py:63-69,191; ``ema_model`` is what ``save_networks('ema', ...)`` ships):
+    ``.ema_model`` (a deep copy of ``model``, ``requires_grad_(False)``), ``.online_model``, ``.update()``, ``.to()``, ``forward`` -> ``ema_model``,
+    ``copy_params_from_model_to_ema()``, ``get_current_decay()``, buffers ``step`` (int64[1]) and ``initted`` (bool[1]); state-dict keys ``initted``,
+    ``step``, ``online_model.*``, ``ema_model.*``.  Keywords of the package that are not in the signature raise NotImplementedError.
+
+    ``update()`` on GPU tensors is ONE call of nd_ema_update_f32 (ema.hip) over all fp32 parameters and fp32 buffers, matched by name: the step
+    counter, the warm-up flag and the decision (skip / copy / lerp and its weight) live in device memory, so there is no host read -- the package's
+    ``self.step.item()`` is a sync per training step -- and the call can be captured into the training step's graph: run one ``update()`` before the
+    capture (the tables are laid out then; captured tables live as long as the object).  Non-floating tensors are left alone, as the package leaves
+    them; fp16 / bf16 (anything floating but fp32), non-contiguous tensors and tensors on more than one device raise NotImplementedError.  CPU modules
+    run the same schedule with ``copy_`` / ``lerp_``.  The decay is computed in fp64 (the package: fp32 tensor arithmetic).
+
+    Every eager ``update()`` on GPU tensors bumps the version counters of the shadow tensors, so the next forward of ``ema_model`` repacks its weights
+    without ``invalidate_packs()``.  REPLAYS of a captured graph bump nothing -- the rule of ``_PackCache``'s docstring holds unchanged: packings made
+    while capturing are repacked on every eager use; after replays, call ``train.invalidate_packs()`` before an eager forward of ``ema_model`` whose
+    packings were made eagerly.
+
+    ``last_plan()`` -> (action, weight) of the last call and ``get_current_decay()`` read the device: for tests and logs."""
+
+    def __init__(self, model: nn.Module, ema_model: Optional[nn.Module] = None, beta: float = 0.9999, update_after_step: int = 100, update_every: int = 10,
+                 inv_gamma: float = 1.0, power: float = 2.0 / 3.0, min_value: float = 0.0, param_or_buffer_names_no_ema=(), **kw):
+        for k in kw:
+            raise NotImplementedError(f"noisediff_amd.train.EMA: {k} is not built (use ema_pytorch.EMA)")
+        if not (0.0 <= beta <= 1.0) or update_every < 1 or not inv_gamma > 0.0:
+            raise ValueError(f"noisediff_amd.train.EMA: beta={beta} must lie in [0, 1], update_every={update_every} must be at least 1, inv_gamma={inv_gamma} positive")
+        super().__init__()
+        import copy
+        self.online_model = model
+        self.ema_model = copy.deepcopy(model) if ema_model is None else ema_model
+        self.ema_model.requires_grad_(False)
+        self.beta, self.update_after_step, self.update_every = float(beta), int(update_after_step), int(update_every)
+        self.inv_gamma, self.power, self.min_value = float(inv_gamma), float(power), float(min_value)
+        self.param_or_buffer_names_no_ema = set(param_or_buffer_names_no_ema)
+        self.register_buffer("initted", torch.tensor([False]))
+        self.register_buffer("step", torch.tensor([0], dtype=torch.int64))
+        self._nd_init_caches()
+
+    def _nd_init_caches(self) -> None:
+        self._nd_tables: Dict[tuple, tuple] = {}     # data_ptrs of the (shadow, online) pairs -> the laid-out tables (_nd_table)
+        self._nd_captured: list = []                 # tables of captured updates: a replay reads them, so they live as long as the object
+        self._nd_last = None                         # (action, weight) of the last update on the CPU, or the device plan record of the last one on a GPU
+        self._nd_kept = None                         # (pairs, holders) of the last walk over both module trees (_nd_pairs)
+
+    def __getstate__(self):
+        """Deep copies and pickles carry their own counters (the buffers) and none of the tables, which hold the original's addresses."""
+        return {k: v for k, v in self.__dict__.items() if not k.startswith("_nd_")}
+
+    def __setstate__(self, state) -> None:
+        super().__setstate__(state)
+        self._nd_init_caches()
+
+    def forward(self, *args, **kwargs):
+        return self.ema_model(*args, **kwargs)
+
+    @staticmethod
+    def _nd_holders(model: nn.Module) -> dict:
+        """name -> (the module's own ``_parameters`` / ``_buffers`` dict, key, tensor) for every parameter and buffer, each tensor once (as
+        ``named_parameters`` / ``named_buffers`` name them)."""
+        out, seen = {}, set()
+        for prefix, mod in model.named_modules():
+            for store in (mod._parameters, mod._buffers):
+                for k, t in store.items():
+                    if t is not None and id(t) not in seen:
+                        seen.add(id(t))
+                        out[(prefix + "." if prefix else "") + k] = (store, k, t)
+        return out
+
+    def _nd_pairs(self) -> list:
+        """(name, shadow tensor, online tensor) of every floating parameter and buffer, matched by name.  Walking both module trees costs more than
+        the whole pass, so the list is kept and only checked per call: every tensor must still be the one its module holds (``.to()`` replaces
+        buffers, an assignment replaces a parameter); modules ADDED after the first update() are seen after ``copy_params_from_model_to_ema()``,
+        ``load_state_dict()`` or ``.to()``, which read the trees again."""
+        kept = self._nd_kept
+        if kept is not None and all(store.get(k) is t for store, k, t in kept[1]):
+            return kept[0]
+        src = self._nd_holders(self.online_model)
+        pairs, holders = [], []
+        for name, (store, k, e) in self._nd_holders(self.ema_model).items():
+            if name not in src:
+                raise RuntimeError(f"noisediff_amd.train.EMA: the online model has no tensor named {name}")
+            if e.is_floating_point() or e.is_complex():
+                pairs.append((name, e, src[name][2]))
+                holders += [(store, k, e), src[name]]
+        self._nd_kept = (pairs, holders)
+        return pairs
+
+    def _apply(self, fn, *args, **kwargs):
+        self._nd_kept = None
+        return super()._apply(fn, *args, **kwargs)
+
+    def load_state_dict(self, *args, **kwargs):
+        self._nd_kept = None
+        return super().load_state_dict(*args, **kwargs)
+
+    def _nd_check(self, pairs: list) -> torch.device:
+        """The one device of the pairs and the two counters; refuses what the pass does not do."""
+        devices = {self.step.device, self.initted.device}
+        for name, e, s in pairs:
+            if e.dtype != torch.float32 or s.dtype != torch.float32:
+                raise NotImplementedError(f"noisediff_amd.train.EMA averages fp32 tensors: {name} is {e.dtype} / {s.dtype}")
+            if e.shape != s.shape or not e.is_contiguous() or not s.is_contiguous():
+                raise NotImplementedError(f"noisediff_amd.train.EMA: {name} must be contiguous and of one shape in both models")
+            devices |= {e.device, s.device}
+        if len(devices) != 1:
+            raise NotImplementedError(f"noisediff_amd.train.EMA: both models and the counters must be on one device (call .to(device)), found {sorted(map(str, devices))}")
+        if self.step.dtype != torch.int64 or self.initted.dtype != torch.bool or self.step.numel() != 1 or self.initted.numel() != 1:
+            raise NotImplementedError("noisediff_amd.train.EMA: step must be one int64 and initted one bool")
+        return devices.pop()
+
+    def _nd_table(self, pairs: list, dev: torch.device, capturing: bool) -> tuple:
+        """Laid out once per set of tensors (keyed on their addresses): (nd_ema_item table and chunk table on the device, number of items and chunks,
+        the plan record, the shadow tensors, the online tensors -- held so that the addresses stay theirs)."""
+        key = (self.step.data_ptr(), self.initted.data_ptr()) + tuple(t.data_ptr() for _, e, s in pairs for t in (e, s))
+        ent = self._nd_tables.get(key)
+        if ent is not None:
+            return ent
+        if capturing:
+            raise RuntimeError("noisediff_amd.train.EMA: run update() once with the same tensors before the capture (the tables are laid out on the first call)")
+        self._nd_check(pairs)
+        if len(self._nd_tables) > 16:
+            self._nd_tables.clear()
+        items = np.zeros(len(pairs), dtype=np.dtype(L.EmaItem))          # nd_ema_item
+        items["ema"] = [e.data_ptr() for _, e, _ in pairs]
+        items["src"] = [s.data_ptr() for _, _, s in pairs]
+        items["n"] = [e.numel() for _, e, _ in pairs]
+        items["vec4"] = ((items["ema"] | items["src"]) & 15) == 0
+        items["no_ema"] = [name in self.param_or_buffer_names_no_ema for name, _, _ in pairs]
+        per = int(L.load().nd_ema_chunk_elements())
+        chunk_pairs = [(i, c) for i, (_, e, _) in enumerate(pairs) for c in range((e.numel() + per - 1) // per)]
+        # the addresses do not change from call to call (Adam's gradient pointers do): both tables are uploaded here, once (synchronous copies of a
+        # few KB), and a captured update copies nothing -- no staging memory is needed while a stream captures
+        table = torch.from_numpy(items.view(np.uint8)).to(dev)
+        chunks = torch.tensor(chunk_pairs, dtype=torch.int32).reshape(-1, 2).to(dev)
+        plan = torch.zeros(2, dtype=torch.int32, device=dev)             # {int32 action; float weight}
+        ent = self._nd_tables[key] = (table, chunks, len(pairs), len(chunk_pairs), plan, [e for _, e, _ in pairs], [s for _, _, s in pairs])
+        return ent
+
+    @torch.no_grad()
+    def update(self) -> None:
+        pairs = self._nd_pairs()
+        if not pairs:
+            self.step += 1
+            return
+        if not pairs[0][1].is_cuda:
+            return self._update_cpu(pairs)
+        capturing = torch.cuda.is_current_stream_capturing()
+        dev = pairs[0][1].device
+        table, chunks, n_items, n_chunks, plan, emas, _ = ent = self._nd_table(pairs, dev, capturing)
+        with _on(dev):
+            L.call("nd_ema_update_f32", table.data_ptr(), n_items, chunks.data_ptr(), n_chunks, self.step.data_ptr(), self.initted.data_ptr(), plan.data_ptr(),
+                   self.beta, self.update_after_step, self.update_every, self.inv_gamma, self.power, self.min_value, _stream(dev))
+        if capturing:
+            self._nd_captured.append(ent)
+        self._nd_last = plan
+        # the kernel wrote through raw pointers: tell autograd and the packing caches (which compare version counters) that the shadow changed
+        torch.autograd.graph.increment_version(emas)
+        torch.autograd.graph.increment_version([self.step, self.initted])
+
+    def _update_cpu(self, pairs: list) -> None:
+        """The same schedule on CPU modules: the plan on the host, ``copy_`` / ``lerp_`` per tensor."""
+        if self._nd_check(pairs).type != "cpu":
+            raise NotImplementedError("noisediff_amd.train.EMA: both models and the counters must be on one device")
+        action, weight = ema_plan(int(self.step), bool(self.initted), self.beta, self.update_after_step, self.update_every, self.inv_gamma, self.power,
+                                  self.min_value)
+        self.step += 1
+        self._nd_last = (action, weight)
+        if action == EMA_SKIP:
+            return
+        if action == EMA_COPY_LERP:
+            self.initted.fill_(True)
+        for name, e, s in pairs:
+            if action != EMA_LERP or name in self.param_or_buffer_names_no_ema:
+                e.copy_(s)
+            if action != EMA_COPY and name not in self.param_or_buffer_names_no_ema:
+                e.lerp_(s, weight)
+
+    @torch.no_grad()
+    def copy_params_from_model_to_ema(self) -> None:
+        self._nd_kept = None
+        for _, e, s in self._nd_pairs():
+            e.copy_(s)
+
+    def get_current_decay(self) -> float:
+        """The decay the next averaging call would use (the package's method: it reads ``step``, on a GPU a sync -- for logging only)."""
+        e = max(int(self.step) - self.update_after_step - 1, 0)
+        return 0.0 if e <= 0 else min(max(1.0 - (1.0 + e / self.inv_gamma) ** -self.power, self.min_value), self.beta)
+
+    def last_plan(self) -> tuple:
+        """(action, weight) of the last ``update()``: EMA_SKIP / EMA_COPY / EMA_LERP / EMA_COPY_LERP and the lerp weight ``1 - decay`` (0 where nothing
+        is averaged).  On a GPU this reads the device's plan record: for tests and logs."""
+        if self._nd_last is None:
+            raise RuntimeError("noisediff_amd.train.EMA.last_plan: no update() yet")
+        if isinstance(self._nd_last, tuple):
+            return self._nd_last
+        rec = self._nd_last.cpu()
+        return int(rec[0]), float(rec[1:].view(torch.float32)[0])
 
 
 # ---------------------------------------------------------------------------------------------------------------- the two ends of a diffusion training step
