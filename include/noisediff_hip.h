@@ -908,6 +908,29 @@ int nd_diffusion_loss_f32(const float* model_out, const float* target, const int
 int nd_diffusion_loss_backward_f32(const float* model_out, const float* target, const int64_t* t, const float* loss_weight, const float* g,
                                    const void* workspace, float* grad_out, int B, int C, int HW, int T, int x0_term, void* stream);
 
+/* ------------------------------------------------------------------ the end of a denoiser training step (denoise_loss.hip)
+ * models/trainer_denoising.py:66-76, 225-235: loss = mse_loss(out, target) * lambda_mse + l1_loss(out, target) * lambda_l1.
+ * `out`: the network output, [B][C][HW] (ND_LAYOUT_NCHW, 1 <= C <= 16) or [B][HW][C] (ND_LAYOUT_NHWC, C = 4 only: LSID's head as it leaves the
+ * 1x1 convolution); `target`: always [B][C][HW].  Anything else: ND_E_SHAPE.  d = fl(out - target) in fp32; |d| and d * d are formed and summed in
+ * fp64 in an order defined over pixels and channels, not over memory: a sample's HW pixels are cut into slices of
+ * nd_denoise_loss_slice_pixels() pixels, one workgroup each, whose two partials go to `workspace`
+ * (nd_denoise_loss_workspace_bytes(B, C, HW) bytes, 16-byte aligned); a second launch of one workgroup adds a sample's slices in slice order and
+ * the samples in a fixed tree.  TWO launches, no atomics.  Every output has the same bits for either layout of `out`, and a sample's terms depend on
+ * neither the batch size nor the sample's row.
+ *   terms [3]             = { (float)(lambda_mse S2 / N + lambda_l1 S1 / N), (float)(S1 / N), (float)(S2 / N) },  S1 = sum |d|, S2 = sum d^2, N = B C HW
+ *   sample_terms [B][2]   = { (float)(S1_b / (C HW)), (float)(S2_b / (C HW)) }   (optional)
+ * A negative or non-finite lambda, or both zero: ND_E_BADARG.  out, target, workspace (and grad below) 16-byte aligned: ND_E_ALIGN.  B <= 65535. */
+enum nd_layout { ND_LAYOUT_NCHW = 0, ND_LAYOUT_NHWC = 1 };
+int nd_denoise_loss_slice_pixels(void);
+int64_t nd_denoise_loss_workspace_bytes(int B, int C, int HW);
+int nd_denoise_loss_f32(const float* out, int out_layout, const float* target, int B, int C, int HW, double lambda_l1, double lambda_mse,
+                        void* workspace, float* terms, float* sample_terms, void* stream);
+/* grad = (float)(g lambda_l1 / N * sign(d) + g 2 lambda_mse / N * d), formed in fp64 and rounded once, sign(0) = 0; written in `out`'s layout, one
+ * pass.  g: the upstream gradient, one float in DEVICE memory (no host read).  With lambda_mse = 0 every element is (float)(g / N) * sign(d)
+ * exactly.  No gradient for target. */
+int nd_denoise_loss_backward_f32(const float* out, int out_layout, const float* target, const float* g, float* grad, int B, int C, int HW,
+                                 double lambda_l1, double lambda_mse, void* stream);
+
 /* ------------------------------------------------------------------ HIP graph helpers */
 int nd_stream_create(void** stream);
 int nd_stream_destroy(void* stream);

@@ -17,6 +17,7 @@ LIB_PATH = os.path.join(HERE, "libnoisediff_hip.so")
 PRO_NONE, PRO_AFFINE_SILU, PRO_AFFINE_MAP_SILU, PRO_LAYERNORM, PRO_SILU, PRO_LEAKY, PRO_LEAKY_SECOND, PRO_AFFINE_GENMAP_SILU = 0, 1, 2, 3, 4, 5, 6, 7
 ACT_NONE, ACT_GELU, ACT_SILU = 0, 1, 2
 OBJECTIVES = {"pred_noise": 0, "pred_x0": 1, "pred_v": 2}
+LAYOUT_NCHW, LAYOUT_NHWC = 0, 1                           # enum nd_layout
 
 fptr = C.c_void_p   # device pointers travel as integers
 
@@ -169,6 +170,10 @@ SIGNATURES = {
     "nd_diffusion_loss_workspace_bytes": (i64, [i32, i32, i32]),
     "nd_diffusion_loss_f32": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, i32, vp, vp, vp, vp]),
     "nd_diffusion_loss_backward_f32": (i32, [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp]),
+    "nd_denoise_loss_slice_pixels": (i32, []),
+    "nd_denoise_loss_workspace_bytes": (i64, [i32, i32, i32]),
+    "nd_denoise_loss_f32": (i32, [vp, i32, vp, i32, i32, i32, f64, f64, vp, vp, vp, vp]),
+    "nd_denoise_loss_backward_f32": (i32, [vp, i32, vp, vp, vp, i32, i32, i32, f64, f64, vp]),
     "nd_groupnorm_finalize_f32": (i32, [vp, vp, i32, vp, vp, vp, i32, vp, i32, i32, i32, f32, vp]),
     "nd_groupnorm_finalize_train_f32": (i32, [vp, vp, i32, vp, vp, vp, i32, vp, vp, i32, i32, i32, f32, vp]),
     "nd_layernorm_stats_f32": (i32, [vp, i32, vp, vp, i32, i32, i32, f32, vp]),
@@ -266,7 +271,8 @@ _UNCHECKED = {"nd_version", "nd_last_error", "nd_stream_device", "nd_conv3x3_wgr
               "nd_convt2x2_wgrad_workspace_floats", "nd_image_quality_workspace_bytes", "nd_illum_scale_workspace_bytes",
               "nd_histogram_chunk_elements", "nd_histogram_workspace_bytes", "nd_patch_std_mean_workspace_bytes", "nd_level_table_bytes",
               "nd_theil_sen_workspace_bytes", "nd_attention_backward_workspace_floats", "nd_linear_attention_backward_workspace_floats",
-              "nd_rmsnorm_backward_workspace_floats", "nd_diffusion_loss_slice_elements", "nd_diffusion_loss_workspace_bytes"}
+              "nd_rmsnorm_backward_workspace_floats", "nd_diffusion_loss_slice_elements", "nd_diffusion_loss_workspace_bytes",
+              "nd_denoise_loss_slice_pixels", "nd_denoise_loss_workspace_bytes"}
 
 _lib: Optional[C.CDLL] = None
 

@@ -23,6 +23,7 @@
 // workgroup each; a slice's partial depends on neither B nor the sample's row, and the final stage adds the slices of a sample in slice order, so a
 // sample's loss bits do not depend on its batch.  No atomics anywhere; every store is a vector store.
 #include "nd_common.h"
+#include "block_sum.h"
 #include "philox_normal.h"
 
 #pragma clang fp contract(off)
@@ -77,20 +78,6 @@ __global__ __launch_bounds__(256) void noising_kernel(nd_diffusion_noising p, in
 }
 
 __global__ void advance_draw_kernel(int64_t* rng) { rng[2] = rng[2] + 1; }
-
-__device__ __forceinline__ double wave_sum(double v) {             // all 64 lanes, fixed order
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, ND_WAVE);
-    return v;
-}
-// sum over the 256 threads of a workgroup, valid in thread 0; `lds`: 4 doubles
-__device__ __forceinline__ double block_sum(double v, double* lds) {
-    v = wave_sum(v);
-    __syncthreads();                                               // (lds may still be read from a previous call)
-    if ((threadIdx.x & 63) == 0) lds[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return ((lds[0] + lds[1]) + lds[2]) + lds[3];
-}
 
 struct loss_ws {                                                   // the workspace's three regions, in this order (each a multiple of 16 bytes from the start)
     float* sign;         // [B][C]       sign of mean_hw(out) - mean_hw(target) (x0_term; read by the backward pass)

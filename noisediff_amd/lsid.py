@@ -158,9 +158,10 @@ def _sizes(H: int, W: int) -> List[Tuple[int, int]]:
     return out
 
 
-def lsid_forward_hip(P: Dict[str, torch.Tensor], x: torch.Tensor, saved: Dict[str, torch.Tensor], run: _Launcher) -> torch.Tensor:
+def lsid_forward_hip(P: Dict[str, torch.Tensor], x: torch.Tensor, saved: Dict[str, torch.Tensor], run: _Launcher, head_nhwc: bool = False) -> torch.Tensor:
     """LSID.forward (SID_arch.py:105-175) as launches of ``run`` on the parameter table ``P``: the (B, 4, H, W) output; fills ``saved`` with the raw
-    tensors lsid_train's backward reads."""
+    tensors lsid_train's backward reads.  ``head_nhwc``: stop at the 1x1 head's own output (B, H, W, 4), without the transpose to NCHW (the fused loss
+    of lsid_train reads it as it lies)."""
     B, _, H, W = x.shape
     sizes = _sizes(H, W)
     xn = x.detach().to(torch.float32).contiguous()
@@ -200,6 +201,12 @@ def lsid_forward_hip(P: Dict[str, torch.Tensor], x: torch.Tensor, saved: Dict[st
     y = run.empty(B, H, W, 4)
     w10 = P["conv10.weight"].reshape(4, cin).contiguous()
     run.pointwise(run.src(cur, mode=L.PRO_LEAKY), run.pack_pw(w10, cin, 4), P["conv10.bias"], y, B, H * W, W, cin, 4, 4)
+    return y if head_nhwc else head_to_nchw(run, y)
+
+
+def head_to_nchw(run: _Launcher, y: torch.Tensor) -> torch.Tensor:
+    """The network's (B, 4, H, W) output from the head's (B, H, W, 4)."""
+    B, H, W, _ = y.shape
     out = run.empty(B, 4, H, W)
     run.launch("nd_nhwc_to_nchw_f32", y.data_ptr(), out.data_ptr(), B, 4, H, W)
     return out

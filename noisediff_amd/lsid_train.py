@@ -3,8 +3,12 @@
 
     net = noisediff_amd.TrainableLSID().cuda().hip()
     opt = noisediff_amd.train.Adam(net.parameters(), lr=1e-4)
-    loss = torch.nn.functional.l1_loss(net(noisy), clean); loss.backward(); opt.step()
+    loss = net.loss(noisy, clean); loss.backward(); opt.step()        # (l1=, mse=: the trainer's --lambda_l1 / --lambda_mse)
     noisediff_amd.LSID(None).load_state_dict(net.state_dict())        # the HIP inference path takes the trained weights as they are
+
+``net.loss`` is the network and the trainer's loss (mse * lambda_mse + l1 * lambda_l1, trainer_denoising.py:225-235) as ONE Function,
+``_LsidLossFunction``: the forward stops at the 1x1 head's NHWC output, the loss kernel (denoise_loss.hip) reads it there and its backward writes the
+head's gradient in that layout.  ``net(noisy)`` followed by any PyTorch loss keeps working: it pays the two layout passes and ATen's loss kernels.
 
 Parameters are registered under the reference's names and shapes (spec.lsid_param_spec) with its init, so ``state_dict()`` loads strictly into
 ``noisediff_amd.LSID`` and into the reference class.  Without ``.hip()`` the forward is plain differentiable PyTorch (CPU or GPU): the restatement
@@ -36,8 +40,8 @@ from torch import nn
 from torch.autograd.function import once_differentiable
 
 from . import _lib as L
-from . import synth
-from .lsid import _Launcher, _sizes, lsid_forward_hip
+from . import synth, train
+from .lsid import _Launcher, _sizes, head_to_nchw, lsid_forward_hip
 from .spec import LSID_STAGES, lsid_param_spec
 
 SLOPE = 0.2
@@ -82,16 +86,23 @@ def convt2x2_dgrad(run: _Launcher, w: torch.Tensor, d_up: torch.Tensor, ld_up: i
 
 
 def _lsid_hip_backward(P: Dict[str, torch.Tensor], saved: Dict[str, torch.Tensor], grad_out: torch.Tensor, run: _Launcher) -> Dict[str, torch.Tensor]:
-    """Weight and bias gradients of every parameter from the raw tensors of the forward, in reverse launch order."""
+    """Weight and bias gradients of every parameter from the gradient of the (B, 4, H, W) output: one layout pass, then the backward from the head."""
+    B, H, W, _ = saved["x8"].shape
+    g = grad_out.detach().to(torch.float32).contiguous()
+    run.keep.append(g)
+    dy = run.empty(B, H, W, 4)
+    L.call("nd_nchw_to_nhwc_f32", g.data_ptr(), dy.data_ptr(), B, 4, H, W, run.st)
+    return _lsid_hip_backward_from_head(P, saved, dy, run)
+
+
+def _lsid_hip_backward_from_head(P: Dict[str, torch.Tensor], saved: Dict[str, torch.Tensor], dy: torch.Tensor, run: _Launcher) -> Dict[str, torch.Tensor]:
+    """Weight and bias gradients of every parameter from the raw tensors of the forward and ``dy`` (B, H, W, 4), the gradient of the 1x1 head's own
+    output, in reverse launch order."""
     lib = run.lib
     x8 = saved["x8"]
     B, H, W, _ = x8.shape
     sizes = _sizes(H, W)
     G: Dict[str, torch.Tensor] = {}
-    g = grad_out.detach().to(torch.float32).contiguous()
-    run.keep.append(g)
-    dy = run.empty(B, H, W, 4)
-    L.call("nd_nchw_to_nhwc_f32", g.data_ptr(), dy.data_ptr(), B, 4, H, W, run.st)
 
     def ws(n: int) -> torch.Tensor:
         return run.empty(int(n))
@@ -185,6 +196,53 @@ class _LsidFunction(torch.autograd.Function):
         return (None,) + tuple(G[n] if need else None for n, need in zip(PARAM_NAMES, ctx.needs_input_grad[1:]))
 
 
+class _LsidLossFunction(torch.autograd.Function):
+    """The network and the trainer's loss as one Function: the forward stops at the 1x1 head's NHWC output, nd_denoise_loss_f32 reads it against the NCHW
+    ``clean``, and the backward has nd_denoise_loss_backward_f32 write the head's gradient where _lsid_hip_backward_from_head reads it -- no layout pass
+    in either direction.  Inputs (x, clean, l1, mse, want_output, *parameters in PARAM_NAMES order); outputs (loss, terms [3], sample terms [B, 2],
+    the (B, 4, H, W) output or None), only the loss differentiable."""
+
+    @staticmethod
+    def forward(ctx, x, clean, l1, mse, want_output, *params):
+        P = dict(zip(PARAM_NAMES, (p.detach() for p in params)))
+        run = _Launcher(x.device, WINO4_FORWARD)
+        saved: Dict[str, torch.Tensor] = {}
+        with torch.cuda.device(x.device):
+            y = lsid_forward_hip(P, x, saved, run, head_nhwc=True)
+            terms, sample, ws = train._denoise_loss_launch(y, L.LAYOUT_NHWC, clean, l1, mse)
+            out = head_to_nchw(run, y) if want_output else None
+        ctx.saved, ctx.head, ctx.lambdas = saved, (y, clean, ws), (l1, mse)      # (ws: the launch's workspace lives as long as the step's graph node)
+        ctx.save_for_backward(*params)
+        ctx.mark_non_differentiable(*(t for t in (terms, sample, out) if t is not None))
+        ctx.set_materialize_grads(False)                     # (no zero tensors -- fill launches -- for the outputs nobody differentiates)
+        return terms[0], terms, sample, out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_loss, *unused):
+        if grad_loss is None:
+            return (None,) * (5 + len(PARAM_NAMES))
+        params = ctx.saved_tensors
+        P = dict(zip(PARAM_NAMES, (p.detach() for p in params)))
+        y, clean, _ws = ctx.head
+        run = _Launcher(y.device, WINO4_DGRAD)
+        with torch.cuda.device(y.device):
+            dy = train._denoise_loss_grad(y, L.LAYOUT_NHWC, clean, grad_loss, *ctx.lambdas)
+            G = _lsid_hip_backward_from_head(P, ctx.saved, dy, run)
+        ctx.saved = ctx.head = None
+        return (None,) * 5 + tuple(G[n] if need else None for n, need in zip(PARAM_NAMES, ctx.needs_input_grad[5:]))
+
+
+def denoise_lr(epoch: int, max_iter: int, base_lr: float) -> float:
+    """The trainer's step schedule (models/trainer_denoising.py:185-188) for epoch ``epoch`` of ``max_iter``: the base rate, half of it after
+    ``max_iter // 2``, 1e-5 after ``int(0.8 * max_iter)``.  Feed it to ``train.Adam.set_lr``: with a tensor lr a captured step follows it."""
+    if epoch > int(max_iter * 0.8):
+        return 1e-5
+    if epoch > max_iter // 2:
+        return base_lr / 2.
+    return base_lr
+
+
 # --------------------------------------------------------------------------------------------------------- the module
 class TrainableLSID(nn.Module):
     """``TrainableLSID(args=None)``: the reference's ``LSID(args)`` for training (4 input channels; ``args`` is accepted and unused, as there).
@@ -209,10 +267,8 @@ class TrainableLSID(nn.Module):
     def _table(self) -> Dict[str, torch.Tensor]:
         return {n: getattr(self._modules[n.rsplit(".", 1)[0]], n.rsplit(".", 1)[1]) for n in PARAM_NAMES}
 
-    def forward(self, x: torch.Tensor) -> torch.Tensor:
-        P = self._table()
-        if not self._hip:
-            return lsid_forward_torch(P, x)
+    def _check_hip_input(self, P: Dict[str, torch.Tensor], x: torch.Tensor) -> bool:
+        """What the HIP path takes; True when the pass is differentiated (grad mode on and a parameter requires grad)."""
         if x.device.type != "cuda" or any(p.device != x.device for p in P.values()):
             raise L.HipError(f"TrainableLSID.hip() runs on the HIP library only: the input and every parameter must be on one GPU (input on {x.device})")
         if x.dim() != 4 or x.shape[1] != 4:
@@ -222,14 +278,61 @@ class TrainableLSID(nn.Module):
                              "pass an input that does not require grad, or use TrainableLSID without .hip()")
         if any(p.dtype != torch.float32 for p in P.values()):
             raise ValueError("TrainableLSID.hip() trains fp32 parameters")
-        if not (torch.is_grad_enabled() and any(p.requires_grad for p in P.values())):
+        return torch.is_grad_enabled() and any(p.requires_grad for p in P.values())
+
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        P = self._table()
+        if not self._hip:
+            return lsid_forward_torch(P, x)
+        if not self._check_hip_input(P, x):
             with torch.no_grad():
                 return _LsidFunction.forward(_NoCtx(), x, *[P[n] for n in PARAM_NAMES])
         return _LsidFunction.apply(x, *[P[n] for n in PARAM_NAMES])
+
+    def loss(self, noisy: torch.Tensor, clean: torch.Tensor, l1: float = 1.0, mse: float = 0.0, *, details: bool = False, return_output: bool = False):
+        """The trainer's loss of a batch (models/trainer_denoising.py:220-235): ``mse * F.mse_loss(net(noisy), clean) + l1 * F.l1_loss(net(noisy), clean)``.
+        With ``.hip()`` the network and the loss are ONE autograd Function (``_LsidLossFunction``): the loss kernel reads the head's NHWC output and its
+        backward writes the head's gradient, in fp64 sums of a fixed order (train.denoise_loss's contract).  ``clean``: (B, 4, H, W) fp32, contiguous, on
+        the input's device, no gradient.  Returns the loss; with ``details`` then a dict of detached tensors for the log line (``l1``, ``mse``: the
+        unweighted terms; ``sample_l1``, ``sample_mse``: (B,)); with ``return_output`` then the detached (B, 4, H, W) output."""
+        l1, mse = float(l1), float(mse)
+        train._check_lambdas("TrainableLSID.loss", l1, mse)
+        P = self._table()
+        if not self._hip:
+            out = lsid_forward_torch(P, noisy)
+            loss = mse * F.mse_loss(out, clean) + l1 * F.l1_loss(out, clean)
+            info = None
+            if details:
+                d = (out - clean).detach().flatten(1)
+                info = {"l1": d.abs().mean(), "mse": (d * d).mean(), "sample_l1": d.abs().mean(1), "sample_mse": (d * d).mean(1)}
+            out = out.detach()
+        else:
+            differentiated = self._check_hip_input(P, noisy)
+            train._need_gpu(clean)
+            if tuple(clean.shape) != tuple(noisy.shape) or clean.device != noisy.device or clean.dtype != torch.float32 or not clean.is_contiguous():
+                raise ValueError(f"TrainableLSID.loss: clean {tuple(clean.shape)} {clean.dtype} must be a contiguous fp32 tensor of the input's shape "
+                                 f"{tuple(noisy.shape)} on its device")
+            if clean.requires_grad:
+                raise ValueError("TrainableLSID.loss: no gradient is produced for clean; detach it")
+            args = (noisy, clean, l1, mse, bool(return_output), *[P[n] for n in PARAM_NAMES])
+            if differentiated:
+                loss, terms, sample, out = _LsidLossFunction.apply(*args)
+            else:
+                with torch.no_grad():
+                    loss, terms, sample, out = _LsidLossFunction.forward(_NoCtx(), *args)
+            info = train._loss_details(terms, sample) if details else None
+        res = (loss,) + ((info,) if details else ()) + ((out,) if return_output else ())
+        return res[0] if len(res) == 1 else res
 
 
 class _NoCtx:
     """Stands in for the autograd context of a forward nobody differentiates (under torch.no_grad / inference)."""
 
     def save_for_backward(self, *a):
+        pass
+
+    def mark_non_differentiable(self, *a):
+        pass
+
+    def set_materialize_grads(self, value):
         pass

@@ -24,6 +24,7 @@ nn.LayerNorm over token channels forward and backward (norm_train.hip).  ``atten
 Attention and LinearAttention and their RMSNorm, forward and backward (attn_train.hip).  Activations stay on PyTorch's own ROCm kernels.
 ``diffusion_noising`` / ``diffusion_loss``: the two ends of ``GaussianDiffusion.forward`` around the network (diffusion_train.hip) -- timestep, noising and
 target in one launch from a counter-based Philox stream, the weighted loss in fp64 in a fixed order, its gradient in one pass.
+``denoise_loss``: the denoiser trainer's mse * lambda_mse + l1 * lambda_l1 the same way (denoise_loss.hip); ``lsid_train`` fuses it with LSID's head.
 
 There is no fallback: a CPU tensor or a missing library raises.
 """
@@ -1723,3 +1724,84 @@ def diffusion_loss(model_out: torch.Tensor, target: torch.Tensor, t: torch.Tenso
     if target.requires_grad:
         raise ValueError("diffusion_loss: no gradient is produced for target; detach it")
     return DiffusionLossFunction.apply(model_out, target, t, loss_weight, bool(x0_term))
+
+
+# ---------------------------------------------------------------------------------------------------------------- the end of a denoiser training step
+def _check_lambdas(op: str, l1: float, mse: float) -> None:
+    if not (0.0 <= l1 < float("inf") and 0.0 <= mse < float("inf")) or (l1 == 0.0 and mse == 0.0):
+        raise ValueError(f"{op}: l1={l1} and mse={mse} must be finite, not negative and not both zero")
+
+
+def _denoise_loss_launch(out: torch.Tensor, layout: int, target: torch.Tensor, l1: float, mse: float):
+    """nd_denoise_loss_f32 on ``out`` ((B, C, H, W) for LAYOUT_NCHW, (B, H, W, 4) for LAYOUT_NHWC) against the NCHW ``target``: (terms [3], sample terms
+    [B, 2], the workspace), all allocated here on the current stream -- the caller keeps the workspace for as long as the launch may be replayed."""
+    B, C_, H, W = target.shape
+    dev = target.device
+    with _on(dev):
+        ws = torch.empty(int(L.call("nd_denoise_loss_workspace_bytes", B, C_, H * W)), dtype=torch.uint8, device=dev)
+        terms, sample = _empty((3,), dev), _empty((B, 2), dev)
+        L.call("nd_denoise_loss_f32", out.data_ptr(), layout, target.data_ptr(), B, C_, H * W, l1, mse, ws.data_ptr(), terms.data_ptr(), sample.data_ptr(),
+               _stream(dev))
+    return terms, sample, ws
+
+
+def _denoise_loss_grad(out: torch.Tensor, layout: int, target: torch.Tensor, grad_loss: torch.Tensor, l1: float, mse: float) -> torch.Tensor:
+    """nd_denoise_loss_backward_f32: the gradient of the loss with respect to ``out``, in ``out``'s layout; ``grad_loss`` is read on the device."""
+    B, C_, H, W = target.shape
+    dev = target.device
+    g = grad_loss.to(dev, torch.float32).reshape(1).contiguous()
+    with _on(dev):
+        grad = torch.empty_like(out)
+        L.call("nd_denoise_loss_backward_f32", out.data_ptr(), layout, target.data_ptr(), g.data_ptr(), grad.data_ptr(), B, C_, H * W, l1, mse, _stream(dev))
+    return grad
+
+
+def _loss_details(terms: torch.Tensor, sample: torch.Tensor) -> Dict[str, torch.Tensor]:
+    """The log line's tensors (models/trainer_denoising.py:225-235 logs both terms on every step): views of the kernel's outputs, on the device."""
+    return {"l1": terms[1], "mse": terms[2], "sample_l1": sample[:, 0], "sample_mse": sample[:, 1]}
+
+
+class DenoiseLossFunction(torch.autograd.Function):
+    """``mse * F.mse_loss(output, target) + l1 * F.l1_loss(output, target)`` on nd_denoise_loss_f32 (fp64 sums in a fixed order) and
+    nd_denoise_loss_backward_f32 (one pass, the upstream gradient read on the device).  Returns (loss, terms [3], sample terms [B, 2]); only the loss is
+    differentiable.  The workspace is allocated here on the current stream and saved, so a captured graph owns it."""
+
+    @staticmethod
+    def forward(ctx, output, target, l1, mse):
+        terms, sample, ws = _denoise_loss_launch(output, L.LAYOUT_NCHW, target, l1, mse)
+        ctx.save_for_backward(output, target, ws)
+        ctx.lambdas = (l1, mse)
+        ctx.mark_non_differentiable(terms, sample)
+        ctx.set_materialize_grads(False)                     # (no zero tensors -- two fill launches -- for the outputs nobody differentiates)
+        return terms[0], terms, sample
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_loss, *unused):
+        if grad_loss is None:
+            return None, None, None, None
+        output, target, _ws = ctx.saved_tensors
+        return _denoise_loss_grad(output, L.LAYOUT_NCHW, target, grad_loss, *ctx.lambdas), None, None, None
+
+
+def _check_denoise_pair(op: str, output: torch.Tensor, target: torch.Tensor) -> None:
+    for what, x in (("output", output), ("target", target)):
+        _need_gpu(x)
+        if x.dim() != 4 or x.dtype != torch.float32 or not x.is_contiguous():
+            raise ValueError(f"{op}: {what} {tuple(x.shape)} {x.dtype}: needs a contiguous 4-D (NCHW) fp32 tensor (there is no fallback)")
+    if target.shape != output.shape or target.device != output.device:
+        raise ValueError(f"{op}: output {tuple(output.shape)} on {output.device} and target {tuple(target.shape)} on {target.device} do not belong together")
+    if target.requires_grad:
+        raise ValueError(f"{op}: no gradient is produced for target; detach it")
+
+
+def denoise_loss(output: torch.Tensor, target: torch.Tensor, l1: float = 1.0, mse: float = 0.0, *, details: bool = False):
+    """The denoiser's training loss (models/trainer_denoising.py:66-76, 225-235: ``--loss_l1`` / ``--loss_mse`` weighted by ``--lambda_l1`` /
+    ``--lambda_mse``) of a batch on the HIP library: ``mse * mean((output - target)^2) + l1 * mean|output - target|``, differentiable in ``output`` only.
+    Both tensors NCHW-contiguous fp32 on one GPU, 1 to 16 channels; a CPU tensor raises HipError.  ``details``: also a dict of non-differentiable device
+    tensors -- ``l1``, ``mse`` (the unweighted terms) and ``sample_l1``, ``sample_mse`` (B,), whose bits do not depend on the batch."""
+    _check_denoise_pair("denoise_loss", output, target)
+    l1, mse = float(l1), float(mse)
+    _check_lambdas("denoise_loss", l1, mse)
+    loss, terms, sample = DenoiseLossFunction.apply(output, target.detach(), l1, mse)
+    return (loss, _loss_details(terms, sample)) if details else loss

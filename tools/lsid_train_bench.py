@@ -3,6 +3,7 @@
 
     hip_eager_ms      TrainableLSID(...).hip(), forward + L1 + backward + train.Adam, launched eagerly
     hip_graph_ms      the same step captured once into a torch.cuda.graph (train.Adam(capturable=True)) and replayed
+    hip_graph_loss_ms the captured step with net.loss(noisy, clean) -- network and L1 loss as one Function -- in place of F.l1_loss(net(noisy), clean)
     torch_ms          TrainableLSID without .hip() (PyTorch's own ROCm kernels) + torch.optim.Adam on the same GPU
     hip_vs_torch      torch_ms / hip_graph_ms (> 1: the library path is faster)
 
@@ -51,35 +52,38 @@ def main() -> None:
     x = synth.uniform(21, "bench.x", (B, 4, S, S), 0.0, 1.0).to(dev)
     y = synth.uniform(21, "bench.y", (B, 4, S, S), 0.0, 1.0).to(dev)
 
-    def stepper(net, opt):
+    def stepper(net, opt, fused=False):
         def step():
             opt.zero_grad(set_to_none=True)
-            loss = F.l1_loss(net(x), y)
+            loss = net.loss(x, y) if fused else F.l1_loss(net(x), y)
             loss.backward()
             opt.step()
             return loss
         return step
 
+    def captured_ms(fused: bool) -> float:
+        """The step captured by torch's recipe (warm-up steps on a side stream, then the capture), replayed."""
+        net = TrainableLSID().to(dev).hip()
+        opt = train.Adam(net.parameters(), lr=1e-4, capturable=True)
+        step = stepper(net, opt, fused)
+        s = torch.cuda.Stream()
+        s.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(s):
+            for _ in range(2):
+                step()
+        torch.cuda.current_stream().wait_stream(s)
+        torch.cuda.synchronize()
+        g = torch.cuda.CUDAGraph()
+        opt.zero_grad(set_to_none=True)
+        with torch.cuda.graph(g, capture_error_mode="relaxed"):    # (train.Adam stages its pointer table through pinned host memory)
+            (net.loss(x, y) if fused else F.l1_loss(net(x), y)).backward()
+            opt.step()
+        return _time(g.replay, args.steps, args.warmup)
+
     from noisediff_amd import lsid_train
     out = {"workload": f"LSID train step, B={B}, {S}x{S}, L1, Adam", "steps": args.steps, "warmup": args.warmup, "wino4_forward": lsid_train.WINO4_FORWARD}
-    # the captured step: torch's recipe (warm-up steps on a side stream, then the capture)
-    net = TrainableLSID().to(dev).hip()
-    opt = train.Adam(net.parameters(), lr=1e-4, capturable=True)
-    step = stepper(net, opt)
-    s = torch.cuda.Stream()
-    s.wait_stream(torch.cuda.current_stream())
-    with torch.cuda.stream(s):
-        for _ in range(2):
-            step()
-    torch.cuda.current_stream().wait_stream(s)
-    torch.cuda.synchronize()
-    g = torch.cuda.CUDAGraph()
-    opt.zero_grad(set_to_none=True)
-    with torch.cuda.graph(g, capture_error_mode="relaxed"):        # (train.Adam stages its pointer table through pinned host memory)
-        F.l1_loss(net(x), y).backward()
-        opt.step()
-    out["hip_graph_ms"] = _time(g.replay, args.steps, args.warmup)
-    del g
+    out["hip_graph_ms"] = captured_ms(False)
+    out["hip_graph_loss_ms"] = captured_ms(True)
 
     net = TrainableLSID().to(dev).hip()
     out["hip_eager_ms"] = _time(stepper(net, train.Adam(net.parameters(), lr=1e-4)), args.steps, args.warmup)
