@@ -305,7 +305,6 @@ Tiling choose_tiling(int B, int H, int W, int cout) {
     return cand[best];
 }
 
-static inline int device_cus() { return nd_device_cus(); }
 
 template <int TW, int MB, int NB, int MODE>
 void launch_mode(const ConvArgs& a, hipStream_t st) {
@@ -317,7 +316,7 @@ void launch_mode(const ConvArgs& a, hipStream_t st) {
         if (force > 0) per_cu = force;
         per_cu_cache.store(per_cu, std::memory_order_relaxed);
     }
-    const long resident = (long)device_cus() * per_cu;
+    const long resident = (long)nd_device_cus() * per_cu;
     const dim3 grid((unsigned)(a.total_wg < resident ? a.total_wg : resident)), block(256);
     hipLaunchKernelGGL((conv3x3_kernel<TW, MB, NB, MODE>), grid, block, 0, st, a);
 }

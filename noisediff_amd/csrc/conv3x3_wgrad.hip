@@ -298,28 +298,27 @@ struct WwArgs {
     int lk0, lk1;                                                    // LeakyReLU(0.2) on the staged input of source 0 / 1 (kernels instantiated with LK only)
 };
 
-typedef float ww_f2 __attribute__((ext_vector_type(2)));
 // (s_nop 1: hipcc places no wait states between a VALU / v_accvgpr_write it put in front of an asm statement and the MFMA reading that register; free next to a 64-cycle MFMA)
 #define WW_MFMA_ASM(k) asm volatile("s_nop 1\n\tv_mfma_f32_32x32x2_f32 %0, %1, %2, %0" : "+a"(accr[(k) % 9]) : "v"(a_), "v"(b_));
-#define WW_LDRAW(p) (*reinterpret_cast<const ww_f2*>(p))
-#define WW_ST2(p, v) *reinterpret_cast<ww_f2*>(p) = (v)
+#define WW_LDRAW(p) (*reinterpret_cast<const f32x2*>(p))
+#define WW_ST2(p, v) *reinterpret_cast<f32x2*>(p) = (v)
 // Rows 3 RH .. 3 RH + 2 of B^T applied to six values / all six rows (float2: two channels at once, packed instructions)
 template <int RH>
-__device__ __forceinline__ void ww_bt3(const ww_f2 (&d)[6], ww_f2 (&t)[3]) {
+__device__ __forceinline__ void ww_bt3(const f32x2 (&d)[6], f32x2 (&t)[3]) {
     if constexpr (RH == 0) {
-        const ww_f2 p = d[4] - 4.0f * d[2], q = d[3] - 4.0f * d[1];
+        const f32x2 p = d[4] - 4.0f * d[2], q = d[3] - 4.0f * d[1];
         t[0] = 4.0f * d[0] - 5.0f * d[2] + d[4];
         t[1] = p + q;
         t[2] = p - q;
     } else {
-        const ww_f2 p = d[4] - d[2], q = d[3] - d[1];
+        const f32x2 p = d[4] - d[2], q = d[3] - d[1];
         t[0] = p + 2.0f * q;
         t[1] = p - 2.0f * q;
         t[2] = 4.0f * d[1] - 5.0f * d[3] + d[5];
     }
 }
-__device__ __forceinline__ void ww_bt6(const ww_f2 (&d)[6], ww_f2 (&t)[6]) {
-    const ww_f2 p = d[4] - 4.0f * d[2], q = d[3] - 4.0f * d[1], r = d[4] - d[2], s = d[3] - d[1];
+__device__ __forceinline__ void ww_bt6(const f32x2 (&d)[6], f32x2 (&t)[6]) {
+    const f32x2 p = d[4] - 4.0f * d[2], q = d[3] - 4.0f * d[1], r = d[4] - d[2], s = d[3] - d[1];
     t[0] = 4.0f * d[0] - 5.0f * d[2] + d[4];
     t[1] = p + q;
     t[2] = p - q;
@@ -329,21 +328,21 @@ __device__ __forceinline__ void ww_bt6(const ww_f2 (&d)[6], ww_f2 (&t)[6]) {
 }
 // Rows 3 RH .. 3 RH + 2 of A (6 x 4) applied to four values / all six rows
 template <int RH>
-__device__ __forceinline__ void ww_a3(const ww_f2 (&y)[4], ww_f2 (&o)[3]) {
+__device__ __forceinline__ void ww_a3(const f32x2 (&y)[4], f32x2 (&o)[3]) {
     if constexpr (RH == 0) {
-        const ww_f2 e = y[0] + y[2], f = y[1] + y[3];
+        const f32x2 e = y[0] + y[2], f = y[1] + y[3];
         o[0] = y[0];
         o[1] = e + f;
         o[2] = e - f;
     } else {
-        const ww_f2 g4 = y[0] + 4.0f * y[2], h = 2.0f * y[1] + 8.0f * y[3];
+        const f32x2 g4 = y[0] + 4.0f * y[2], h = 2.0f * y[1] + 8.0f * y[3];
         o[0] = g4 + h;
         o[1] = g4 - h;
         o[2] = y[3];
     }
 }
-__device__ __forceinline__ void ww_a6(const ww_f2 (&y)[4], ww_f2 (&o)[6]) {
-    const ww_f2 e = y[0] + y[2], f = y[1] + y[3], g4 = y[0] + 4.0f * y[2], h = 2.0f * y[1] + 8.0f * y[3];
+__device__ __forceinline__ void ww_a6(const f32x2 (&y)[4], f32x2 (&o)[6]) {
+    const f32x2 e = y[0] + y[2], f = y[1] + y[3], g4 = y[0] + 4.0f * y[2], h = 2.0f * y[1] + 8.0f * y[3];
     o[0] = y[0];
     o[1] = e + f;
     o[2] = e - f;
@@ -465,13 +464,13 @@ __device__ __forceinline__ void ww_wave(const WwArgs& a, float* sm, const int wa
         float* const vdw = sm + 2 * WW_RAWF + Q * (2 * WW_VDF) + wr_off + (3 * RH * 6) * 128;        // X(p+1) writes its rows of VD[(p+1) & 1]
         auto commit = [&](auto ii, auto hh) {                        // W: half of one staged float4 -> the raw buffer.  8-byte writes: behind an MFMA a ds_write_b64
             constexpr int it = decltype(ii)::value, h = decltype(hh)::value;      // costs the wave ~2 cycles, a ds_write_b128 ~80 (tools/wgrad_clock.py)
-            ww_f2 v = h ? ww_f2{sr[P][it][2], sr[P][it][3]} : ww_f2{sr[P][it][0], sr[P][it][1]};
-            if constexpr (LK && !ISV) { if (lk) v = ww_f2{fmaxf(v[0], 0.2f * v[0]), fmaxf(v[1], 0.2f * v[1])}; }
+            f32x2 v = h ? f32x2{sr[P][it][2], sr[P][it][3]} : f32x2{sr[P][it][0], sr[P][it][1]};
+            if constexpr (LK && !ISV) { if (lk) v = f32x2{fmaxf(v[0], 0.2f * v[0]), fmaxf(v[1], 0.2f * v[1])}; }
             float* d;
             if constexpr (ISV) d = wbuf + lds_c + it * WW_GW * WW_PS;
             else if constexpr (it < 6) d = wbuf + lds_c + it * WW_HC * WW_PS;
             else d = wbuf + lds_6;
-            if (ISV || it < 6 || u < 96) *reinterpret_cast<ww_f2*>(d + 2 * h) = v;
+            if (ISV || it < 6 || u < 96) *reinterpret_cast<f32x2*>(d + 2 * h) = v;
         };
 #define WW_I(k) std::integral_constant<int, (k)>{}
 #define WW_C(it, h) commit(WW_I(it), WW_I(h))
@@ -490,7 +489,7 @@ __device__ __forceinline__ void ww_wave(const WwArgs& a, float* sm, const int wa
         if constexpr (ISV) { WW_C(0, 0); } else { WW_C(0, 0);  WW_C(3, 1); }
         WW_SB();
         if constexpr (ISV) {
-            ww_f2 X6[6][6], T[3][6];
+            f32x2 X6[6][6], T[3][6];
             WW_MFMA(Q, 16)  WW_C(0, 1);
 #pragma unroll
             for (int r = 0; r < 6; ++r) X6[0][r] = WW_LDRAW(rbuf + (r * WW_HC) * WW_PS);
@@ -502,7 +501,7 @@ __device__ __forceinline__ void ww_wave(const WwArgs& a, float* sm, const int wa
             if constexpr ((k) < 5) {                                                                                           \
                 _Pragma("unroll") for (int r = 0; r < 6; ++r) X6[(k) + 1][r] = WW_LDRAW(rbuf + (r * WW_HC + (k) + 1) * WW_PS); \
             }                                                                                                                  \
-            { ww_f2 t3[3];  ww_bt3<RH>(X6[k], t3);  T[0][k] = t3[0];  T[1][k] = t3[1];  T[2][k] = t3[2]; }                      \
+            { f32x2 t3[3];  ww_bt3<RH>(X6[k], t3);  T[0][k] = t3[0];  T[1][k] = t3[1];  T[2][k] = t3[2]; }                      \
             E;  WW_SB();
             WW_COL(0, WW_C(1, 1)) WW_COL(1, WW_C(2, 0)) WW_COL(2, WW_C(2, 1)) WW_COL(3, WW_C(3, 0)) WW_COL(4, WW_C(3, 1))
             WW_COL(5, if (MF && do_bias) bsum += av[P][7][0] + av[P][7][1])
@@ -510,7 +509,7 @@ __device__ __forceinline__ void ww_wave(const WwArgs& a, float* sm, const int wa
             // slots 6..14: row r through all of B^T, its six 8-byte writes two per slot
 #define WW_ROW(r)                                                                                                              \
             {                                                                                                                  \
-                ww_f2 v[6];                                                                                                    \
+                f32x2 v[6];                                                                                                    \
                 float* const o = vdw + ((r) * 6) * 128;                                                                        \
                 WW_MFMA(P, 6 + 3 * (r))  ww_bt6(T[r], v);  WW_ST2(o, v[0]);  WW_ST2(o + 128, v[1]);  WW_SB();                  \
                 WW_MFMA(P, 7 + 3 * (r))  WW_ST2(o + 256, v[2]);  WW_ST2(o + 384, v[3]);  WW_SB();                              \
@@ -519,7 +518,7 @@ __device__ __forceinline__ void ww_wave(const WwArgs& a, float* sm, const int wa
             WW_ROW(0) WW_ROW(1) WW_ROW(2)
 #undef WW_ROW
         } else {
-            ww_f2 Y4[4][4], U[3][4];
+            f32x2 Y4[4][4], U[3][4];
             WW_MFMA(Q, 16)  WW_C(1, 0);  WW_C(4, 1);
 #pragma unroll
             for (int m = 0; m < 4; ++m) Y4[0][m] = WW_LDRAW(rbuf + (m * WW_GW) * WW_PS);
@@ -531,14 +530,14 @@ __device__ __forceinline__ void ww_wave(const WwArgs& a, float* sm, const int wa
             if constexpr ((k) < 3) {                                                                                           \
                 _Pragma("unroll") for (int m = 0; m < 4; ++m) Y4[(k) + 1][m] = WW_LDRAW(rbuf + (m * WW_GW + (k) + 1) * WW_PS); \
             }                                                                                                                  \
-            { ww_f2 o3[3];  ww_a3<RH>(Y4[k], o3);  U[0][k] = o3[0];  U[1][k] = o3[1];  U[2][k] = o3[2]; }                       \
+            { f32x2 o3[3];  ww_a3<RH>(Y4[k], o3);  U[0][k] = o3[0];  U[1][k] = o3[1];  U[2][k] = o3[2]; }                       \
             WW_C(3 + (k), 0);  WW_C(((k) + 6) % 7, 1);  WW_SB();
             WW_COL(0) WW_COL(1) WW_COL(2) WW_COL(3)
 #undef WW_COL
             // slots 4..12: row r through all of A, its six 8-byte writes two per slot; 13, 14: MFMAs only
 #define WW_ROW(r)                                                                                                              \
             {                                                                                                                  \
-                ww_f2 v[6];                                                                                                    \
+                f32x2 v[6];                                                                                                    \
                 float* const o = vdw + ((r) * 6) * 128;                                                                        \
                 WW_MFMA(P, 4 + 3 * (r))  ww_a6(U[r], v);  WW_ST2(o, v[0]);  WW_ST2(o + 128, v[1]);  WW_SB();                   \
                 WW_MFMA(P, 5 + 3 * (r))  WW_ST2(o + 256, v[2]);  WW_ST2(o + 384, v[3]);  WW_SB();                              \
@@ -762,15 +761,15 @@ __device__ __forceinline__ void ww8_wave(const WwArgs& a, float* sm, const int w
         if (MF && do_bias) bsum += oa[7][0] + oa[7][1];
         // ================= segment 2: fourteen MFMAs (K step 0 of positions 0..6, then K step 1); slot m = MFMA m + what fits behind it
 #define W8_M(m) if constexpr ((m) < 14) { W8_MFMA((m) % 7, (m) / 7) }
-        ww_f2 T[3][ROLE == W8_V ? 6 : 4];
+        f32x2 T[3][ROLE == W8_V ? 6 : 4];
         if constexpr (ROLE == W8_V) {
-            ww_f2 X6[6][6];
+            f32x2 X6[6][6];
 #pragma unroll
             for (int r = 0; r < 6; ++r) X6[0][r] = WW_LDRAW(rd + (r * WW_HC) * WW_PS);
             WW_SB();
 #define W8_COL(k)                                                                                                              \
             W8_M(k)                                                                                                            \
-            { ww_f2 t3[3];  ww_bt3<RH>(X6[k], t3);  T[0][k] = t3[0];  T[1][k] = t3[1];  T[2][k] = t3[2]; }                      \
+            { f32x2 t3[3];  ww_bt3<RH>(X6[k], t3);  T[0][k] = t3[0];  T[1][k] = t3[1];  T[2][k] = t3[2]; }                      \
             asm volatile("" ::: "memory");                                                                                     \
             if constexpr ((k) < 5) {                                                                                           \
                 _Pragma("unroll") for (int r = 0; r < 6; ++r) X6[(k) + 1][r] = WW_LDRAW(rd + (r * WW_HC + (k) + 1) * WW_PS);   \
@@ -780,7 +779,7 @@ __device__ __forceinline__ void ww8_wave(const WwArgs& a, float* sm, const int w
 #undef W8_COL
 #define W8_ROW(r, m0)                                                                                                          \
             {                                                                                                                  \
-                ww_f2 v[6];                                                                                                    \
+                f32x2 v[6];                                                                                                    \
                 float* const o = vdw + ((r) * 6) * WSTEP;                                                                      \
                 W8_M(m0)  ww_bt6(T[r], v);  WW_ST2(o, v[0]);  WW_ST2(o + WSTEP, v[1]);  WW_SB();                               \
                 W8_M((m0) + 1)  WW_ST2(o + 2 * WSTEP, v[2]);  WW_ST2(o + 3 * WSTEP, v[3]);  WW_SB();                           \
@@ -789,7 +788,7 @@ __device__ __forceinline__ void ww8_wave(const WwArgs& a, float* sm, const int w
             W8_ROW(0, 6) W8_ROW(1, 9) W8_ROW(2, 12)
 #undef W8_ROW
         } else if constexpr (ROLE == W8_D) {
-            ww_f2 Y4[4][4];
+            f32x2 Y4[4][4];
 #pragma unroll
             for (int m = 0; m < 4; ++m) Y4[0][m] = WW_LDRAW(rd + (m * WW_GW) * W8_PSY);
             WW_SB();
@@ -798,13 +797,13 @@ __device__ __forceinline__ void ww8_wave(const WwArgs& a, float* sm, const int w
             if constexpr ((k) < 3) {                                                                                           \
                 _Pragma("unroll") for (int m = 0; m < 4; ++m) Y4[(k) + 1][m] = WW_LDRAW(rd + (m * WW_GW + (k) + 1) * W8_PSY);  \
             }                                                                                                                  \
-            { ww_f2 o3[3];  ww_a3<RH>(Y4[k], o3);  T[0][k] = o3[0];  T[1][k] = o3[1];  T[2][k] = o3[2]; }                       \
+            { f32x2 o3[3];  ww_a3<RH>(Y4[k], o3);  T[0][k] = o3[0];  T[1][k] = o3[1];  T[2][k] = o3[2]; }                       \
             commit(W8_I(k));  WW_SB();
             W8_COL(0) W8_COL(1) W8_COL(2) W8_COL(3)
 #undef W8_COL
 #define W8_ROW(r, m0)                                                                                                          \
             {                                                                                                                  \
-                ww_f2 v[6];                                                                                                    \
+                f32x2 v[6];                                                                                                    \
                 float* const o = vdw + ((r) * 6) * WSTEP;                                                                      \
                 W8_M(m0)  ww_a6(T[r], v);  WW_ST2(o, v[0]);  WW_ST2(o + WSTEP, v[1]);  WW_SB();                                \
                 W8_M((m0) + 1)  WW_ST2(o + 2 * WSTEP, v[2]);  WW_ST2(o + 3 * WSTEP, v[3]);  WW_SB();                           \

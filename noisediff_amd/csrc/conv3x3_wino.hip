@@ -21,6 +21,7 @@
 //   * epilogue identical to the direct kernel: +bias, store, per-(wave, channel) GroupNorm partials {sum, M2}.
 #include <stdlib.h>
 #include "nd_common.h"
+#include "wino2x2.h"
 
 namespace {
 
@@ -36,16 +37,6 @@ struct WinoArgs {
     nd_conv3x3 d;
     int tiles_x, tiles_y, n_tiles, coutP, slots, total_wg;
 };
-
-// B^T rows as (index, sign) pairs: xi -> s1*d[r1] + s2*d[r2]
-__device__ __forceinline__ constexpr int bt_r1(int xi) { return xi == 0 ? 0 : 1; }
-__device__ __forceinline__ constexpr int bt_r2(int xi) { return xi == 3 ? 3 : 2; }
-__device__ __forceinline__ constexpr float bt_s1(int xi) { return xi == 2 ? -1.0f : 1.0f; }
-__device__ __forceinline__ constexpr float bt_s2(int xi) { return (xi == 0 || xi == 3) ? -1.0f : 1.0f; }
-// A^T[a][xi]
-__device__ __forceinline__ constexpr int at_coef(int a, int xi) {
-    return a == 0 ? (xi <= 2 ? 1 : 0) : (xi == 0 ? 0 : (xi == 1 ? 1 : -1));
-}
 
 template <int NB, int NG, int LDA>
 __device__ __forceinline__ void wino_chunk(f32x16 (&Y)[2][2][NB], const float* As, const int a_base, const float* wchunk) {
@@ -315,7 +306,6 @@ __global__ void pack_wino_kernel(const float* __restrict__ w, float* __restrict_
     }
 }
 
-static inline int device_cus() { return nd_device_cus(); }
 
 template <int NB, int MODE, int KC>
 void launch_kc(const WinoArgs& a, hipStream_t st) {
@@ -325,7 +315,7 @@ void launch_kc(const WinoArgs& a, hipStream_t st) {
         if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, wino_kernel<NB, MODE, KC>, 256, 0) != hipSuccess || per_cu <= 0) per_cu = 2;
         per_cu_cache.store(per_cu, std::memory_order_relaxed);
     }
-    const long resident = (long)device_cus() * per_cu;
+    const long resident = (long)nd_device_cus() * per_cu;
     const dim3 grid((unsigned)(a.total_wg < resident ? a.total_wg : resident)), block(256);
     hipLaunchKernelGGL((wino_kernel<NB, MODE, KC>), grid, block, 0, st, a);
 }

@@ -16,6 +16,7 @@
 #include <stdlib.h>
 #include <type_traits>
 #include "nd_common.h"
+#include "wino2x2.h"
 
 namespace {
 
@@ -72,7 +73,6 @@ constexpr int STAGE_IT = (NPIX * 8 + 255) / 256;    // 11
 #define W2_MFMA_DRAIN() asm volatile("s_nop 15\n\ts_nop 15" ::: "memory")
 #define W2_PIN(x) asm volatile("" : "+v"(x))          // value is complete here: keeps pure VALU work in its slice
 
-typedef float f32x2 __attribute__((ext_vector_type(2)));
 typedef const __attribute__((address_space(1))) char* gchar_p;        // global (not flat) pointers for the weight stream
 typedef const __attribute__((address_space(1))) f32x4* gf32x4_p;
 // s1 * a + s2 * b on four floats as two packed adds (a VALU slot costs the single in-order wave ~5 cycles of matrix
@@ -101,14 +101,6 @@ struct Wino2Args {
     nd_conv3x3 d;
     int tiles_x, tiles_y, n_tiles, coutP, slots, total_wg;
 };
-
-__device__ __forceinline__ constexpr int bt_r1(int xi) { return xi == 0 ? 0 : 1; }
-__device__ __forceinline__ constexpr int bt_r2(int xi) { return xi == 3 ? 3 : 2; }
-__device__ __forceinline__ constexpr float bt_s1(int xi) { return xi == 2 ? -1.0f : 1.0f; }
-__device__ __forceinline__ constexpr float bt_s2(int xi) { return (xi == 0 || xi == 3) ? -1.0f : 1.0f; }
-__device__ __forceinline__ constexpr int at_coef(int a, int xi) {
-    return a == 0 ? (xi <= 2 ? 1 : 0) : (xi == 0 ? 0 : (xi == 1 ? 1 : -1));
-}
 
 template <int MODE>
 __global__ __launch_bounds__(256, 1) void wino2_kernel(const Wino2Args a) {
@@ -556,14 +548,13 @@ __global__ __launch_bounds__(256, 1) void wino2_kernel(const Wino2Args a) {
 #endif
 }
 
-static inline int device_cus() { return nd_device_cus(); }
 
 template <int MODE>
 int launch_mode(const Wino2Args& a, hipStream_t st) {
     static nd_device_once configured;
     const size_t lds = ((size_t)2 * BUF + 3 * STAGE_IT * 256) * sizeof(float);
     if (int e = nd_reserve_lds(configured, reinterpret_cast<const void*>(wino2_kernel<MODE>), lds, "nd_conv3x3_wino2")) return e;
-    const long resident = device_cus();                   // one workgroup per CU by construction (LDS + registers)
+    const long resident = nd_device_cus();                // one workgroup per CU by construction (LDS + registers)
     const dim3 grid((unsigned)(a.total_wg < resident ? a.total_wg : resident)), block(256);
     hipLaunchKernelGGL((wino2_kernel<MODE>), grid, block, lds, st, a);
     return 0;

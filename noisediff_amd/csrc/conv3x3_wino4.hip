@@ -41,7 +41,6 @@
 
 namespace {
 
-typedef float f32x2 __attribute__((ext_vector_type(2)));
 typedef unsigned u32x4_t __attribute__((ext_vector_type(4)));
 typedef __attribute__((address_space(3))) void* lds_ptr;
 typedef __attribute__((address_space(3))) short* lds_short_ptr;

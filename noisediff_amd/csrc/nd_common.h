@@ -119,7 +119,8 @@ __device__ __forceinline__ float nd_act(float v, int act) {
 __device__ __forceinline__ f32x4 nd_ld4(const float* p) { return *reinterpret_cast<const f32x4*>(p); }
 __device__ __forceinline__ void nd_st4(float* p, f32x4 v) { *reinterpret_cast<f32x4*>(p) = v; }
 
-__device__ __forceinline__ float nd_clip(float v, float lo, float hi) { return v < lo ? lo : (v > hi ? hi : v); }       // NaN passes through
+template <typename T>
+__device__ __forceinline__ T nd_clip(T v, T lo, T hi) { return v < lo ? lo : (v > hi ? hi : v); }       // NaN passes through
 
 // V = 1, 2 or 4 consecutive floats from p, by the widest load p's alignment allows (p is 4-byte aligned at least)
 template <int V>

@@ -14,6 +14,7 @@
 //
 // No floating-point atomics, no cooperative launch, no kernel that waits for another workgroup, no host read.
 #include "nd_common.h"
+#include "block_sum.h"
 #include <float.h>
 
 // The fit mirrors numpy operation by operation (the order of the long sums apart): a product and a sum stay two roundings.
@@ -242,22 +243,6 @@ struct ts_head {
     int done, n_iter;
 };
 
-template <int K>
-__device__ __forceinline__ void ts_block_sum(double (&a)[K], double (*red)[4]) {      // the same tree every time; every thread gets the result
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1)
-#pragma unroll
-        for (int k = 0; k < K; ++k) a[k] += __shfl_xor(a[k], o);
-    const int w = threadIdx.x >> 6;
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0)
-#pragma unroll
-        for (int k = 0; k < K; ++k) red[k][w] = a[k];
-    __syncthreads();
-#pragma unroll
-    for (int k = 0; k < K; ++k) a[k] = (red[k][0] + red[k][1]) + (red[k][2] + red[k][3]);
-}
-
 __device__ __forceinline__ int ts_m(const int* m, int max_m) {
     const int v = *m;
     return v < 0 ? 0 : (v > max_m ? max_m : v);
@@ -309,7 +294,7 @@ __global__ __launch_bounds__(TS_THREADS) void ts_partial_kernel(const double* __
             for (int j = i + 1 + t; j < m; j += TS_THREADS) point(xi, yi, x[j], y[j]);
         }
     }
-    ts_block_sum<TS_SUMS>(acc, red);
+    block_sum_all<TS_SUMS>(acc, red);
     if (t == 0) {
         double* s = ws + TS_HEAD + (size_t)b * TS_SUMS;
 #pragma unroll
@@ -330,7 +315,7 @@ __global__ __launch_bounds__(TS_THREADS) void ts_finalize_kernel(const int* __re
 #pragma unroll
         for (int k = 0; k < TS_SUMS; ++k) S[k] += s[k];
     }
-    ts_block_sum<TS_SUMS>(S, red);
+    block_sum_all<TS_SUMS>(S, red);
     if (threadIdx.x != 0) return;
     if (MEAN) {
         const int m = ts_m(m_dev, max_m);

@@ -10,6 +10,7 @@
 // writes its partial (counts, or the four fp64 sums of a tile) to its own workspace slot with plain stores; a finalize kernel sums a set's
 // slots in a fixed order.  The slot layout of a set depends on its own size only, so a set's result does not depend on the other sets in the call.
 #include "nd_common.h"
+#include "block_sum.h"
 
 #ifndef ND_HIST_VARIANT
 #define ND_HIST_VARIANT 0      // 0: one LDS histogram per workgroup, one atomic per element (shipped: the measured choice);
@@ -139,24 +140,6 @@ int hist_blocks(int64_t n) {
 }
 bool hist_sizes_ok(int S, int64_t n) { return S > 0 && S <= 65535 && n > 0 && n <= HIST_MAX_N; }
 
-// K fp64 values summed over the 256 threads of the block, the same order every time: xor butterfly in each wave, then the four waves in a
-// fixed tree.  Every thread gets the result.
-template <int K>
-__device__ __forceinline__ void ns_block_sum(double (&a)[K], double (*red)[4]) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1)
-#pragma unroll
-        for (int k = 0; k < K; ++k) a[k] += __shfl_xor(a[k], o);
-    const int w = threadIdx.x >> 6;
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0)
-#pragma unroll
-        for (int k = 0; k < K; ++k) red[k][w] = a[k];
-    __syncthreads();
-#pragma unroll
-    for (int k = 0; k < K; ++k) a[k] = (red[k][0] + red[k][1]) + (red[k][2] + red[k][3]);
-}
-
 __device__ __forceinline__ bool ns_finite(double v) { return v - v == 0.0; }
 
 // One workgroup per set.  COUNTS: p and q are int64 counts divided by n_p, n_q; else fp64 hists, whose NaN and inf entries drop the bin as
@@ -182,7 +165,7 @@ __global__ __launch_bounds__(256) void kl_div_kernel(const void* __restrict__ pv
             acc[1] += q * log(q / p);
         }
     }
-    ns_block_sum<2>(acc, red);
+    block_sum_all<2>(acc, red);
     if (threadIdx.x == 0) {
         out[3 * (size_t)s] = acc[0];
         out[3 * (size_t)s + 1] = acc[1];
@@ -241,14 +224,14 @@ __global__ __launch_bounds__(256) void patch_std_mean_kernel(const float* __rest
             acc[3] = fma(md, sdd, acc[3]);
         }
     }
-    ns_block_sum<4>(acc, red);
+    block_sum_all<4>(acc, red);
     if (threadIdx.x == 0) {
         double* o = slots + (((size_t)b * C + c) * (size_t)(ntx * nty) + tl) * 4;
         o[0] = acc[0];  o[1] = acc[1];  o[2] = acc[2];  o[3] = acc[3];
     }
 }
 
-// One workgroup per (image, channel): its tiles' sums thread-strided, then in ns_block_sum's tree; the closed-form line.
+// One workgroup per (image, channel): its tiles' sums thread-strided, then in block_sum_all's tree; the closed-form line.
 __global__ __launch_bounds__(256) void patch_fit_kernel(const double* __restrict__ slots, int ntile, double N, double* __restrict__ fit) {
     __shared__ double red[4][4];
     const int bc = blockIdx.x;
@@ -258,7 +241,7 @@ __global__ __launch_bounds__(256) void patch_fit_kernel(const double* __restrict
 #pragma unroll
         for (int k = 0; k < 4; ++k) a[k] += s[4 * (size_t)i + k];
     }
-    ns_block_sum<4>(a, red);
+    block_sum_all<4>(a, red);
     if (threadIdx.x == 0) {
         const double sm = a[0], ss = a[1], smm = a[2], sms = a[3];
         const double den = N * smm - sm * sm;

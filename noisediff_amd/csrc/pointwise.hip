@@ -14,6 +14,7 @@
 #include <stdlib.h>
 #include <type_traits>
 #include "nd_common.h"
+#include "split_bf16.h"
 
 namespace {
 
@@ -504,33 +505,18 @@ __global__ __launch_bounds__(256, 1) void pointwise_big_kernel(const PwArgs a) {
 }
 
 // ---- SPLIT variant (r6; nd_pointwise_gemm_split_nhwc_f32): the same per-pixel GEMM with every product on the bf16 matrix pipe at the operands' FULL fp32
-// significand.  v = v1 + v2 + v3 exactly (v1 = bf16(v), v2 = bf16(v - v1), round-to-nearest-even; v3 = v - v1 - v2: at most 8 significant bits); six of the nine
-// term products are kept (w1 v1, w1 v2, w2 v1, w2 v2, w1 v3, w3 v1: the dropped ones are below 2^-25 of the product), each one v_mfma_f32_32x32x16_bf16 -- 16
-// channels of a 32 x 32 tile cost 6 x 32 matrix cycles against 8 x 64 on v_mfma_f32_32x32x2_f32, and the bf16 instruction leaves the vector ALU to the split,
-// the prologue and the epilogue (the fp32 one issues on the VALU's own lanes).  The wide 1x1 layers then sit against HBM, so the kernel is built to keep bytes
+// significand: the three-term split and its six kept products are split_bf16.h's.  The wide 1x1 layers then sit against HBM, so the kernel is built to keep bytes
 // in flight: TWO workgroups per CU (67.6 KB of LDS, 256 registers each), each one software-pipelined over 32-channel chunks.
 //   * activations: 128 rows x 32 channels per chunk, thread = (row, 8-channel segment): two 16-byte loads, the prologue, the split ONCE per element
 //     (11 VALU instructions per value pair), three ds_write_b128 into the chunk's term planes [term 3][row 128][64 bytes + 16 pad] (conflict-free b128 reads);
 //   * weights: split once at pack time (nd_pack_pointwise_weight_split: [K step][term][32-cout tile][lane 64] x 16 bytes, lane (cout l & 31, K group l >> 5) holding
 //     channels 16 ks + 8 (l >> 5) .. + 7), straight from the L2 into a register ring one K step ahead;
 //   * a wave owns 64 pixels x 64 couts: 4 accumulators, 6 + 6 operand reads (16 bytes per lane each) per 24 MFMAs.
-// Epilogue: pw_epilogue, as every other kernel of this file.  Accuracy against fp64: profiles/r6_split_gemm_accuracy.txt.
-typedef __bf16 pw_bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 pw_bf16x2 __attribute__((ext_vector_type(2)));
-typedef unsigned pw_u32x4 __attribute__((ext_vector_type(4)));
+// Epilogue: pw_epilogue, as every other kernel of this file.
 constexpr int SKC = 32;                                      // channels per chunk: two 16-channel K steps
 constexpr int SROW = SKC * 2 + 16;                           // bytes per row of a term plane
 constexpr int SPLANE = 128 * SROW, SABUF = 3 * SPLANE;       // one term plane, one chunk buffer (30 KB)
 constexpr int SPLIT_LDS = 2 * SABUF > 128 * 132 * 4 ? 2 * SABUF : 128 * 132 * 4;
-
-// (x, y) -> one dword of each of the three bf16 terms (x in the low half)
-__device__ __forceinline__ void pw_split2(float x, float y, unsigned& w1, unsigned& w2, unsigned& w3) {
-    w1 = __builtin_bit_cast(unsigned, __builtin_convertvector(f32x2{x, y}, pw_bf16x2));
-    const float rx = x - __builtin_bit_cast(float, w1 << 16), ry = y - __builtin_bit_cast(float, w1 & 0xFFFF0000u);
-    w2 = __builtin_bit_cast(unsigned, __builtin_convertvector(f32x2{rx, ry}, pw_bf16x2));
-    const float sx = rx - __builtin_bit_cast(float, w2 << 16), sy = ry - __builtin_bit_cast(float, w2 & 0xFFFF0000u);
-    w3 = __builtin_amdgcn_perm(__builtin_bit_cast(unsigned, sy), __builtin_bit_cast(unsigned, sx), 0x07060302u);   // the upper halves ARE the third terms
-}
 
 template <int MODE>
 __global__ __launch_bounds__(256, 2) void pointwise_split_kernel(const PwArgs a) {
@@ -583,7 +569,7 @@ __global__ __launch_bounds__(256, 2) void pointwise_split_kernel(const PwArgs a)
         }
     }
 
-    pw_u32x4 bq[2][3][NB];                                     // weight ring: K step parity x term x 32-cout tile
+    u32x4 bq[2][3][NB];                                        // weight ring: K step parity x term x 32-cout tile
     f32x4 raw[2][2];                                           // the next chunk's activations in flight: pass x half segment
     f32x4 pA[2], pB[2], pC[2];                                 // per-chunk channel constants of the prologue
     auto load_b = [&](int slot, int ks) {                      // weight fragments of K step ks (beyond the last one: a harmless reload of it)
@@ -591,7 +577,7 @@ __global__ __launch_bounds__(256, 2) void pointwise_split_kernel(const PwArgs a)
         for (int t = 0; t < 3; ++t)
 #pragma unroll
             for (int nb = 0; nb < NB; ++nb)
-                bq[slot][t][nb] = __builtin_bit_cast(pw_u32x4, __builtin_amdgcn_raw_buffer_load_b128(
+                bq[slot][t][nb] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(
                     wrsrc, wvoff, __builtin_amdgcn_readfirstlane((((ks * 3 + t) * n32 + wtile + nb) * 64) * 16), 0));
     };
     auto stage_load = [&](int cb) {
@@ -625,7 +611,7 @@ __global__ __launch_bounds__(256, 2) void pointwise_split_kernel(const PwArgs a)
 #pragma unroll
         for (int it = 0; it < 2; ++it) {
             const int r = prow + it * 64;
-            pw_u32x4 t1, t2, t3;
+            u32x4 t1, t2, t3;
 #pragma unroll
             for (int j = 0; j < 2; ++j) {
                 f32x4 v = raw[it][j];
@@ -636,36 +622,33 @@ __global__ __launch_bounds__(256, 2) void pointwise_split_kernel(const PwArgs a)
                 const f32x4 zero = {0, 0, 0, 0};
                 v = (p0 + r < HW) ? v : zero;
                 unsigned u1, u2, u3;
-                pw_split2(v.x, v.y, u1, u2, u3);  t1[2 * j] = u1;  t2[2 * j] = u2;  t3[2 * j] = u3;
-                pw_split2(v.z, v.w, u1, u2, u3);  t1[2 * j + 1] = u1;  t2[2 * j + 1] = u2;  t3[2 * j + 1] = u3;
+                nd_split2_bf16(v.x, v.y, u1, u2, u3);  t1[2 * j] = u1;  t2[2 * j] = u2;  t3[2 * j] = u3;
+                nd_split2_bf16(v.z, v.w, u1, u2, u3);  t1[2 * j + 1] = u1;  t2[2 * j + 1] = u2;  t3[2 * j + 1] = u3;
             }
             char* o = dst + r * SROW + seg * 16;
-            *reinterpret_cast<pw_u32x4*>(o) = t1;
-            *reinterpret_cast<pw_u32x4*>(o + SPLANE) = t2;
-            *reinterpret_cast<pw_u32x4*>(o + 2 * SPLANE) = t3;
+            *reinterpret_cast<u32x4*>(o) = t1;
+            *reinterpret_cast<u32x4*>(o + SPLANE) = t2;
+            *reinterpret_cast<u32x4*>(o + 2 * SPLANE) = t3;
         }
-    };
-    auto mfma = [&](pw_u32x4 av, pw_u32x4 bv, f32x16 c) {
-        return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(pw_bf16x8, av), __builtin_bit_cast(pw_bf16x8, bv), c, 0, 0, 0);
     };
     auto kstep = [&](auto slot_c, const char* src, int k2) {   // one 16-channel K step of the chunk in `src` (k2 = 0, 1) on ring slot `slot_c`
         constexpr int S = decltype(slot_c)::value;
-        pw_u32x4 av[MB][3];
+        u32x4 av[MB][3];
 #pragma unroll
         for (int mb = 0; mb < MB; ++mb)
 #pragma unroll
-            for (int t = 0; t < 3; ++t) av[mb][t] = *reinterpret_cast<const pw_u32x4*>(src + t * SPLANE + a_off[mb] + k2 * 32);
+            for (int t = 0; t < 3; ++t) av[mb][t] = *reinterpret_cast<const u32x4*>(src + t * SPLANE + a_off[mb] + k2 * 32);
 #pragma unroll
         for (int mb = 0; mb < MB; ++mb)
 #pragma unroll
             for (int nb = 0; nb < NB; ++nb) {
                 f32x16 c = acc[mb][nb];
-                c = mfma(av[mb][0], bq[S][0][nb], c);
-                c = mfma(av[mb][1], bq[S][0][nb], c);
-                c = mfma(av[mb][0], bq[S][1][nb], c);
-                c = mfma(av[mb][1], bq[S][1][nb], c);
-                c = mfma(av[mb][2], bq[S][0][nb], c);
-                c = mfma(av[mb][0], bq[S][2][nb], c);
+                c = nd_mfma_bf16(av[mb][0], bq[S][0][nb], c);
+                c = nd_mfma_bf16(av[mb][1], bq[S][0][nb], c);
+                c = nd_mfma_bf16(av[mb][0], bq[S][1][nb], c);
+                c = nd_mfma_bf16(av[mb][1], bq[S][1][nb], c);
+                c = nd_mfma_bf16(av[mb][2], bq[S][0][nb], c);
+                c = nd_mfma_bf16(av[mb][0], bq[S][2][nb], c);
                 acc[mb][nb] = c;
             }
     };
@@ -1030,15 +1013,10 @@ __global__ void pack_pointwise_split_kernel(const float* __restrict__ w, unsigne
         const int tile = (int)(rest % n32), ks = (int)(rest / n32);
         const int n = 32 * tile + (l & 31), k = 16 * ks + 8 * (l >> 5) + i;
         const float v = (n < cout && k < cin) ? w[(size_t)n * cin + k] : 0.0f;
-        const __bf16 t1 = (__bf16)v;
-        const float r1 = v - (float)t1;                       // exact
-        const __bf16 t2 = (__bf16)r1;
-        const float r2 = r1 - (float)t2;                      // exact, at most 8 significant bits: its upper half is the third term
+        const bf16_terms t = nd_split3_bf16(v);
         unsigned short* o = out + (((size_t)ks * 3 * n32 + tile) * 64 + l) * 8 + i;
         const size_t term = (size_t)n32 * 512;
-        o[0] = __builtin_bit_cast(unsigned short, t1);
-        o[term] = __builtin_bit_cast(unsigned short, t2);
-        o[2 * term] = (unsigned short)(__builtin_bit_cast(unsigned, r2) >> 16);
+        o[0] = t.t1;  o[term] = t.t2;  o[2 * term] = t.t3;
     }
 }
 

@@ -19,37 +19,16 @@
 // four waves per SIMD (768 / 1024 threads) let one wave's activation VALU run under the others' MFMAs.
 //
 // SPLIT instances (r6; nd_pointwise_chain_split_nhwc_f32): the same chain with every product on the bf16 matrix pipe at the operands' FULL
-// fp32 significand.  x = x1 + x2 + x3 exactly, x1 = bf16(x), x2 = bf16(x - x1) (round-to-nearest-even, v_cvt_pk_bf16_f32), x3 = x - x1 - x2 (both
-// remainders are exact in fp32 and the second has at most 8 significant bits); weights are split once at pack time, activations per 16-channel
-// K step in registers (11 VALU instructions per value pair).  Six of the nine term products are kept -- w1 x1, w1 x2, w2 x1, w2 x2, w1 x3, w3 x1;
-// the dropped ones are below 2^-25 of the product, under the rounding of an fp32 FMA -- each one v_mfma_f32_32x32x16_bf16 (products of bf16 pairs
-// are exact in fp32; accumulation in fp32).  16 channels cost 6 x 32 matrix cycles per 32 x 32 tile against 8 x 64 for v_mfma_f32_32x32x2_f32
-// (2.67x), and -- unlike the fp32 instruction, which issues on the VALU's own lanes -- leave 24 of every 32 cycles of vector issue to the split,
-// LayerNorm and GELU work of the other waves.  Same operand pairing as the fp32 form: slot (K step s, lane half h, i < 8) = channel
+// fp32 significand -- the three-term split and its six kept products are split_bf16.h's.  Weights are split once at pack time, activations per
+// 16-channel K step in registers; the bf16 MFMA leaves 24 of every 32 cycles of vector issue to the split, LayerNorm and GELU work of the other
+// waves.  Same operand pairing as the fp32 form: slot (K step s, lane half h, i < 8) = channel
 // 16 s + 8 (i >> 2) + 4 h + (i & 3), which is both "registers (2s, 2s+1) of the input row's float4s" and "registers 8 (s & 1) .. + 7 of n-tile
 // s >> 1 of the previous stage's accumulators": the chain still flows register to register.  Weight terms sit in LDS (120 KB at C = 64).
-// Accuracy against fp64: profiles/r6_split_gemm_accuracy.txt (the r5 study of the same split on the F(4x4) kernel: rms error 0.94 of fp32's).
 #include <type_traits>
 #include "nd_common.h"
+#include "split_bf16.h"
 
 namespace {
-
-typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4_t __attribute__((ext_vector_type(4)));
-
-// (x, y) -> one dword of each of the three bf16 terms (x in the low half): x == t1 + t2 + t3 exactly
-__device__ __forceinline__ void chain_split2(float x, float y, unsigned& w1, unsigned& w2, unsigned& w3) {
-    w1 = __builtin_bit_cast(unsigned, __builtin_convertvector(f32x2{x, y}, bf16x2_t));
-    const float rx = x - __builtin_bit_cast(float, w1 << 16), ry = y - __builtin_bit_cast(float, w1 & 0xFFFF0000u);
-    w2 = __builtin_bit_cast(unsigned, __builtin_convertvector(f32x2{rx, ry}, bf16x2_t));
-    const float sx = rx - __builtin_bit_cast(float, w2 << 16), sy = ry - __builtin_bit_cast(float, w2 & 0xFFFF0000u);
-    w3 = __builtin_amdgcn_perm(__builtin_bit_cast(unsigned, sy), __builtin_bit_cast(unsigned, sx), 0x07060302u);   // the upper halves ARE the third terms
-}
-
-__device__ __forceinline__ f32x16 chain_mfma_bf16(u32x4_t a, u32x4_t b, f32x16 c) {
-    return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8_t, a), __builtin_bit_cast(bf16x8_t, b), c, 0, 0, 0);
-}
 
 struct ChainArgs {
     nd_chain d;
@@ -89,17 +68,17 @@ __device__ __forceinline__ void chain_gemm_split(const float (&in)[K / 2], const
     static_assert(K % 16 == 0, "whole 16-channel K steps");
     constexpr int S = K / 16, NT = N / 32;
     const int half = lane >> 5;
-    const u32x4_t* const wl = reinterpret_cast<const u32x4_t*>(w) + lane;
-    u32x4_t wq[2][3], xs[2][3];
+    const u32x4* const wl = reinterpret_cast<const u32x4*>(w) + lane;
+    u32x4 wq[2][3], xs[2][3];
     auto load_w = [&](int slot, int s_, int nt_) {
-        const u32x4_t* p = wl + ((nt_ * S + s_) * 3) * 64;
+        const u32x4* p = wl + ((nt_ * S + s_) * 3) * 64;
         wq[slot][0] = p[0];  wq[slot][1] = p[64];  wq[slot][2] = p[128];
     };
     auto split = [&](int slot, int s_) {
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             unsigned t1, t2, t3;
-            chain_split2(in[8 * s_ + 2 * j], in[8 * s_ + 2 * j + 1], t1, t2, t3);
+            nd_split2_bf16(in[8 * s_ + 2 * j], in[8 * s_ + 2 * j + 1], t1, t2, t3);
             xs[slot][0][j] = t1;  xs[slot][1][j] = t2;  xs[slot][2][j] = t3;
         }
     };
@@ -121,14 +100,14 @@ __device__ __forceinline__ void chain_gemm_split(const float (&in)[K / 2], const
             if (g + 1 < S * NT) load_w((g + 1) & 1, nt + 1 < NT ? s : s + 1, nt + 1 < NT ? nt + 1 : 0);
             __builtin_amdgcn_sched_barrier(0);
             if (nt == 0 && s + 1 < S) split((s + 1) & 1, s + 1);
-            const u32x4_t w1 = wq[g & 1][0], w2 = wq[g & 1][1], w3 = wq[g & 1][2];
-            const u32x4_t x1 = xs[s & 1][0], x2 = xs[s & 1][1], x3 = xs[s & 1][2];
-            acc[nt] = chain_mfma_bf16(w1, x1, acc[nt]);
-            acc[nt] = chain_mfma_bf16(w1, x2, acc[nt]);
-            acc[nt] = chain_mfma_bf16(w2, x1, acc[nt]);
-            acc[nt] = chain_mfma_bf16(w2, x2, acc[nt]);
-            acc[nt] = chain_mfma_bf16(w1, x3, acc[nt]);
-            acc[nt] = chain_mfma_bf16(w3, x1, acc[nt]);
+            const u32x4 w1 = wq[g & 1][0], w2 = wq[g & 1][1], w3 = wq[g & 1][2];
+            const u32x4 x1 = xs[s & 1][0], x2 = xs[s & 1][1], x3 = xs[s & 1][2];
+            acc[nt] = nd_mfma_bf16(w1, x1, acc[nt]);
+            acc[nt] = nd_mfma_bf16(w1, x2, acc[nt]);
+            acc[nt] = nd_mfma_bf16(w2, x1, acc[nt]);
+            acc[nt] = nd_mfma_bf16(w2, x2, acc[nt]);
+            acc[nt] = nd_mfma_bf16(w1, x3, acc[nt]);
+            acc[nt] = nd_mfma_bf16(w3, x1, acc[nt]);
             __builtin_amdgcn_sched_barrier(0);
         }
 }
@@ -174,7 +153,7 @@ __device__ __forceinline__ void chain_store_buf(const f32x16 (&acc)[N / 32], __a
         for (int g = 0; g < 4; ++g) {
             const int n0 = 32 * nt + 8 * g + 4 * half;
             const f32x4 v = {acc[nt][4 * g], acc[nt][4 * g + 1], acc[nt][4 * g + 2], acc[nt][4 * g + 3]};
-            __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4_t, v), rso, n0 < cout ? row_bytes + n0 * 4u : 0xFFFFFFF0u, 0, 0);
+            __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), rso, n0 < cout ? row_bytes + n0 * 4u : 0xFFFFFFF0u, 0, 0);
         }
 }
 
@@ -425,18 +404,11 @@ __global__ void pack_chain_split_kernel(const float* __restrict__ w, unsigned sh
         const int s = rest % (KP / 16), nt = rest / (KP / 16);
         const int n = 32 * nt + (l & 31), k = 16 * s + 8 * (i >> 2) + 4 * (l >> 5) + (i & 3);
         const float v = (n < cout && k < cin) ? w[(size_t)n * cin + k] : 0.0f;
-        const __bf16 t1 = (__bf16)v;
-        const float r1 = v - (float)t1;                       // exact
-        const __bf16 t2 = (__bf16)r1;
-        const float r2 = r1 - (float)t2;                      // exact, at most 8 significant bits: its upper half is the third term
+        const bf16_terms t = nd_split3_bf16(v);
         unsigned short* o = out + ((size_t)(nt * (KP / 16) + s) * 3 * 64 + l) * 8 + i;
-        o[0] = __builtin_bit_cast(unsigned short, t1);
-        o[512] = __builtin_bit_cast(unsigned short, t2);
-        o[1024] = (unsigned short)(__builtin_bit_cast(unsigned, r2) >> 16);
+        o[0] = t.t1;  o[512] = t.t2;  o[1024] = t.t3;
     }
 }
-
-static inline int device_cus() { return nd_device_cus(); }
 
 template <int K0, int N1, int N2, int N3, int MODE, bool SPLIT = false>
 int launch(const ChainArgs& a, hipStream_t st) {
@@ -446,7 +418,7 @@ int launch(const ChainArgs& a, hipStream_t st) {
     static_assert((size_t)(chain_w_floats<SPLIT>(N1, K0) + chain_w_floats<SPLIT>(N2, N1) + chain_w_floats<SPLIT>(N3, N2) + N1 + N2 + N3 + 2 * K0 + 16 * K0) * 4 <= 160 * 1024, "LDS");
     if (int e = nd_reserve_lds(configured, reinterpret_cast<const void*>(chain_kernel<K0, N1, N2, N3, MODE, SPLIT>), lds, "nd_pointwise_chain")) return e;
     const int wgs = nd_cdiv(a.n_tiles, WAVES);
-    const int grid = wgs < device_cus() ? wgs : device_cus();
+    const int grid = wgs < nd_device_cus() ? wgs : nd_device_cus();
     hipLaunchKernelGGL((chain_kernel<K0, N1, N2, N3, MODE, SPLIT>), dim3(grid), dim3(THREADS), lds, st, a);
     return 0;
 }

@@ -13,6 +13,7 @@
 // an image's slots in a fixed order (thread-strided, then a fixed tree), so a repeated call gives the same bits and an image's results
 // in a batch of any size equal its results alone.
 #include "nd_common.h"
+#include "block_sum.h"
 
 namespace {
 
@@ -23,24 +24,6 @@ constexpr int Q_LDS = QT_W + 8;           // one staged row: columns x0-4 .. x0+
 constexpr int Q_VEC_LANES = Q_LDS / 4;    // float4 loads per tensor and row
 constexpr int IL_THREADS = 256;
 constexpr int IL_CHUNK = IL_THREADS * 4 * 16;     // elements per illumination partial: 16 float4 per thread
-
-__device__ __forceinline__ float q_clip(float v, float hi) { return v < 0.0f ? 0.0f : (v > hi ? hi : v); }     // NaN passes through
-
-// Sum of two fp64 values over the 256 threads of the block, the same order every time: xor butterfly in each wave, then the four waves
-// in a fixed tree.  Every thread gets the result.
-__device__ __forceinline__ void q_block_sum2(double& a, double& b, double (*red)[4]) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        a += __shfl_xor(a, o);
-        b += __shfl_xor(b, o);
-    }
-    const int w = threadIdx.x >> 6;
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) { red[0][w] = a;  red[1][w] = b; }
-    __syncthreads();
-    a = (red[0][0] + red[0][1]) + (red[0][2] + red[0][3]);
-    b = (red[1][0] + red[1][1]) + (red[1][2] + red[1][3]);
-}
 
 // One (image, channel, QT_H x QT_W tile) per workgroup.  The block walks the tile's input rows y0-3 .. y1+2 top to bottom: every row is
 // staged in LDS (clipped, and illumination-corrected when `scale` is given), each lane forms the five horizontal 7-sums of its column
@@ -66,7 +49,7 @@ __global__ __launch_bounds__(QT_W) void quality_tile_kernel(const float* __restr
     const bool in_x = x < W, s_x = x >= Q_R && x < W - Q_R;
     const int rb = y0 - Q_R, re = y1 + Q_R;
 
-    auto fx = [&](float v) { return corr ? q_clip(k * q_clip(v, 1.0f), R) : q_clip(v, R); };
+    auto fx = [&](float v) { return corr ? nd_clip(k * nd_clip(v, 0.0f, 1.0f), 0.0f, R) : nd_clip(v, 0.0f, R); };
 
     // ---- the row loader: global -> registers (issued a row ahead), registers -> LDS
     f32x4 v4 = {0.0f, 0.0f, 0.0f, 0.0f};           // VEC: threads 0..65 hold est, 66..131 target
@@ -93,11 +76,11 @@ __global__ __launch_bounds__(QT_W) void quality_tile_kernel(const float* __restr
         if (VEC) {
             if (t < Q_VEC_LANES) nd_st4(&xs[buf][4 * t], f32x4{fx(v4[0]), fx(v4[1]), fx(v4[2]), fx(v4[3])});
             else if (t < 2 * Q_VEC_LANES)
-                nd_st4(&ys[buf][4 * (t - Q_VEC_LANES)], f32x4{q_clip(v4[0], R), q_clip(v4[1], R), q_clip(v4[2], R), q_clip(v4[3], R)});
+                nd_st4(&ys[buf][4 * (t - Q_VEC_LANES)], f32x4{nd_clip(v4[0], 0.0f, R), nd_clip(v4[1], 0.0f, R), nd_clip(v4[2], 0.0f, R), nd_clip(v4[3], 0.0f, R)});
         } else {
             xs[buf][t] = fx(e0);
-            ys[buf][t] = q_clip(g0, R);
-            if (t < Q_LDS - QT_W) { xs[buf][QT_W + t] = fx(e1);  ys[buf][QT_W + t] = q_clip(g1, R); }
+            ys[buf][t] = nd_clip(g0, 0.0f, R);
+            if (t < Q_LDS - QT_W) { xs[buf][QT_W + t] = fx(e1);  ys[buf][QT_W + t] = nd_clip(g1, 0.0f, R); }
         }
     };
 
@@ -149,7 +132,7 @@ __global__ __launch_bounds__(QT_W) void quality_tile_kernel(const float* __restr
             }
         }
     }
-    q_block_sum2(accS, accD, red);
+    block_sum_all(accS, accD, red);
     if (t == 0) {
         double* o = slots + ((size_t)b * C * nty * ntx + ((size_t)c * nty + ty) * ntx + tx) * 2;
         o[0] = accS;
@@ -157,7 +140,7 @@ __global__ __launch_bounds__(QT_W) void quality_tile_kernel(const float* __restr
     }
 }
 
-// One block per image: that image's `nslot` pairs summed thread-strided, then in q_block_sum2's tree.
+// One block per image: that image's `nslot` pairs summed thread-strided, then in block_sum_all's tree.
 __global__ __launch_bounds__(256) void quality_finalize_kernel(const double* __restrict__ slots, int nslot, double R2, double n_all,
                                                                double n_int, double* psnr, double* ssim, double* mse) {
     __shared__ double red[2][4];
@@ -168,7 +151,7 @@ __global__ __launch_bounds__(256) void quality_finalize_kernel(const double* __r
         aS += s[2 * i];
         aD += s[2 * i + 1];
     }
-    q_block_sum2(aS, aD, red);
+    block_sum_all(aS, aD, red);
     if (threadIdx.x == 0) {
         const double m = aD / n_all;
         mse[b] = m;
@@ -202,14 +185,14 @@ __global__ __launch_bounds__(IL_THREADS) void illum_partial_kernel(const float* 
         }
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
-            const double pc = q_clip(pv[e], 1.0f);
+            const double pc = nd_clip(pv[e], 0.0f, 1.0f);
             if (sv[e] != 1.0f) {
                 num = fma(pc, (double)sv[e], num);
                 den = fma(pc, pc, den);
             }
         }
     }
-    q_block_sum2(num, den, red);
+    block_sum_all(num, den, red);
     if (threadIdx.x == 0) {
         part[((size_t)b * nchunk + chunk) * 2] = num;
         part[((size_t)b * nchunk + chunk) * 2 + 1] = den;
@@ -225,7 +208,7 @@ __global__ __launch_bounds__(IL_THREADS) void illum_finalize_kernel(const double
         num += q[2 * i];
         den += q[2 * i + 1];
     }
-    q_block_sum2(num, den, red);
+    block_sum_all(num, den, red);
     if (threadIdx.x == 0) {
         const double kk = num / den;              // den 0: NaN or inf, as the reference
         k64[b] = kk;
@@ -243,11 +226,11 @@ __global__ __launch_bounds__(IL_THREADS) void illum_apply_kernel(const float* pr
     for (size_t i = start + 4 * threadIdx.x; i < end; i += 4 * IL_THREADS) {
         if (VEC) {
             const f32x4 v = nd_ld4(p + i);
-            nd_st4(o + i, f32x4{k * q_clip(v[0], 1.0f), k * q_clip(v[1], 1.0f), k * q_clip(v[2], 1.0f), k * q_clip(v[3], 1.0f)});
+            nd_st4(o + i, f32x4{k * nd_clip(v[0], 0.0f, 1.0f), k * nd_clip(v[1], 0.0f, 1.0f), k * nd_clip(v[2], 0.0f, 1.0f), k * nd_clip(v[3], 0.0f, 1.0f)});
         } else {
 #pragma unroll
             for (int e = 0; e < 4; ++e)
-                if (i + e < end) o[i + e] = k * q_clip(p[i + e], 1.0f);
+                if (i + e < end) o[i + e] = k * nd_clip(p[i + e], 0.0f, 1.0f);
         }
     }
 }

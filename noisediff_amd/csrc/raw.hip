@@ -30,7 +30,6 @@ constexpr int RW_THREADS = 256;
 constexpr uint32_t RW_NORMAL_BLOCK = 32u;           // the Philox block of the normal draw: PO_MAX_ATTEMPTS / 2, the first the Poisson draw leaves
 static_assert(RW_NORMAL_BLOCK == PO_MAX_ATTEMPTS / 2, "the normal draw takes the first block the Poisson draw cannot reach");
 
-__device__ __forceinline__ double rw_clipd(double v, double lo, double hi) { return v < lo ? lo : (v > hi ? hi : v); }
 
 // 2 V codes from p (4-byte aligned at least) as V words: the even Bayer column in the low half, the odd one in the high half
 template <int V>
@@ -266,7 +265,7 @@ __global__ __launch_bounds__(RW_THREADS) void raw_pg_kernel(PgArgs A) {
         const double g = s.sd * (double)nrm[i];
         double t = p + g;
         t = t * s.ratio64;
-        t = rw_clipd(t, 0.0, wbd);
+        t = nd_clip<double>(t, 0.0, wbd);
         t = t / wbd;
         noisy[i] = (float)t;
     }

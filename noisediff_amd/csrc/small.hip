@@ -1,6 +1,7 @@
 // small.hip -- the conditioning path (tiny dense ops on (B, K) rows), the two special
 // full-resolution layers with <= 4 input channels, and NCHW<->NHWC plumbing for the API tensors.
 #include "nd_common.h"
+#include "split_bf16.h"
 
 namespace {
 
@@ -205,35 +206,23 @@ __global__ __launch_bounds__(512, 1) void conv7x7_kernel(const float* __restrict
     }
 }
 
-// ---- the same stem on the bf16 matrix cores at full fp32 significand (r6: the split-product form of pointwise.hip / pwchain.hip).  K = 49 taps x 4 channels in
+// ---- the same stem on the bf16 matrix cores at full fp32 significand (r6: the split-product form of pointwise.hip / pwchain.hip, arithmetic in split_bf16.h).  K = 49 taps x 4 channels in
 // 13 K steps of 16 (4 taps x 4 channels; taps 49-51 carry zero weights): slot i of lane (column, half h) in K step s = tap 4 s + 2 h + (i >> 2), channel i & 3.
 // The weights of a wave's 32 couts sit in registers as three bf16 terms (13 x 3 x 4 = 156 registers, two waves per SIMD); the halo tile is split ONCE per element when
 // it is staged into LDS term planes [term][pixel][4 x bf16]; a lane's operand of a K step is two 8-byte reads per term.  13 x 6 MFMAs of 32 cycles per 32-pixel row and
 // 32 couts against 98 of 64.
-typedef __bf16 c7_bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 c7_bf16x2 __attribute__((ext_vector_type(2)));
-typedef unsigned c7_u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned c7_u32x2 __attribute__((ext_vector_type(2)));
 constexpr int C7_KS = 13;
 
-__device__ __forceinline__ void c7_split2(float x, float y, unsigned& w1, unsigned& w2, unsigned& w3) {
-    w1 = __builtin_bit_cast(unsigned, __builtin_convertvector(f32x2{x, y}, c7_bf16x2));
-    const float rx = x - __builtin_bit_cast(float, w1 << 16), ry = y - __builtin_bit_cast(float, w1 & 0xFFFF0000u);
-    w2 = __builtin_bit_cast(unsigned, __builtin_convertvector(f32x2{rx, ry}, c7_bf16x2));
-    const float sx = rx - __builtin_bit_cast(float, w2 << 16), sy = ry - __builtin_bit_cast(float, w2 & 0xFFFF0000u);
-    w3 = __builtin_amdgcn_perm(__builtin_bit_cast(unsigned, sy), __builtin_bit_cast(unsigned, sx), 0x07060302u);
-}
-
 template <int NT>
-__global__ __launch_bounds__(512, 1) void conv7x7_split_kernel(const float* __restrict__ x, const c7_u32x4* __restrict__ wp, const float* __restrict__ bias,
+__global__ __launch_bounds__(512, 1) void conv7x7_split_kernel(const float* __restrict__ x, const u32x4* __restrict__ wp, const float* __restrict__ bias,
                                                                float* __restrict__ out, int ldo, int B, int H, int W, int cout) {
     constexpr int NPX = C7_HH * C7_HW;
-    __shared__ __attribute__((aligned(16))) c7_u32x2 tile[3][NPX];                 // term planes: a pixel's four channels as bf16 = 8 bytes
+    __shared__ __attribute__((aligned(16))) u32x2 tile[3][NPX];                    // term planes: a pixel's four channels as bf16 = 8 bytes
     constexpr int RG = 8 / NT;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, half = lane >> 5, col = lane & 31;
     const int nt = wave % NT, rg = wave / NT;
     // ---- this wave's weight terms: [cout tile][K step][term][lane] x 16 bytes
-    c7_u32x4 wq[C7_KS][3];
+    u32x4 wq[C7_KS][3];
 #pragma unroll
     for (int s = 0; s < C7_KS; ++s)
 #pragma unroll
@@ -266,11 +255,11 @@ __global__ __launch_bounds__(512, 1) void conv7x7_split_kernel(const float* __re
             f32x4 v = {0, 0, 0, 0};
             if (y >= 0 && y < H && xx >= 0 && xx < W) v = nd_ld4(x + ((size_t)(b * H + y) * W + xx) * 4);
             unsigned a1, a2, a3, b1, b2, b3;
-            c7_split2(v.x, v.y, a1, a2, a3);
-            c7_split2(v.z, v.w, b1, b2, b3);
-            tile[0][i] = c7_u32x2{a1, b1};
-            tile[1][i] = c7_u32x2{a2, b2};
-            tile[2][i] = c7_u32x2{a3, b3};
+            nd_split2_bf16(v.x, v.y, a1, a2, a3);
+            nd_split2_bf16(v.z, v.w, b1, b2, b3);
+            tile[0][i] = u32x2{a1, b1};
+            tile[1][i] = u32x2{a2, b2};
+            tile[2][i] = u32x2{a3, b3};
         }
         __syncthreads();
         for (int ly = rg; ly < C7_TH; ly += RG) {
@@ -282,13 +271,13 @@ __global__ __launch_bounds__(512, 1) void conv7x7_split_kernel(const float* __re
             const int p = ly * C7_HW + col;
 #pragma unroll
             for (int s = 0; s < C7_KS; ++s) {
-                c7_u32x4 xv[3];
+                u32x4 xv[3];
 #pragma unroll
                 for (int tm = 0; tm < 3; ++tm) {
-                    const c7_u32x2 lo = tile[tm][p + toff[s][0]], hi = tile[tm][p + toff[s][1]];
-                    xv[tm] = c7_u32x4{lo.x, lo.y, hi.x, hi.y};
+                    const u32x2 lo = tile[tm][p + toff[s][0]], hi = tile[tm][p + toff[s][1]];
+                    xv[tm] = u32x4{lo.x, lo.y, hi.x, hi.y};
                 }
-#define C7_MFMA(wt, xt) acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(c7_bf16x8, wq[s][wt]), __builtin_bit_cast(c7_bf16x8, xv[xt]), acc, 0, 0, 0)
+#define C7_MFMA(wt, xt) acc = nd_mfma_bf16(wq[s][wt], xv[xt], acc)
                 C7_MFMA(0, 0);  C7_MFMA(0, 1);  C7_MFMA(1, 0);  C7_MFMA(1, 1);  C7_MFMA(0, 2);  C7_MFMA(2, 0);
 #undef C7_MFMA
             }
@@ -319,14 +308,9 @@ __global__ void pack_conv7x7_split_kernel(const float* __restrict__ w, unsigned 
         const int s = rest % C7_KS, tile = rest / C7_KS;
         const int n = 32 * tile + (l & 31), tap = 4 * s + 2 * (l >> 5) + (i >> 2), c = i & 3;
         const float v = (n < cout && tap < 49) ? w[((size_t)n * 4 + c) * 49 + tap] : 0.0f;
-        const __bf16 t1 = (__bf16)v;
-        const float r1 = v - (float)t1;
-        const __bf16 t2 = (__bf16)r1;
-        const float r2 = r1 - (float)t2;
+        const bf16_terms t = nd_split3_bf16(v);
         unsigned short* o = out + ((size_t)((tile * C7_KS + s) * 3) * 64 + l) * 8 + i;
-        o[0] = __builtin_bit_cast(unsigned short, t1);
-        o[512] = __builtin_bit_cast(unsigned short, t2);
-        o[1024] = (unsigned short)(__builtin_bit_cast(unsigned, r2) >> 16);
+        o[0] = t.t1;  o[512] = t.t2;  o[1024] = t.t3;
     }
 }
 
@@ -635,7 +619,7 @@ extern "C" int nd_conv7x7_c4_split_f32(const float* x, const float* wsplit, cons
     const int cus = nd_device_cus();
     const dim3 grid((unsigned)(tiles < cus ? tiles : cus)), block(512);
     const int ntiles = nd_cdiv(cout, 32);
-    const c7_u32x4* wq = reinterpret_cast<const c7_u32x4*>(wsplit);
+    const u32x4* wq = reinterpret_cast<const u32x4*>(wsplit);
 #define ND_C7S_LAUNCH(NT) hipLaunchKernelGGL(conv7x7_split_kernel<NT>, grid, block, 0, (hipStream_t)stream, x, wq, bias, out, ldo, B, H, W, cout)
     if (ntiles <= 1) ND_C7S_LAUNCH(1);
     else if (ntiles <= 2) ND_C7S_LAUNCH(2);

@@ -36,7 +36,7 @@ CASES = {
 UPSAMPLE_TWIN = {"one_over": (2, 18, 34, 24, 68), "ragged": (2, 20, 36, 40, 20), "deep": (1, 16, 16, 512, 64)}   # even-sized twins for nearest-x2 addressing
 PROLOGUES = ("none", "affine", "map", "map_blocked", "genmap", "leaky", "leaky_second", "concat", "upsample")
 
-# Lavin & Gray; m = 4 as in conv3x3_wino4.hip's header comment, m = 2 as conv3x3_wino.hip's bt_* / at_coef
+# Lavin & Gray; m = 4 as in conv3x3_wino4.hip's header comment, m = 2 as csrc/wino2x2.h's bt_* / at_coef
 WINO = {
     4: ([[4, 0, -5, 0, 1, 0], [0, -4, -4, 1, 1, 0], [0, 4, -4, -1, 1, 0], [0, -2, -1, 2, 1, 0], [0, 2, -1, -2, 1, 0], [0, 4, 0, -5, 0, 1]],
         [[1 / 4, 0, 0], [-1 / 6, -1 / 6, -1 / 6], [-1 / 6, 1 / 6, -1 / 6], [1 / 24, 1 / 12, 1 / 6], [1 / 24, -1 / 12, 1 / 6], [0, 0, 1]],
