@@ -571,6 +571,27 @@ int nd_pointwise_gemm_split_takes(const nd_pointwise* d);
 int64_t nd_pack_pointwise_weight_split_floats(int cin, int cout);
 int nd_pack_pointwise_weight_split(const float* w, float* packed, int cin, int cout, void* stream);
 
+/* Two 1x1 layers with nothing between them but an addition, the second one narrow (cout 4 or 8), as ONE streaming dot product -- the end of the
+ * U-Net, final_conv(res_conv(cat(xp, x0)) + silu(GN(c2))) + shot (Diffusion_arch.py:156,170,554,644):
+ *   out[p] = W [p0[p]; p1[p]; silu((t[p] - M[b]) * A[b] + D[b])] + bias [+ res0[p]],    W = [Wf Wr | Wf],  bias = Wf br + bf
+ * `weight` / `bias` are nd_pack_narrow_fold's outputs ([cin/4][cout][4] and [cout], cin = c0 + c1 + c2 = cin_r + mid): the mid-term sums of
+ * Wf (cout, mid) times Wr (mid, cin_r) and of Wf br + bf are formed in fp64 and rounded once to fp32; nd_pack_narrow_fold_floats: the floats of
+ * `weight`.  mad: [B][3][c2] as nd_groupnorm_finalize_f32 writes it.  Any pixel count.  Takes (nd_pointwise_narrow_fold_takes): channel counts
+ * in fours, p1 optional (c1 = 0), cout 4 or 8, cin * cout <= 8192; anything else: ND_E_SHAPE.  Strides multiples of 4, pointers 16-byte aligned. */
+typedef struct nd_narrow_fold {
+    const float* p0; const float* p1;   /* plain sources [B][HW] x ld0 / ld1 (c0 / c1 channels); p1 NULL iff c1 == 0 */
+    const float* t;  const float* mad;  /* the activated source x ldt (c2 channels) and its per-sample M | A | D     */
+    const float* weight; const float* bias;
+    const float* res0;                  /* [B][HW] x ldr0 or NULL                                                    */
+    float*   out;
+    int32_t  B, HW, c0, c1, c2, ld0, ld1, ldt, cout, ldo, ldr0, reserved;
+} nd_narrow_fold;
+int nd_pointwise_narrow_fold_nhwc_f32(const nd_narrow_fold* d, void* stream);
+int nd_pointwise_narrow_fold_takes(int c0, int c1, int c2, int cout);
+int64_t nd_pack_narrow_fold_floats(int cin, int cout);
+int nd_pack_narrow_fold(const float* wf, const float* bf, const float* wr, const float* br, float* w_out, float* b_out, int cin_r, int mid, int cout,
+                        void* stream);
+
 /* ------------------------------------------------------------------ chained pointwise layers
  * Two or three per-pixel Linear layers in one kernel, the intermediate activations never leaving registers:
  *   Mlp (Diffusion_arch.py:340-356):            out = fc2(act(fc1(x)))
@@ -605,6 +626,20 @@ int nd_pack_chain_weight(const float* w, float* packed, int cin, int cout, int f
 int nd_pointwise_chain_split_nhwc_f32(const nd_chain* d, void* stream);
 int64_t nd_pack_chain_weight_split_floats(int cin, int cout, int first_stage);
 int nd_pack_chain_weight_split(const float* w, float* packed, int cin, int cout, int first_stage, void* stream);
+/* A two-stage split chain behind a ResnetBlock tail (the shot-noise branch's end, shot_mlp3(shot_time(s2) + r): Diffusion_arch.py:168-170,603-604):
+ * the chain's input row is  silu((t - M[b]) * A[b] + D[b]) + r0 [+ r1]  with t = chain.src.p0 (one plain source, ND_PRO_NONE, no vec), mad [B][3][cin]
+ * as nd_groupnorm_finalize_f32 writes it -- what nd_affine_silu_add_f32 would store and the chain read back.  Stages without residuals; weights are
+ * nd_pack_chain_weight_split packings.  Widths: cin 64 or 48, first stage up to 64 wide, second up to 32 (nd_pointwise_chain_tail_takes, n3 = 0);
+ * anything else is refused with ND_E_SHAPE -- run the two launches.  HW a multiple of 32, tensors below 4 GiB, strides multiples of 4. */
+typedef struct nd_chain_tail {
+    nd_chain chain;
+    const float* mad;
+    const float* r0;       /* [B][HW] x ldr0 */
+    const float* r1;       /* [B][HW] x ldr1 or NULL */
+    int32_t  ldr0, ldr1;
+} nd_chain_tail;
+int nd_pointwise_chain_tail_split_nhwc_f32(const nd_chain_tail* d, void* stream);
+int nd_pointwise_chain_tail_takes(int cin, int n1, int n2, int n3);
 
 /* ------------------------------------------------------------------ GroupNorm plumbing */
 

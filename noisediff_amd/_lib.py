@@ -66,6 +66,16 @@ class Chain(C.Structure):
                 ("ldo", C.c_int32)]
 
 
+class ChainTail(C.Structure):
+    _fields_ = [("chain", Chain), ("mad", fptr), ("r0", fptr), ("r1", fptr), ("ldr0", C.c_int32), ("ldr1", C.c_int32)]
+
+
+class NarrowFold(C.Structure):
+    _fields_ = [("p0", fptr), ("p1", fptr), ("t", fptr), ("mad", fptr), ("weight", fptr), ("bias", fptr), ("res0", fptr), ("out", fptr),
+                ("B", C.c_int32), ("HW", C.c_int32), ("c0", C.c_int32), ("c1", C.c_int32), ("c2", C.c_int32), ("ld0", C.c_int32), ("ld1", C.c_int32),
+                ("ldt", C.c_int32), ("cout", C.c_int32), ("ldo", C.c_int32), ("ldr0", C.c_int32), ("reserved", C.c_int32)]
+
+
 class RawSample(C.Structure):
     _fields_ = [("frame", C.c_int32), ("frame_clean", C.c_int32), ("x0", C.c_int32), ("y0", C.c_int32), ("flip", C.c_int32),
                 ("branch", C.c_int32), ("iso", C.c_float), ("ratio", C.c_float), ("blc", C.c_float), ("reserved", C.c_int32),
@@ -149,6 +159,12 @@ SIGNATURES = {
     "nd_pointwise_gemm_split_takes": (i32, [C.POINTER(Pointwise)]),
     "nd_pack_pointwise_weight_split_floats": (i64, [i32, i32]),
     "nd_pack_pointwise_weight_split": (i32, [vp, vp, i32, i32, vp]),
+    "nd_pointwise_chain_tail_split_nhwc_f32": (i32, [C.POINTER(ChainTail), vp]),
+    "nd_pointwise_chain_tail_takes": (i32, [i32, i32, i32, i32]),
+    "nd_pointwise_narrow_fold_nhwc_f32": (i32, [C.POINTER(NarrowFold), vp]),
+    "nd_pointwise_narrow_fold_takes": (i32, [i32, i32, i32, i32]),
+    "nd_pack_narrow_fold_floats": (i64, [i32, i32]),
+    "nd_pack_narrow_fold": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, i32, vp]),
     "nd_pack_pointwise_weight_floats": (i64, [i32, i32]),
     "nd_pack_pointwise_weight": (i32, [vp, vp, i32, i32, i32, vp]),
     "nd_pack_pointwise_weight_t": (i32, [vp, vp, i32, i32, vp]),
@@ -263,7 +279,7 @@ SIGNATURES = {
     "nd_raw_diffusion_batch_f32": (i32, [vp, i32, i32, i32, vp, f32, f32, vp, vp, vp, vp, i32, i32, i32, vp]),
 }
 
-_UNCHECKED = {"nd_version", "nd_last_error", "nd_stream_device", "nd_conv3x3_wgrad_form", "nd_adam_chunk_elements", "nd_ema_chunk_elements", "nd_conv7x7_c4_wgrad_workspace_floats", "nd_conv3x3_stat_slots", "nd_conv3x3_tiling_id", "nd_pack_conv3x3_weight_floats",
+_UNCHECKED = {"nd_pointwise_chain_tail_takes", "nd_pointwise_narrow_fold_takes", "nd_pack_narrow_fold_floats", "nd_version", "nd_last_error", "nd_stream_device", "nd_conv3x3_wgrad_form", "nd_adam_chunk_elements", "nd_ema_chunk_elements", "nd_conv7x7_c4_wgrad_workspace_floats", "nd_conv3x3_stat_slots", "nd_conv3x3_tiling_id", "nd_pack_conv3x3_weight_floats",
               "nd_pack_pointwise_weight_floats", "nd_linear_attention_workspace_floats", "nd_conv3x3_wino_stat_slots", "nd_conv3x3_wino4_stat_slots",
               "nd_pack_conv3x3_wino_weight_floats", "nd_pack_conv3x3_wino4_weight_floats", "nd_conv3x3_wino4_splitk_plan", "nd_conv3x3_wino4_16_splitk_plan", "nd_conv3x3_wino4_splitk_workspace_floats", "nd_token_sum_workspace_floats", "nd_cond_step_lds_bytes", "nd_conv3x3_wgrad_workspace_floats",
               "nd_groupnorm_train_workspace_floats", "nd_linear_wgrad_workspace_floats",

@@ -918,6 +918,124 @@ __global__ __launch_bounds__(256) void pointwise_narrow_kernel(const PwArgs a) {
     }
 }
 
+// ---- the trunk's end folded (nd_pointwise_narrow_fold_nhwc_f32): final_conv(res_conv(cat(xp, x0)) + silu(GN(c2))) + shot is linear in its three sources,
+//   out = (Wf Wr) [xp; x0] + Wf silu((c2 - M) A + D) + (Wf br + bf) + shot,
+// a narrow dot product over c0 + c1 + c2 channels with the GroupNorm-affine + SiLU applied to the third source as it is loaded: no 128 -> 64 GEMM and no 64-channel
+// tensor between the two layers.  Lane scheme of pointwise_narrow_kernel (four lanes per pixel, folded weights [cin/4][CO][4] in LDS, two DPP steps); every lane
+// carries TWO pixels (64 apart), so a weight read from LDS feeds two rows -- at 3 d input channels the LDS reads of one pixel per lane take as long as the stream.
+template <int CO>
+__device__ __forceinline__ void nf_fma(float (&acc)[CO], const f32x4 x, const float* wq) {
+#pragma unroll
+    for (int n = 0; n < CO; ++n) {
+        const f32x4 w = nd_ld4(wq + n * 4);
+        acc[n] = fmaf(x.w, w.w, fmaf(x.z, w.z, fmaf(x.y, w.y, fmaf(x.x, w.x, acc[n]))));
+    }
+}
+
+template <int CO>
+__global__ __launch_bounds__(256) void pointwise_narrow_fold_kernel(const nd_narrow_fold d) {
+    extern __shared__ __attribute__((aligned(16))) float wl[];      // (c0 + c1 + c2) / 4 x CO x 4 floats
+    const int tid = threadIdx.x, part = tid & 3;
+    const int nq0 = d.c0 >> 2, nq1 = d.c1 >> 2, nq2 = d.c2 >> 2;
+    for (int i = tid; i < (nq0 + nq1 + nq2) * CO; i += 256) nd_st4(wl + i * 4, nd_ld4(d.weight + (size_t)i * 4));
+    __syncthreads();
+    const long P = (long)d.B * d.HW;
+    for (long base = (long)blockIdx.x * 128; base < P; base += (long)gridDim.x * 128) {
+        long pix[2], pc[2];
+        float acc[2][CO];
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+            pix[j] = base + 64 * j + (tid >> 2);
+            pc[j] = pix[j] < P ? pix[j] : P - 1;               // (clamped: every lane takes part in the DPP steps)
+#pragma unroll
+            for (int n = 0; n < CO; ++n) acc[j][n] = 0.0f;
+        }
+        {
+            const float* ra = d.p0 + pc[0] * d.ld0;
+            const float* rb = d.p0 + pc[1] * d.ld0;
+#pragma unroll 4
+            for (int q = part; q < nq0; q += 4) {
+                const f32x4 xa = nd_ld4(ra + 4 * q), xb = nd_ld4(rb + 4 * q);
+                nf_fma<CO>(acc[0], xa, wl + q * CO * 4);
+                nf_fma<CO>(acc[1], xb, wl + q * CO * 4);
+            }
+        }
+        if (nq1 > 0) {
+            const float* ra = d.p1 + pc[0] * d.ld1;
+            const float* rb = d.p1 + pc[1] * d.ld1;
+#pragma unroll 4
+            for (int q = part; q < nq1; q += 4) {
+                const f32x4 xa = nd_ld4(ra + 4 * q), xb = nd_ld4(rb + 4 * q);
+                nf_fma<CO>(acc[0], xa, wl + (nq0 + q) * CO * 4);
+                nf_fma<CO>(acc[1], xb, wl + (nq0 + q) * CO * 4);
+            }
+        }
+        {
+            const float* ra = d.t + pc[0] * d.ldt;
+            const float* rb = d.t + pc[1] * d.ldt;
+            const float* ma = d.mad + (pc[0] / d.HW) * 3 * d.c2;      // M | A | D of the pixel's sample (gn_finalize's layout)
+            const float* mb = d.mad + (pc[1] / d.HW) * 3 * d.c2;
+#pragma unroll 4
+            for (int q = part; q < nq2; q += 4) {
+                const f32x4 ta = nd_ld4(ra + 4 * q), tb = nd_ld4(rb + 4 * q);
+                const f32x4 xa = nd_silu4((ta - nd_ld4(ma + 4 * q)) * nd_ld4(ma + d.c2 + 4 * q) + nd_ld4(ma + 2 * d.c2 + 4 * q));
+                const f32x4 xb = nd_silu4((tb - nd_ld4(mb + 4 * q)) * nd_ld4(mb + d.c2 + 4 * q) + nd_ld4(mb + 2 * d.c2 + 4 * q));
+                nf_fma<CO>(acc[0], xa, wl + (nq0 + nq1 + q) * CO * 4);
+                nf_fma<CO>(acc[1], xb, wl + (nq0 + nq1 + q) * CO * 4);
+            }
+        }
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+#pragma unroll
+            for (int n = 0; n < CO; ++n) {                    // parts 0 + 1, 2 + 3, then the two pairs (quad_perm [1 0 3 2], [2 3 0 1])
+                acc[j][n] += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(acc[j][n]), 0xB1, 0xF, 0xF, true));
+                acc[j][n] += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(acc[j][n]), 0x4E, 0xF, 0xF, true));
+            }
+            if (part == 0 && pix[j] < P) {
+#pragma unroll
+                for (int q = 0; q < CO / 4; ++q) {
+                    f32x4 v = {acc[j][4 * q], acc[j][4 * q + 1], acc[j][4 * q + 2], acc[j][4 * q + 3]};
+                    v += nd_ld4(d.bias + 4 * q);
+                    if (d.res0) v += nd_ld4(d.res0 + pix[j] * d.ldr0 + 4 * q);
+                    nd_st4(d.out + pix[j] * d.ldo + 4 * q, v);
+                }
+            }
+        }
+    }
+}
+
+// The fold itself, once per weight load: w_out [(cin_r + mid) / 4][CO][4] and b_out [CO] (CO = cout rounded up to 4, the kernel's LDS image) from the two layers'
+// torch-layout weights -- Wf (cout, mid), Wr (mid, cin_r).  Column k < cin_r: sum_j Wf[n][j] Wr[j][k] (the mid-term sums in fp64, rounded ONCE to fp32);
+// column cin_r + j: Wf[n][j] as it is; bias: Wf br + bf the same way.
+__global__ void pack_narrow_fold_kernel(const float* __restrict__ wf, const float* __restrict__ bf, const float* __restrict__ wr, const float* __restrict__ br,
+                                        float* __restrict__ w_out, float* __restrict__ b_out, int cin_r, int mid, int cout, int CO) {
+    const int total = (cin_r + mid) * CO;
+    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < total + CO; i += gridDim.x * blockDim.x) {
+        if (i >= total) {
+            const int n = i - total;
+            double s = 0.0;
+            if (n < cout) {
+                for (int j = 0; j < mid; ++j) s += (double)wf[(size_t)n * mid + j] * (double)(br ? br[j] : 0.0f);
+                s += (double)(bf ? bf[n] : 0.0f);
+            }
+            b_out[n] = (float)s;
+            continue;
+        }
+        const int e = i & 3, r = i >> 2, n = r % CO, k = (r / CO) * 4 + e;
+        float v = 0.0f;
+        if (n < cout) {
+            if (k < cin_r) {
+                double s = 0.0;
+                for (int j = 0; j < mid; ++j) s += (double)wf[(size_t)n * mid + j] * (double)wr[(size_t)j * cin_r + k];
+                v = (float)s;
+            } else {
+                v = wf[(size_t)n * mid + (k - cin_r)];
+            }
+        }
+        w_out[i] = v;
+    }
+}
+
 // (cout, cin) -> [cinP/4][coutP][4], optional K permutation for pixel-unshuffled inputs
 // transposed: `w` is (cin, cout) row-major -- the forward weight of the Linear whose DATA gradient dx = dy @ W this packing serves
 __global__ void pack_pointwise_kernel(const float* __restrict__ w, float* __restrict__ out,
@@ -1220,6 +1338,43 @@ extern "C" int nd_pointwise_gemm_unshuffle_crop_nhwc_f32(const nd_pointwise* d, 
 extern "C" int nd_pointwise_gemm_split_nhwc_f32(const nd_pointwise* d, void* stream) { return pw_run(d, stream, true); }
 
 extern "C" int nd_pointwise_gemm_split_takes(const nd_pointwise* d) { return d && pw_split_takes(d) ? 1 : 0; }
+
+// ---- two 1x1 layers with only an addition between them, the second one narrow, as ONE streaming dot product (pointwise_narrow_fold_kernel above)
+extern "C" int nd_pointwise_narrow_fold_takes(int c0, int c1, int c2, int cout) {
+    return c0 > 0 && c1 >= 0 && c2 > 0 && c0 % 4 == 0 && c1 % 4 == 0 && c2 % 4 == 0 && (cout == 4 || cout == 8) && (long)(c0 + c1 + c2) * cout <= 8192;   // weights <= 32 KB of LDS
+}
+
+extern "C" int64_t nd_pack_narrow_fold_floats(int cin, int cout) { return (int64_t)nd_round_up(cin, 4) * nd_round_up(cout, 4); }
+
+extern "C" int nd_pack_narrow_fold(const float* wf, const float* bf, const float* wr, const float* br, float* w_out, float* b_out, int cin_r, int mid, int cout,
+                                   void* stream) {
+    ND_REQUIRE(wf && wr && w_out && b_out, ND_E_BADARG, "nd_pack_narrow_fold: null pointer");
+    ND_REQUIRE(cin_r > 0 && mid > 0 && cout > 0 && cin_r % 4 == 0 && mid % 4 == 0, ND_E_SHAPE, "nd_pack_narrow_fold: %d -> %d -> %d (widths of the wide layer in fours)", cin_r, mid, cout);
+    const int CO = nd_round_up(cout, 4), total = (cin_r + mid) * CO + CO;
+    hipLaunchKernelGGL(pack_narrow_fold_kernel, dim3(nd_cdiv(total, 256)), dim3(256), 0, (hipStream_t)stream, wf, bf, wr, br, w_out, b_out, cin_r, mid, cout, CO);
+    return nd_launch_status("nd_pack_narrow_fold");
+}
+
+extern "C" int nd_pointwise_narrow_fold_nhwc_f32(const nd_narrow_fold* d, void* stream) {
+    ND_REQUIRE(d, ND_E_BADARG, "nd_pointwise_narrow_fold: null descriptor");
+    ND_REQUIRE(d->p0 && d->t && d->mad && d->weight && d->bias && d->out, ND_E_BADARG, "nd_pointwise_narrow_fold: null tensor pointer");
+    ND_REQUIRE(d->B > 0 && d->HW > 0 && (long)d->B * d->HW < (1L << 31), ND_E_BADARG, "nd_pointwise_narrow_fold: B = %d, HW = %d", d->B, d->HW);
+    ND_REQUIRE((d->c1 == 0) == (d->p1 == nullptr), ND_E_BADARG, "nd_pointwise_narrow_fold: p1/c1 mismatch");
+    ND_REQUIRE(nd_pointwise_narrow_fold_takes(d->c0, d->c1, d->c2, d->cout), ND_E_SHAPE,
+               "nd_pointwise_narrow_fold: %d + %d + %d -> %d is not a shape of this kernel (channels in fours, cout 4 or 8, cin * cout <= 8192: "
+               "nd_pointwise_narrow_fold_takes)", d->c0, d->c1, d->c2, d->cout);
+    ND_REQUIRE(d->ld0 >= d->c0 && (d->c1 == 0 || d->ld1 >= d->c1) && d->ldt >= d->c2 && d->ldo >= d->cout && (!d->res0 || d->ldr0 >= d->cout), ND_E_SHAPE,
+               "nd_pointwise_narrow_fold: a pixel stride below its channel count");
+    ND_REQUIRE(d->ld0 % 4 == 0 && d->ld1 % 4 == 0 && d->ldt % 4 == 0 && d->ldo % 4 == 0 && d->ldr0 % 4 == 0, ND_E_ALIGN, "nd_pointwise_narrow_fold: pixel strides must be multiples of 4");
+    ND_REQUIRE(nd_aligned16(d->p0) && nd_aligned16(d->p1) && nd_aligned16(d->t) && nd_aligned16(d->mad) && nd_aligned16(d->weight) && nd_aligned16(d->bias) &&
+               nd_aligned16(d->res0) && nd_aligned16(d->out), ND_E_ALIGN, "nd_pointwise_narrow_fold: pointers must be 16-byte aligned");
+    const long blocks = ((long)d->B * d->HW + 127) / 128;
+    const int grid = (int)(blocks < 8L * nd_device_cus() ? blocks : 8L * nd_device_cus());
+    const size_t lds = (size_t)(d->c0 + d->c1 + d->c2) * d->cout * sizeof(float);
+    if (d->cout == 4) hipLaunchKernelGGL((pointwise_narrow_fold_kernel<4>), dim3(grid), dim3(256), lds, (hipStream_t)stream, *d);
+    else hipLaunchKernelGGL((pointwise_narrow_fold_kernel<8>), dim3(grid), dim3(256), lds, (hipStream_t)stream, *d);
+    return nd_launch_status("nd_pointwise_narrow_fold_nhwc_f32");
+}
 
 extern "C" int64_t nd_pack_pointwise_weight_split_floats(int cin, int cout) {
     return (int64_t)nd_round_up(cin, 32) * nd_round_up(cout, 128) * 3 / 2;       // three bf16 terms per value, counted in floats (the arena's unit)

@@ -34,6 +34,11 @@ struct ChainArgs {
     nd_chain d;
     int n_tiles;            // 32-pixel tiles in total
     int tiles_per_sample;
+    // TAIL instances (nd_pointwise_chain_tail_split_nhwc_f32): the input row is silu((t - M[b]) A[b] + D[b]) + r0 (+ r1), t = src.p0
+    const float* mad;       // [B][3][cin]
+    const float* r0;
+    const float* r1;        // or null
+    int ldr0, ldr1;
 };
 
 template <int K, int N>
@@ -190,10 +195,14 @@ __device__ unsigned long long chain_dbg[4096 * 16 * 10];
 // floats of LDS a stage's weights take: fp32 operands, or three bf16 terms (6 bytes per value)
 template <bool SPLIT> constexpr int chain_w_floats(int n, int k) { return SPLIT ? n * k * 3 / 2 : n * k; }
 
-template <int K0, int N1, int N2, int N3, int MODE, bool SPLIT = false>
+// TAIL (SPLIT only): a ResnetBlock tail as the chain's prologue -- the row is silu((t - M[b]) A[b] + D[b]) + r0 (+ r1) with t = src.p0 the block's second conv
+// output and M | A | D the per-sample GroupNorm affine (kept in the wave's LDS stash like `vec`, reloaded when the sample changes); the two residual rows are
+// prefetched with the t row, through buffer resources like every access of the tile loop (an absent r1 is a resource of zero records: its loads return 0).
+template <int K0, int N1, int N2, int N3, int MODE, bool SPLIT = false, bool TAIL = false>
 __global__ __launch_bounds__(chain_threads(N1, SPLIT, K0), 1) void chain_kernel(const ChainArgs a) {
     constexpr int THREADS = chain_threads(N1, SPLIT, K0), WAVES = THREADS / 64;
     static_assert(!SPLIT || K0 % 16 == 0, "SPLIT: the first stage reads whole 16-channel K steps");
+    static_assert(!TAIL || (SPLIT && MODE == ND_PRO_NONE), "TAIL: a prologue of the SPLIT form");
     extern __shared__ __attribute__((aligned(16))) float lds[];
     float* w1 = lds;
     float* w2 = w1 + chain_w_floats<SPLIT>(N1, K0);
@@ -204,6 +213,7 @@ __global__ __launch_bounds__(chain_threads(N1, SPLIT, K0), 1) void chain_kernel(
     float* gam = b3 + (N3 > 0 ? N3 : 0);
     float* bet = gam + K0;
     float* vst = bet + K0;                                // [WAVES][K0]: this wave's per-sample vector
+    float* mst = vst + WAVES * K0;                        // TAIL: [WAVES][3][K0]: this wave's per-sample M | A | D
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, half = lane >> 5;
     const nd_src& s = a.d.src;
@@ -236,6 +246,7 @@ __global__ __launch_bounds__(chain_threads(N1, SPLIT, K0), 1) void chain_kernel(
     const int n_waves = gridDim.x * WAVES, wid = blockIdx.x * WAVES + wave;
     const int t_begin = (int)((long)wid * a.n_tiles / n_waves), t_end = (int)((long)(wid + 1) * a.n_tiles / n_waves);
     float* myv = vst + wave * K0;
+    float* mym = mst + wave * 3 * K0;
     int b_cur = -1;
     const int cout_last = a.d.st[N3 > 0 ? 2 : 1].cout;
 
@@ -249,7 +260,12 @@ __global__ __launch_bounds__(chain_threads(N1, SPLIT, K0), 1) void chain_kernel(
     const __amdgpu_buffer_rsrc_t rs1 = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(s.p1 ? s.p1 : s.p0), 0,
                                                                           s.p1 ? (int)((unsigned)a.d.B * a.d.HW * s.ld1 * 4u) : 0, 0x00020000);
     const __amdgpu_buffer_rsrc_t rso = __builtin_amdgcn_make_buffer_rsrc(a.d.out, 0, (int)((unsigned)a.d.B * a.d.HW * a.d.ldo * 4u), 0x00020000);
+    const __amdgpu_buffer_rsrc_t rr0 = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(TAIL ? a.r0 : s.p0), 0,
+                                                                          TAIL ? (int)((unsigned)a.d.B * a.d.HW * a.ldr0 * 4u) : 0, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rr1 = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(TAIL && a.r1 ? a.r1 : s.p0), 0,
+                                                                          TAIL && a.r1 ? (int)((unsigned)a.d.B * a.d.HW * a.ldr1 * 4u) : 0, 0x00020000);
     f32x4 Xn[SPLIT ? K0 / 8 : 1], Xm[TWO ? K0 / 8 : 1];     // SPLIT: the next tile's rows, in flight over this tile's stages
+    f32x4 R0n[TAIL ? K0 / 8 : 1], R1n[TAIL ? K0 / 8 : 1];   // TAIL: ... and its two residual rows
     auto prefetch_rows = [&](int t_) {
         const unsigned pix_ = (unsigned)t_ * 32u + (unsigned)(lane & 31);
 #pragma unroll
@@ -258,6 +274,10 @@ __global__ __launch_bounds__(chain_threads(N1, SPLIT, K0), 1) void chain_kernel(
             Xn[SPLIT ? q : 0] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs0, c < s.c0 ? (pix_ * (unsigned)s.ld0 + c) * 4u : OOB, 0, 0));
             if constexpr (TWO)
                 Xm[q] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs1, (c >= s.c0 && c < cin) ? (pix_ * (unsigned)s.ld1 + (c - s.c0)) * 4u : OOB, 0, 0));
+            if constexpr (TAIL) {
+                R0n[q] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rr0, c < cin ? (pix_ * (unsigned)a.ldr0 + c) * 4u : OOB, 0, 0));
+                R1n[q] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rr1, c < cin ? (pix_ * (unsigned)a.ldr1 + c) * 4u : OOB, 0, 0));
+            }
         }
     };
     if constexpr (SPLIT) {
@@ -276,6 +296,13 @@ __global__ __launch_bounds__(chain_threads(N1, SPLIT, K0), 1) void chain_kernel(
             for (int c = lane; c < K0; c += 64) myv[c] = c < cin ? s.vec[(size_t)b * cin + c] : 0.0f;
             b_cur = b;
         }
+        if (TAIL && b != b_cur) {                          // stash M | A | D of sample b for this wave (zeros in the padded channels: silu(0) = 0)
+            for (int c = lane; c < 3 * K0; c += 64) {
+                const int j = c / K0, cc = c - j * K0;
+                mym[c] = cc < cin ? a.mad[((size_t)b * 3 + j) * cin + cc] : 0.0f;
+            }
+            b_cur = b;
+        }
         // ---- this pixel's input row, channels 8q + 4*half .. +3 (two sources = virtual concat)
         f32x4 X[K0 / 8];
         if constexpr (SPLIT) {
@@ -283,6 +310,10 @@ __global__ __launch_bounds__(chain_threads(N1, SPLIT, K0), 1) void chain_kernel(
             for (int q = 0; q < K0 / 8; ++q) {
                 X[q] = Xn[q];
                 if constexpr (TWO) X[q] += Xm[q];
+                if constexpr (TAIL) {
+                    const float* m = mym + 8 * q + 4 * half;
+                    X[q] = nd_silu4((X[q] - nd_ld4(m)) * nd_ld4(m + K0) + nd_ld4(m + 2 * K0)) + R0n[q] + R1n[q];
+                }
             }
             prefetch_rows(t + 1 < t_end ? t + 1 : t);      // (behind the last tile: a harmless reload of it)
             if (s.vec) {
@@ -410,16 +441,17 @@ __global__ void pack_chain_split_kernel(const float* __restrict__ w, unsigned sh
     }
 }
 
-template <int K0, int N1, int N2, int N3, int MODE, bool SPLIT = false>
+template <int K0, int N1, int N2, int N3, int MODE, bool SPLIT = false, bool TAIL = false>
 int launch(const ChainArgs& a, hipStream_t st) {
     static nd_device_once configured;
     constexpr int THREADS = chain_threads(N1, SPLIT, K0), WAVES = THREADS / 64;
-    const size_t lds = (size_t)(chain_w_floats<SPLIT>(N1, K0) + chain_w_floats<SPLIT>(N2, N1) + chain_w_floats<SPLIT>(N3, N2) + N1 + N2 + N3 + 2 * K0 + WAVES * K0) * sizeof(float);
-    static_assert((size_t)(chain_w_floats<SPLIT>(N1, K0) + chain_w_floats<SPLIT>(N2, N1) + chain_w_floats<SPLIT>(N3, N2) + N1 + N2 + N3 + 2 * K0 + 16 * K0) * 4 <= 160 * 1024, "LDS");
-    if (int e = nd_reserve_lds(configured, reinterpret_cast<const void*>(chain_kernel<K0, N1, N2, N3, MODE, SPLIT>), lds, "nd_pointwise_chain")) return e;
+    constexpr int STASH = (TAIL ? 4 : 1) * K0;            // per wave: vec, and M | A | D with the tail prologue
+    const size_t lds = (size_t)(chain_w_floats<SPLIT>(N1, K0) + chain_w_floats<SPLIT>(N2, N1) + chain_w_floats<SPLIT>(N3, N2) + N1 + N2 + N3 + 2 * K0 + WAVES * STASH) * sizeof(float);
+    static_assert((size_t)(chain_w_floats<SPLIT>(N1, K0) + chain_w_floats<SPLIT>(N2, N1) + chain_w_floats<SPLIT>(N3, N2) + N1 + N2 + N3 + 2 * K0 + 16 * STASH) * 4 <= 160 * 1024, "LDS");
+    if (int e = nd_reserve_lds(configured, reinterpret_cast<const void*>(chain_kernel<K0, N1, N2, N3, MODE, SPLIT, TAIL>), lds, "nd_pointwise_chain")) return e;
     const int wgs = nd_cdiv(a.n_tiles, WAVES);
     const int grid = wgs < nd_device_cus() ? wgs : nd_device_cus();
-    hipLaunchKernelGGL((chain_kernel<K0, N1, N2, N3, MODE, SPLIT>), dim3(grid), dim3(THREADS), lds, st, a);
+    hipLaunchKernelGGL((chain_kernel<K0, N1, N2, N3, MODE, SPLIT, TAIL>), dim3(grid), dim3(THREADS), lds, st, a);
     return 0;
 }
 
@@ -499,7 +531,7 @@ static int chain_run(const nd_chain* d, void* stream, bool split) {
     ND_REQUIRE(nd_pointwise_chain_supported(cin, d->st[0].cout, d->st[1].cout, n3), ND_E_SHAPE,
                "nd_pointwise_chain: widths %d->%d->%d->%d are not instantiated (use nd_pointwise_gemm_nhwc_f32 per layer)", cin,
                d->st[0].cout, d->st[1].cout, n3);
-    ChainArgs a;
+    ChainArgs a{};
     a.d = *d;
     a.tiles_per_sample = d->HW / 32;
     const long tiles = (long)d->B * a.tiles_per_sample;
@@ -548,6 +580,50 @@ static int chain_run(const nd_chain* d, void* stream, bool split) {
 #undef ND_CHAIN_CASE
     if (rc) return rc;
     return nd_launch_status("nd_pointwise_chain_nhwc_f32");
+}
+
+// The SPLIT chain behind a ResnetBlock tail (the shot-noise branch's end: shot_mlp3(shot_time(s2) + r), Diffusion_arch.py:168-170,603-604): the tail pass
+// nd_affine_silu_add_f32 would write and the chain read back is the chain's prologue instead.  Two-stage chains of the widths nd_pointwise_chain_tail_takes names.
+extern "C" int nd_pointwise_chain_tail_takes(int cin, int n1, int n2, int n3) {
+    return n3 == 0 && (cin == 64 || cin == 48) && nd_round_up(n1, 32) == 64 && n1 > 0 && nd_round_up(n2, 32) == 32 && n2 > 0;
+}
+
+extern "C" int nd_pointwise_chain_tail_split_nhwc_f32(const nd_chain_tail* dt, void* stream) {
+    ND_REQUIRE(dt, ND_E_BADARG, "nd_pointwise_chain_tail: null descriptor");
+    const nd_chain* d = &dt->chain;
+    const nd_src& s = d->src;
+    ND_REQUIRE(d->n_stages == 2 && s.p0 && d->out && dt->mad && dt->r0, ND_E_BADARG, "nd_pointwise_chain_tail: two stages, t, mad, r0 and out");
+    ND_REQUIRE(d->B > 0 && d->HW > 0 && d->HW % 32 == 0, ND_E_SHAPE, "nd_pointwise_chain_tail: HW=%d must be a positive multiple of 32", d->HW);
+    ND_REQUIRE(s.c1 == 0 && !s.p1 && s.mode == ND_PRO_NONE && !s.vec && !s.upsample && !s.unshuffle && !s.rowstats, ND_E_BADARG,
+               "nd_pointwise_chain_tail: one plain source (the affine + SiLU is this entry point's own prologue)");
+    const int cin = s.c0;
+    ND_REQUIRE(nd_pointwise_chain_tail_takes(cin, d->st[0].cout, d->st[1].cout, 0), ND_E_SHAPE,
+               "nd_pointwise_chain_tail: widths %d->%d->%d are not instantiated (nd_affine_silu_add_f32, then the chain)", cin, d->st[0].cout, d->st[1].cout);
+    ND_REQUIRE(s.ld0 >= cin && s.ld0 % 4 == 0 && dt->ldr0 >= cin && dt->ldr0 % 4 == 0 && (!dt->r1 || (dt->ldr1 >= cin && dt->ldr1 % 4 == 0)), ND_E_ALIGN,
+               "nd_pointwise_chain_tail: pixel strides must be >= channels and multiples of 4");
+    int width = cin;
+    for (int i = 0; i < 2; ++i) {
+        const nd_chain_stage& g = d->st[i];
+        ND_REQUIRE(g.weight && g.cin == width && g.cout > 0 && g.res == ND_CHAIN_RES_NONE, ND_E_SHAPE, "nd_pointwise_chain_tail: stage %d is %d->%d, expected input width %d, no residual",
+                   i, g.cin, g.cout, width);
+        ND_REQUIRE(nd_aligned16(g.weight), ND_E_ALIGN, "nd_pointwise_chain_tail: weights must be 16-byte aligned");
+        width = g.cout;
+    }
+    ND_REQUIRE(width % 4 == 0 && d->ldo >= width && d->ldo % 4 == 0, ND_E_SHAPE, "nd_pointwise_chain_tail: output width %d, ldo %d", width, d->ldo);
+    ND_REQUIRE(nd_aligned16(s.p0) && nd_aligned16(d->out) && nd_aligned16(dt->mad) && nd_aligned16(dt->r0) && nd_aligned16(dt->r1), ND_E_ALIGN,
+               "nd_pointwise_chain_tail: tensors must be 16-byte aligned");
+    const long px = (long)d->B * d->HW, lim = (1L << 32) - 65536;
+    ND_REQUIRE(px * s.ld0 * 4 < lim && px * dt->ldr0 * 4 < lim && px * (dt->r1 ? dt->ldr1 : 0) * 4 < lim && px * d->ldo * 4 < lim, ND_E_SHAPE,
+               "nd_pointwise_chain_tail: a tensor of 4 GiB or more");
+    ChainArgs a{};
+    a.d = *d;
+    a.tiles_per_sample = d->HW / 32;
+    ND_REQUIRE(px / 32 < (1L << 31), ND_E_SHAPE, "nd_pointwise_chain_tail: too many pixels");
+    a.n_tiles = (int)(px / 32);
+    a.mad = dt->mad;  a.r0 = dt->r0;  a.r1 = dt->r1;  a.ldr0 = dt->ldr0;  a.ldr1 = dt->r1 ? dt->ldr1 : 0;
+    const int rc = cin == 64 ? launch<64, 64, 32, 0, ND_PRO_NONE, true, true>(a, (hipStream_t)stream) : launch<48, 64, 32, 0, ND_PRO_NONE, true, true>(a, (hipStream_t)stream);
+    if (rc) return rc;
+    return nd_launch_status("nd_pointwise_chain_tail_split_nhwc_f32");
 }
 
 #ifdef CHAIN_STAMP

@@ -66,6 +66,9 @@ _ALIGN = 64   # floats; keeps every arena slice 256-byte aligned
 _SPLIT = os.environ.get("ND_SPLIT_GEMM", "1")                 # "1" both kinds, "chain" / "pw" one of them, "0" neither (A/B, tools/ only)
 SPLIT_GEMM = _SPLIT != "0"
 SPLIT_CHAIN, SPLIT_PW = _SPLIT in ("1", "chain"), _SPLIT in ("1", "pw")
+# The step's two full-resolution block tails folded into their per-pixel consumers.  ND_FOLD_FINAL=0 / ND_SHOT_TAIL=0: A/B knobs (tools/ only).
+FOLD_FINAL = os.environ.get("ND_FOLD_FINAL", "1") != "0"     # final_res_block.res_conv + final_conv: one narrow streaming dot product over [xp; x0; silu(GN(c2))]
+SHOT_TAIL = os.environ.get("ND_SHOT_TAIL", "1") != "0"       # shot_time's tail as the prologue of the shot_mlp3 chain
 TIME_TABLE = True        # the time embedding's head looked up per timestep (r3; was ND_TIME_TABLE)
 PROJ_TABLE = True        # ... and the stacked ResnetBlock.mlp projection (r4e; was ND_PROJ_TABLE)
 TIME_TABLE_ROWS = 1000                                      # timesteps the table covers (the reference's --timesteps; larger t: computed)
@@ -219,6 +222,12 @@ class Engine:
         add("tproj.weight", j * 4 * self.dim, "derived", (j, 4 * self.dim))
         add("tproj.bias", j, "derived", (j,))
         add("time_freqs", self.dim // 2, "derived", (self.dim // 2,))
+        # final_conv . res_conv folded into one narrow weight over [xp; x0; silu(GN(c2))] (nd_pack_narrow_fold; a function of the widths alone)
+        wr, wf = self.slots.get("final_res_block.res_conv.weight"), self.slots.get("final_conv.weight")
+        if wr is not None and wf is not None and wf.shape[1] == wr.shape[0] and wr.shape[1] == 2 * wr.shape[0] and \
+                self.lib.nd_pointwise_narrow_fold_takes(wr.shape[0], wr.shape[0], wr.shape[0], wf.shape[0]):
+            add("final_fold.weight", self.lib.nd_pack_narrow_fold_floats(wr.shape[1] + wr.shape[0], wf.shape[0]), "derived", (wf.shape[0], wr.shape[1] + wr.shape[0]))
+            add("final_fold.bias", wf.shape[0], "derived", (wf.shape[0],))
         # time_mlp's result for every timestep 0 .. TIME_TABLE_ROWS - 1 (st = SiLU(time_mlp(emb(t))), Diffusion_arch.py:100-107,502-507,149): the
         # step kernel looks the head up instead of running two dependent small Linears at the start of every diffusion step
         # (only where the table's builder runs: its head batch of 16 timesteps needs 16 * dim * 36 bytes of LDS and 4 * dim <= 2048 -- dim <= 280;
@@ -294,6 +303,11 @@ class Engine:
                     L.call("nd_pack_conv7x7_weight", t.data_ptr(), dst, p.shape[0], st)
                     if p.name + ".split" in self.slots:
                         L.call("nd_pack_conv7x7_weight_split", t.data_ptr(), self.p(p.name + ".split"), p.shape[0], st)
+            if "final_fold.weight" in self.slots:      # W = [Wf Wr | Wf], bias = Wf br + bf: the 64-term sums in fp64 on the device, rounded once
+                raw = {p.name: t for p, t in zip([q for q in self.spec if q.name in self.slots], keep)}
+                wr, wf = raw["final_res_block.res_conv.weight"], raw["final_conv.weight"]
+                L.call("nd_pack_narrow_fold", wf.data_ptr(), raw["final_conv.bias"].data_ptr(), wr.data_ptr(), raw["final_res_block.res_conv.bias"].data_ptr(),
+                       self.p("final_fold.weight"), self.p("final_fold.bias"), wr.shape[1], wr.shape[0], wf.shape[0], st)
             L.call("nd_stream_sync", st)
             tw = torch.cat([self.view(r + ".mlp.1.weight") for r in self.resnet_names])
             tb = torch.cat([self.view(r + ".mlp.1.bias") for r in self.resnet_names])
@@ -709,8 +723,9 @@ class Plan:
 
     # ------------------------------------------------------------------ composite layers
     def resnet(self, name: str, x: torch.Tensor, skip: Optional[torch.Tensor], cout: int, H: int, W: int, groups: int,
-               posmap: Optional[torch.Tensor] = None, extra_res: Optional[torch.Tensor] = None) -> torch.Tensor:
-        """ResnetBlock / ResnetBlock2 (Diffusion_arch.py:146-196) as 2 convs + 2 tiny finalizes + 1 tail."""
+               posmap: Optional[torch.Tensor] = None, extra_res: Optional[torch.Tensor] = None, tail: bool = True):
+        """ResnetBlock / ResnetBlock2 (Diffusion_arch.py:146-196) as 2 convs + 2 tiny finalizes + 1 tail.  ``tail=False``: no tail launch; returns
+        (c2, mad2) -- the block's output is silu((c2 - M) A + D) + its shortcut, formed by the caller's fused consumer."""
         cin = x.shape[-1] + (skip.shape[-1] if skip is not None else 0)
         HW = H * W
         c1, st1, sc1, n1 = self.conv3(name + ".block1.proj", self._src(x, skip), cin, cout, H, W, stats=True)
@@ -736,6 +751,9 @@ class Plan:
         if a1 is not None:
             self._release(a1)
         mad2 = self.gn_finalize(st2, sc2, n2, name + ".block2.norm", cout, groups, None)
+        if not tail:          # the block's last pass runs inside its consumer: (c2, mad2) are that consumer's activated source
+            self._release(c1, st1, sc1, mad1, st2, sc2)
+            return c2, mad2
         if cin != cout:       # h + res_conv(x): the 1x1 GEMM adds silu(GN(c2)) in its epilogue   :170
             assert extra_res is None
             out = self.pw(name + ".res_conv", self._src(x, skip), cin, cout, HW, W, gn_t=c2, gn_mad=mad2)
@@ -749,18 +767,21 @@ class Plan:
         self._release(c1, st1, sc1, mad1, c2, st2, sc2, mad2)
         return out.view(self.B, H, W, cout)
 
-    def chain(self, name: str, src: L.Src, stages, HW: int) -> torch.Tensor:
-        """Fused per-pixel Linear chain; stages = [(layer, cin, cout, act, res)]."""
+    def chain(self, name: str, src: L.Src, stages, HW: int, tail=None) -> torch.Tensor:
+        """Fused per-pixel Linear chain; stages = [(layer, cin, cout, act, res)].  ``tail`` = (mad, r0, r1 or None): the chain's input row is
+        silu((src - M) A + D) + r0 (+ r1), a ResnetBlock tail as the split chain's prologue (nd_pointwise_chain_tail_split_nhwc_f32)."""
         e = self.e
         out = self._alloc(self.B, HW, stages[-1][2])
         # the split-product form (a function of the widths alone); two sources only where the first stage is one K step (pwchain.hip)
         split = all((layer + ".weight.chain_s") in e.slots for layer, *_ in stages) and (src.c1 == 0 or stages[0][1] <= 16)
         ldo = stages[-1][2]
+        if tail is not None and not split:
+            raise L.HipError(f"{name}: the tail prologue is a form of the split chain only")
         # the split kernel addresses its tensors through 32-bit buffer offsets (below 4 GiB): a larger batch runs as equal pieces of whole samples -- same kernel,
         # same arithmetic per pixel, so a sample's bits do not depend on the batch (as Plan._conv_rows does for the convolutions)
         rows = self.B
         if split:
-            per = 4 * HW * max(src.ld0, src.ld1, ldo)
+            per = 4 * HW * max(src.ld0, src.ld1, ldo, *([t.shape[-1] for t in tail[1:] if t is not None] if tail else []))
             rows = max(1, min(self.B, _CHAIN_SPLIT_LIMIT // per))
             rows = -(-self.B // -(-self.B // rows))
         for b0 in range(0, self.B, rows):
@@ -777,9 +798,19 @@ class Plan:
             for i, (layer, cin, cout, act, res) in enumerate(stages):
                 d.st[i].weight, d.st[i].bias = e.p(layer + (".weight.chain_s" if split else ".weight.chain")), e.p(layer + ".bias")
                 d.st[i].cin, d.st[i].cout, d.st[i].act, d.st[i].res = cin, cout, act, res
-            self._add("nd_pointwise_chain_split_nhwc_f32" if split else "nd_pointwise_chain_nhwc_f32", C.byref(d), e.stream,
-                      meta={"layer": name, "B": nb, "HW": HW, "cin": stages[0][1], "cout": stages[-1][2], "split": int(split),
-                            "flop_per_px": 2.0 * sum(c_in * c_out for _, c_in, c_out, _, _ in stages)})
+            meta = {"layer": name, "B": nb, "HW": HW, "cin": stages[0][1], "cout": stages[-1][2], "split": int(split),
+                    "flop_per_px": 2.0 * sum(c_in * c_out for _, c_in, c_out, _, _ in stages)}
+            if tail is not None:
+                mad, r0, r1 = tail
+                dt = L.ChainTail()
+                dt.chain, dt.mad = d, mad.data_ptr() + 4 * b0 * 3 * src.c0
+                dt.r0, dt.ldr0 = r0.data_ptr() + 4 * b0 * HW * r0.shape[-1], r0.shape[-1]
+                if r1 is not None:
+                    dt.r1, dt.ldr1 = r1.data_ptr() + 4 * b0 * HW * r1.shape[-1], r1.shape[-1]
+                self._add("nd_pointwise_chain_tail_split_nhwc_f32", C.byref(dt), e.stream, meta=meta)
+                self._keep.append(dt)
+                continue
+            self._add("nd_pointwise_chain_split_nhwc_f32" if split else "nd_pointwise_chain_nhwc_f32", C.byref(d), e.stream, meta=meta)
             self._keep.append(d)
         return out
 
@@ -888,11 +919,22 @@ class Plan:
             r_shot = self.mlp("shot_mlp1", self._src(self.clean, self.x), 2 * e.inp_dim, d, d, H, W)
             s = self.attn_block("shot_attn", r_shot, H, W)
             s2 = self.mlp("shot_mlp2", self._src(s), d, d, d, H, W)
-            s3 = self.resnet("shot_time", s2, None, d, H, W, SHOT_GROUPS, extra_res=r_shot)   # shot_time(...) + r
-            shot_noise = self._tap("shot_noise", self.mlp("shot_mlp3", self._src(s3), d, d, e.inp_dim, H, W))
-            for nm, tt in (("shot_mlp1", r_shot), ("shot_attn", s), ("shot_mlp2", s2), ("shot_time", s3)):
-                self._tap(nm, tt)
-            self._release(r_shot, s, s2, s3)
+            if (SHOT_TAIL and not self.debug and SPLIT_CHAIN and self._chain_ok(H * W, (d, d, e.inp_dim)) and e.lib.nd_pointwise_chain_tail_takes(d, d, e.inp_dim, 0)
+                    and all(n + ".weight.chain_s" in e.slots for n in ("shot_mlp3.fc1", "shot_mlp3.fc2"))):
+                # shot_mlp3(shot_time(s2) + r): the block's tail is the chain's prologue -- no s3
+                c2, mad2 = self.resnet("shot_time", s2, None, d, H, W, SHOT_GROUPS, tail=False)
+                shot_noise = self.chain("shot_time.tail+shot_mlp3", self._src(c2), [("shot_mlp3.fc1", d, d, L.ACT_GELU, L.CHAIN_RES_NONE),
+                                                                                   ("shot_mlp3.fc2", d, e.inp_dim, L.ACT_NONE, L.CHAIN_RES_NONE)], H * W,
+                                        tail=(mad2, s2, r_shot)).view(B, H, W, e.inp_dim)
+                self._release(r_shot, s, s2, c2, mad2)
+                s3 = None
+            else:
+                s3 = self.resnet("shot_time", s2, None, d, H, W, SHOT_GROUPS, extra_res=r_shot)   # shot_time(...) + r
+                shot_noise = self._tap("shot_noise", self.mlp("shot_mlp3", self._src(s3), d, d, e.inp_dim, H, W))
+            if s3 is not None:
+                for nm, tt in (("shot_mlp1", r_shot), ("shot_attn", s), ("shot_mlp2", s2), ("shot_time", s3)):
+                    self._tap(nm, tt)
+                self._release(r_shot, s, s2, s3)
         # ---- trunk
         x0 = self._alloc(B, H, W, d)
         stem_split = "init_conv.weight.split" in e.slots
@@ -958,6 +1000,22 @@ class Plan:
             self._tap(p + ".0", x1); self._tap(p + ".1", x2); self._tap(p + ".2", xa); self._tap(f"up{i}", x)
         xp = self._tap("pos_block2", self.resnet("pos_block2", x, None, d, H, W, POS_GROUPS, posmap=pm2))
         self._release(x)
+        if FOLD_FINAL and not self.debug and "final_fold.weight" in e.slots:
+            # final_conv(res_conv(cat(xp, x0)) + silu(GN(c2))) + shot is linear in its three sources: one narrow dot product with the folded weight, no xf
+            c2, mad2 = self.resnet("final_res_block", xp, x0, d, H, W, G, tail=False)
+            nf = L.NarrowFold()
+            nf.p0, nf.p1, nf.t, nf.mad = xp.data_ptr(), x0.data_ptr(), c2.data_ptr(), mad2.data_ptr()
+            nf.weight, nf.bias, nf.out = e.p("final_fold.weight"), e.p("final_fold.bias"), self.model_out.data_ptr()
+            nf.B, nf.HW, nf.c0, nf.c1, nf.c2, nf.ld0, nf.ld1, nf.ldt, nf.cout, nf.ldo = B, H * W, d, d, d, d, d, d, e.inp_dim, e.inp_dim
+            if shot_noise is not None:
+                nf.res0, nf.ldr0 = shot_noise.data_ptr(), e.inp_dim
+            self._add("nd_pointwise_narrow_fold_nhwc_f32", C.byref(nf), e.stream,
+                      meta={"layer": "final_res_block.res_conv+final_conv", "B": B, "HW": H * W, "cin": 3 * d, "cout": e.inp_dim})
+            self._keep.append(nf)
+            self._release(xp, x0, c2, mad2)
+            if shot_noise is not None:
+                self._release(shot_noise)
+            return
         xf = self._tap("final_res_block", self.resnet("final_res_block", xp, x0, d, H, W, G))
         self._release(xp, x0)
         # NoiseDiffNet: shot + read (:644); the ablation nets return final_conv(x) alone

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Idle time between the kernels of a replayed diffusion step: python tools/step_gaps.py <..._kernel_trace.csv>
 (from `rocprofv3 --kernel-trace --output-format csv -- python3 bench.py --steps 5 --warmup 1 --soak-s 0 --no-cpu --no-roofline`).
-Takes the last 3 x 159-launch windows that start with cond_step_kernel; prints span, busy time, the gap histogram and the largest gaps."""
+Takes the last three step windows (each starts with cond_step_kernel); prints span, busy time, the gap histogram and the largest gaps."""
 import csv, sys
 ev = sorted(((int(r["Start_Timestamp"]), int(r["End_Timestamp"]), r["Kernel_Name"]) for r in csv.DictReader(open(sys.argv[1]))), key=lambda e: e[0])
 starts = [i for i, e in enumerate(ev) if "cond_step_kernel" in e[2]]
