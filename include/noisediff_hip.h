@@ -93,7 +93,10 @@ enum nd_act { ND_ACT_NONE = 0, ND_ACT_GELU = 1, ND_ACT_SILU = 2 };
  * Weights are pre-packed by nd_pack_conv3x3_weight.  When `stats` != NULL the epilogue
  * also emits per-(sample, slot, channel) partial sums {sum, M2} of the output for the
  * following GroupNorm (Block.norm :132); `slot_count[slot]` receives the number of pixels
- * behind each slot.  Query the slot count with nd_conv3x3_stat_slots. */
+ * behind each slot.  Query the slot count with nd_conv3x3_stat_slots.
+ * Five kernels compute this operator from the same descriptor (below), each within limits of its own: channel multiples, chunk boundaries of a concat, pixel and
+ * byte counts, the prologues it reads.  nd_conv3x3_takes answers whether a kernel takes a descriptor and is the ONLY statement of those limits (csrc/conv3x3_desc.h,
+ * run by the entry points themselves): callers ask it and keep policy only -- which kernel they prefer where several take the layer. */
 typedef struct nd_conv3x3 {
     nd_src   src;
     const float* weight;   /* packed, see nd_pack_conv3x3_weight                         */
@@ -106,6 +109,10 @@ typedef struct nd_conv3x3 {
 } nd_conv3x3;
 
 int nd_conv3x3_nhwc_f32(const nd_conv3x3* d, void* stream);
+/* 1 where `kernel`'s entry takes the sizes, strides, prologue and addressing of `d`, else 0.  Host code: no GPU, no HIP call, nd_last_error untouched (a question
+ * is not a failure).  Reads no pointer of `d`: a descriptor with the integers alone will do.  `splits` > 1: the split-K entry of an F(4x4) kernel with that many ranges. */
+enum nd_conv3x3_kernel { ND_CONV3X3_DIRECT = 0, ND_CONV3X3_WINO = 1, ND_CONV3X3_WINO2 = 2, ND_CONV3X3_WINO4 = 3, ND_CONV3X3_WINO4_16 = 4 };
+int nd_conv3x3_takes(int kernel, const nd_conv3x3* d, int splits);   /* 1 / 0; splits <= 1: the plain form */
 int nd_conv3x3_stat_slots(int H, int W, int cout, int B);
 /* which conv3x3_kernel<TW, MB, NB> instance a shape runs on: TW*100 + MB*10 + NB (for profiling reports) */
 int nd_conv3x3_tiling_id(int B, int H, int W, int cout);

@@ -5,6 +5,7 @@ of a 3x3 convolution outside the sampling engine.  Imports only ``torch`` and ``
 from __future__ import annotations
 
 import ctypes as C
+import functools
 from typing import Optional
 
 import torch
@@ -52,15 +53,26 @@ def _workspace(entry: str, device: torch.device, *dims) -> torch.Tensor:
     return torch.empty(int(getattr(L.load(), entry)(*dims)), dtype=torch.float32, device=device)
 
 
+def conv3x3_takes(kernel: int, B: int, H: int, W: int, cin: int, cout: int, c0: int, c1: int, ld0: int, ld1: int, mode: int = L.PRO_NONE, upsample: bool = False,
+                  map_blocked: bool = False, ldo: Optional[int] = None, splits: int = 1) -> bool:
+    """Does the conv3x3 kernel ``kernel`` (L.CONV3X3_*) take a layer of these sizes?  The library's answer (nd_conv3x3_takes: the kernel's own shape checks, the
+    only place its limits are written); ``splits`` > 1: its split-K entry.  Host code: needs the built library and no GPU."""
+    d = L.Conv3x3(B=B, H=H, W=W, cin=cin, cout=cout, ldo=cout if ldo is None else ldo)
+    d.src.c0, d.src.c1, d.src.ld0, d.src.ld1, d.src.mode, d.src.upsample, d.src.map_blocked = c0, c1, ld0, ld1, mode, int(upsample), int(map_blocked)
+    return bool(L.load().nd_conv3x3_takes(kernel, C.byref(d), splits))
+
+
+@functools.lru_cache(maxsize=None)
 def conv3x3_kind(B: int, H: int, W: int, cin: int, cout: int, c0: int, c1: int, ld: int, wino4: bool = True) -> str:
     """The kernel of a 3x3 convolution outside the sampling engine: 'wino4', 'wino2', 'wino' (F(2x2,3x3) past wino2's limits) or 'direct'.
     ``c0`` / ``c1``: the channels of the two sources (c1 = 0: one source); ``ld``: the pixel stride the source-size limits are computed with;
-    ``wino4`` False: never the F(4x4,3x3) kernel.  Host-only: needs no library."""
-    wino = H >= 16 and W >= 16 and cin % 8 == 0
-    if (wino4 and wino and cin > 16 and cin % 4 == 0 and cout % 4 == 0 and cout <= 2048 and W >= 32 and (W % 32 == 0 or W >= 96) and W <= 2048
-            and (c1 == 0 or c0 % 16 == 0) and B * H * W + W + 2 < (1 << 24) and (B * H * W + W + 2) * 4 * ld < (1 << 30) - (1 << 16)):
+    ``wino4`` False: never the F(4x4,3x3) kernel.  Policy only -- the order of preference, images of at least one 16 x 16 tile, F(4x4) where the image fills its
+    16 x 32-pixel regions; what a kernel can take is the library's answer.  Needs the built library and no GPU; cached (a training step asks several hundred times)."""
+    takes = lambda kernel: conv3x3_takes(kernel, B, H, W, cin, cout, c0, c1, ld, ld if c1 else 0)
+    wino = H >= 16 and W >= 16 and takes(L.CONV3X3_WINO)
+    if wino4 and wino and W >= 32 and (W % 32 == 0 or W >= 96) and takes(L.CONV3X3_WINO4):
         return "wino4"
-    if wino and (c1 == 0 or c0 % 32 == 0) and B * H * W < (1 << 24) and B * H * W * 4 * ld < (1 << 31):
+    if wino and takes(L.CONV3X3_WINO2):
         return "wino2"
     return "wino" if wino else "direct"
 

@@ -18,6 +18,7 @@ PRO_NONE, PRO_AFFINE_SILU, PRO_AFFINE_MAP_SILU, PRO_LAYERNORM, PRO_SILU, PRO_LEA
 ACT_NONE, ACT_GELU, ACT_SILU = 0, 1, 2
 OBJECTIVES = {"pred_noise": 0, "pred_x0": 1, "pred_v": 2}
 LAYOUT_NCHW, LAYOUT_NHWC = 0, 1                           # enum nd_layout
+CONV3X3_DIRECT, CONV3X3_WINO, CONV3X3_WINO2, CONV3X3_WINO4, CONV3X3_WINO4_16 = 0, 1, 2, 3, 4      # enum nd_conv3x3_kernel
 
 fptr = C.c_void_p   # device pointers travel as integers
 
@@ -108,6 +109,7 @@ SIGNATURES = {
     "nd_last_error": (C.c_char_p, []),
     "nd_device_arch": (i32, [C.c_char_p, i32]),
     "nd_conv3x3_nhwc_f32": (i32, [C.POINTER(Conv3x3), vp]),
+    "nd_conv3x3_takes": (i32, [i32, C.POINTER(Conv3x3), i32]),
     "nd_conv3x3_stat_slots": (i32, [i32, i32, i32, i32]),
     "nd_conv3x3_tiling_id": (i32, [i32, i32, i32, i32]),
     "nd_pack_conv3x3_weight_floats": (i64, [i32, i32]),
@@ -279,7 +281,7 @@ SIGNATURES = {
     "nd_raw_diffusion_batch_f32": (i32, [vp, i32, i32, i32, vp, f32, f32, vp, vp, vp, vp, i32, i32, i32, vp]),
 }
 
-_UNCHECKED = {"nd_pointwise_chain_tail_takes", "nd_pointwise_narrow_fold_takes", "nd_pack_narrow_fold_floats", "nd_version", "nd_last_error", "nd_stream_device", "nd_conv3x3_wgrad_form", "nd_adam_chunk_elements", "nd_ema_chunk_elements", "nd_conv7x7_c4_wgrad_workspace_floats", "nd_conv3x3_stat_slots", "nd_conv3x3_tiling_id", "nd_pack_conv3x3_weight_floats",
+_UNCHECKED = {"nd_conv3x3_takes", "nd_pointwise_chain_tail_takes", "nd_pointwise_narrow_fold_takes", "nd_pack_narrow_fold_floats", "nd_version", "nd_last_error", "nd_stream_device", "nd_conv3x3_wgrad_form", "nd_adam_chunk_elements", "nd_ema_chunk_elements", "nd_conv7x7_c4_wgrad_workspace_floats", "nd_conv3x3_stat_slots", "nd_conv3x3_tiling_id", "nd_pack_conv3x3_weight_floats",
               "nd_pack_pointwise_weight_floats", "nd_linear_attention_workspace_floats", "nd_conv3x3_wino_stat_slots", "nd_conv3x3_wino4_stat_slots",
               "nd_pack_conv3x3_wino_weight_floats", "nd_pack_conv3x3_wino4_weight_floats", "nd_conv3x3_wino4_splitk_plan", "nd_conv3x3_wino4_16_splitk_plan", "nd_conv3x3_wino4_splitk_workspace_floats", "nd_token_sum_workspace_floats", "nd_cond_step_lds_bytes", "nd_conv3x3_wgrad_workspace_floats",
               "nd_groupnorm_train_workspace_floats", "nd_linear_wgrad_workspace_floats",

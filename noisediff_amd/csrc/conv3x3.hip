@@ -20,6 +20,7 @@
 // K order inside a group of 8 channels: lane half h supplies channel 4h+s at k-step s.
 #include <stdlib.h>
 #include "nd_common.h"
+#include "conv3x3_desc.h"
 
 namespace {
 
@@ -393,27 +394,8 @@ extern "C" int nd_pack_conv3x3_weight_dgrad(const float* oihw_fwd, float* packed
 
 extern "C" int nd_conv3x3_nhwc_f32(const nd_conv3x3* d, void* stream) {
     ND_REQUIRE(d, ND_E_BADARG, "nd_conv3x3: null descriptor");
-    const nd_src& s = d->src;
-    ND_REQUIRE(s.p0 && d->weight && d->out, ND_E_BADARG, "nd_conv3x3: null tensor pointer");
-    ND_REQUIRE(d->B > 0 && d->H > 0 && d->W > 0 && d->cin > 0 && d->cout > 0, ND_E_BADARG, "nd_conv3x3: non-positive size");
-    ND_REQUIRE(d->cin % 8 == 0, ND_E_SHAPE, "nd_conv3x3: cin=%d must be a multiple of 8", d->cin);
-    ND_REQUIRE(s.c0 + s.c1 == d->cin && s.c0 % 4 == 0 && s.c1 % 4 == 0 && s.c0 > 0, ND_E_SHAPE,
-               "nd_conv3x3: source channels %d+%d do not match cin=%d (multiples of 4)", s.c0, s.c1, d->cin);
-    ND_REQUIRE((s.c1 == 0) == (s.p1 == nullptr), ND_E_BADARG, "nd_conv3x3: p1/c1 mismatch");
-    ND_REQUIRE(s.ld0 >= s.c0 && s.ld0 % 4 == 0 && (s.c1 == 0 || (s.ld1 >= s.c1 && s.ld1 % 4 == 0)), ND_E_ALIGN,
-               "nd_conv3x3: pixel strides must be >= channels and multiples of 4");
-    ND_REQUIRE(nd_aligned16(s.p0) && nd_aligned16(s.p1) && nd_aligned16(d->weight) && nd_aligned16(s.mad) && nd_aligned16(s.map),
-               ND_E_ALIGN, "nd_conv3x3: pointers must be 16-byte aligned");
-    ND_REQUIRE(d->ldo >= d->cout, ND_E_SHAPE, "nd_conv3x3: ldo < cout");
-    const bool affine = s.mode == ND_PRO_AFFINE_SILU || s.mode == ND_PRO_AFFINE_MAP_SILU;
-    ND_REQUIRE(s.mode == ND_PRO_NONE || affine || s.mode == ND_PRO_LEAKY || s.mode == ND_PRO_LEAKY_SECOND, ND_E_BADARG,
-               "nd_conv3x3: unsupported prologue %d", s.mode);
-    ND_REQUIRE(!affine || s.mad, ND_E_BADARG, "nd_conv3x3: affine prologue needs mad");
-    ND_REQUIRE(s.mode != ND_PRO_AFFINE_MAP_SILU || s.map, ND_E_BADARG, "nd_conv3x3: map prologue needs map");
-    ND_REQUIRE(!s.map_blocked, ND_E_BADARG, "nd_conv3x3: the blocked map layout is read by nd_conv3x3_wino4_nhwc_f32 only");
-    ND_REQUIRE(!s.upsample || (d->H % 2 == 0 && d->W % 2 == 0 && s.c1 == 0), ND_E_SHAPE, "nd_conv3x3: upsample needs even H, W and one source");
-    ND_REQUIRE(!s.unshuffle, ND_E_BADARG, "nd_conv3x3: unshuffle is a pointwise-only addressing mode");
-    ND_REQUIRE((d->stats == nullptr) == (d->slot_count == nullptr), ND_E_BADARG, "nd_conv3x3: stats and slot_count go together");
+    if (int e = nd_conv3x3_f2_ptrs(d, "nd_conv3x3")) return e;
+    if (int e = nd_conv3x3_f2_shape(d, "nd_conv3x3")) return e;
 
     const Tiling t = choose_tiling(d->B, d->H, d->W, d->cout);
     ConvArgs a;

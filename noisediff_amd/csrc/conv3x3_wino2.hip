@@ -16,6 +16,7 @@
 #include <stdlib.h>
 #include <type_traits>
 #include "nd_common.h"
+#include "conv3x3_desc.h"
 #include "wino2x2.h"
 
 namespace {
@@ -568,42 +569,13 @@ int launch_mode(const Wino2Args& a, hipStream_t st) {
 extern "C" int W2_ENTRY(const nd_conv3x3* d, void* stream) {
     ND_REQUIRE(d, ND_E_BADARG, "nd_conv3x3_wino2: null descriptor");
     const nd_src& s = d->src;
-    ND_REQUIRE(s.p0 && d->weight && d->out, ND_E_BADARG, "nd_conv3x3_wino2: null tensor pointer");
-    ND_REQUIRE(d->B > 0 && d->H > 0 && d->W > 0 && d->cin > 0 && d->cout > 0, ND_E_BADARG, "nd_conv3x3_wino2: non-positive size");
-    ND_REQUIRE(d->cin % 8 == 0, ND_E_SHAPE, "nd_conv3x3_wino2: cin=%d must be a multiple of 8", d->cin);
-    ND_REQUIRE(s.c0 + s.c1 == d->cin && s.c0 % 4 == 0 && s.c1 % 4 == 0 && s.c0 > 0, ND_E_SHAPE,
-               "nd_conv3x3_wino2: source channels %d+%d do not match cin=%d (multiples of 4)", s.c0, s.c1, d->cin);
-    ND_REQUIRE((s.c1 == 0) == (s.p1 == nullptr), ND_E_BADARG, "nd_conv3x3_wino2: p1/c1 mismatch");
-    ND_REQUIRE(s.ld0 >= s.c0 && s.ld0 % 4 == 0 && (s.c1 == 0 || (s.ld1 >= s.c1 && s.ld1 % 4 == 0)), ND_E_ALIGN,
-               "nd_conv3x3_wino2: pixel strides must be >= channels and multiples of 4");
-    ND_REQUIRE(nd_aligned16(s.p0) && nd_aligned16(s.p1) && nd_aligned16(d->weight) && nd_aligned16(s.mad) && nd_aligned16(s.map),
-               ND_E_ALIGN, "nd_conv3x3_wino2: pointers must be 16-byte aligned");
-    ND_REQUIRE(d->ldo >= d->cout, ND_E_SHAPE, "nd_conv3x3_wino2: ldo < cout");
-    const bool affine = s.mode == ND_PRO_AFFINE_SILU || s.mode == ND_PRO_AFFINE_MAP_SILU;
-    ND_REQUIRE(s.mode == ND_PRO_NONE || affine || s.mode == ND_PRO_LEAKY || s.mode == ND_PRO_LEAKY_SECOND, ND_E_BADARG,
-               "nd_conv3x3_wino2: unsupported prologue %d", s.mode);
-    ND_REQUIRE(!affine || s.mad, ND_E_BADARG, "nd_conv3x3_wino2: affine prologue needs mad");
-    ND_REQUIRE(s.mode != ND_PRO_AFFINE_MAP_SILU || s.map, ND_E_BADARG, "nd_conv3x3_wino2: map prologue needs map");
-    ND_REQUIRE(!s.map_blocked, ND_E_BADARG, "nd_conv3x3_wino2: the blocked map layout is read by nd_conv3x3_wino4_nhwc_f32 only");
-    ND_REQUIRE(!s.upsample || (d->H % 2 == 0 && d->W % 2 == 0 && s.c1 == 0), ND_E_SHAPE, "nd_conv3x3_wino2: upsample needs even H, W and one source");
-    ND_REQUIRE(!s.unshuffle, ND_E_BADARG, "nd_conv3x3_wino2: unshuffle is a pointwise-only addressing mode");
-    ND_REQUIRE(!(s.mode == ND_PRO_AFFINE_MAP_SILU && s.upsample), ND_E_BADARG,
-               "nd_conv3x3_wino2: map prologue with upsample is not supported here (use nd_conv3x3_wino_nhwc_f32)");
-    ND_REQUIRE((long)d->B * d->H * d->W < (1L << 24) && (long)(7 * d->W + 7) * d->ldo < (1L << 31), ND_E_SHAPE,
-               "nd_conv3x3_wino2: more than 2^24 pixels (use nd_conv3x3_wino_nhwc_f32)");
-    {
-        const long px = (long)d->B * (d->H >> (s.upsample ? 1 : 0)) * (d->W >> (s.upsample ? 1 : 0));
-        const long widest = s.mode == ND_PRO_AFFINE_MAP_SILU ? 2L * (s.c0 + s.c1) : 0;
-        // (sources 64 KB below 2 GiB: pixel offset + channel offset + the 2^31 of an invalid channel quad stay below 2^32)
-        ND_REQUIRE(px * s.ld0 * 4 < (1L << 31) - 65536 && px * s.ld1 * 4 < (1L << 31) - 65536 && px * widest * 4 < (1L << 31), ND_E_SHAPE,
-                   "nd_conv3x3_wino2: a source tensor of 2 GiB or more (use nd_conv3x3_wino_nhwc_f32)");
-    }
-    ND_REQUIRE(s.c1 == 0 || s.c0 % 32 == 0, ND_E_SHAPE,
-               "nd_conv3x3_wino2: first concat source has %d channels; a 32-channel K chunk must not straddle the sources "
-               "(use nd_conv3x3_wino_nhwc_f32)", s.c0);
 #ifndef W2_STAMP
-    ND_REQUIRE((d->stats == nullptr) == (d->slot_count == nullptr), ND_E_BADARG, "nd_conv3x3_wino2: stats and slot_count go together");
+    const bool stats_pair = true;
+#else
+    const bool stats_pair = false;                         // slot_count alone carries the stamps
 #endif
+    if (int e = nd_conv3x3_f2_ptrs(d, "nd_conv3x3_wino2", stats_pair)) return e;
+    if (int e = nd_conv3x3_wino2_shape(d, "nd_conv3x3_wino2")) return e;
 
     Wino2Args a;
     a.d = *d;

@@ -38,6 +38,7 @@
 #include <stdlib.h>
 #include <type_traits>
 #include "nd_common.h"
+#include "conv3x3_desc.h"
 
 namespace {
 
@@ -48,7 +49,7 @@ typedef __attribute__((address_space(3))) unsigned* lds_u32_ptr;
 typedef __attribute__((address_space(3))) unsigned short* lds_u16_ptr;
 typedef __attribute__((address_space(3))) f32x4* lds_f32x4_ptr;
 
-constexpr int KC4 = 16;                              // channels per K chunk
+constexpr int KC4 = ND_W4_CHUNK;                          // channels per K chunk
 constexpr int NPOS = 36;                             // positions (xi, nu) == patch entries (a, b)
 constexpr int VD_FLOATS = NPOS * 256;                // one tile group's chunk image: 36 entries x 1 KB = 36 KB
 
@@ -63,7 +64,7 @@ constexpr int VD_FLOATS = NPOS * 256;                // one tile group's chunk i
 //                     OTHER workgroup's MFMAs do (the fp32 MFMA shares the VALU lanes, so only waits can be hidden, never VALU work); the price is that
 //                     a weight fragment serves one MFMA quad instead of two (32 B/clk per CU from the L2 instead of 16).  It is also the F(4x4) path of
 //                     images narrower than 32 pixels.  Same arithmetic in the same order: the two forms agree bit for bit.
-constexpr int MAX_COUT = 2048;                                           // NTG == 2: the whole bias vector (padded to cout tiles) lives in LDS
+constexpr int MAX_COUT = ND_W4_MAX_COUT;                                         // NTG == 2: the whole bias vector (padded to cout tiles) lives in LDS
 template <int NTG, int NW = 4>
 struct W4Geo {
     static constexpr int NT = 64 * NW;                                    // threads: NW waves (4: one per SIMD and workgroup; 8: two per SIMD in ONE workgroup)
@@ -1170,53 +1171,22 @@ extern "C" int nd_pack_conv3x3_wino4_weights_batch(const nd_pack_item* items_dev
 
 extern "C" int nd_conv3x3_wino4_stat_slots(int H, int W) { return nd_cdiv(W, 16) * nd_cdiv(H, 16); }
 
-// descriptor checks shared by the entry points; fills the launch arguments
-static int w4_prepare(const nd_conv3x3* d, Wino4Args& a, int ntg = 2) {
+// descriptor checks shared by the entry points -- the pointer part here, the shape part in conv3x3_desc.h (`split`: the split-K form with `splits` K ranges;
+// `who`: the entry that speaks in the refusals of the 16 x 16-region and split-K forms' own conditions); fills the launch arguments
+static int w4_prepare(const nd_conv3x3* d, Wino4Args& a, int ntg = 2, bool split = false, int splits = 1, const char* who = "nd_conv3x3_wino4_16") {
     ND_REQUIRE(d, ND_E_BADARG, "nd_conv3x3_wino4: null descriptor");
     const nd_src& s = d->src;
-    ND_REQUIRE(s.p0 && d->weight && d->out, ND_E_BADARG, "nd_conv3x3_wino4: null tensor pointer");
-    ND_REQUIRE(d->B > 0 && d->H > 0 && d->W > 0 && d->cin > 0 && d->cout > 0, ND_E_BADARG, "nd_conv3x3_wino4: non-positive size");
-    ND_REQUIRE(d->cin % 4 == 0 && d->cout % 4 == 0 && d->cin > KC4 && d->cout <= MAX_COUT, ND_E_SHAPE,
-               "nd_conv3x3_wino4: cin=%d and cout=%d must be multiples of 4, cin > 16 (at least two K chunks), cout <= %d", d->cin, d->cout, MAX_COUT);
-    ND_REQUIRE(s.c0 + s.c1 == d->cin && s.c0 % 4 == 0 && s.c1 % 4 == 0 && s.c0 > 0, ND_E_SHAPE,
-               "nd_conv3x3_wino4: source channels %d+%d do not match cin=%d (multiples of 4)", s.c0, s.c1, d->cin);
-    ND_REQUIRE((s.c1 == 0) == (s.p1 == nullptr), ND_E_BADARG, "nd_conv3x3_wino4: p1/c1 mismatch");
-    ND_REQUIRE(s.ld0 >= s.c0 && s.ld0 % 4 == 0 && (s.c1 == 0 || (s.ld1 >= s.c1 && s.ld1 % 4 == 0)), ND_E_ALIGN,
-               "nd_conv3x3_wino4: pixel strides must be >= channels and multiples of 4");
+    if (int e = nd_conv3x3_common_ptrs(d, "nd_conv3x3_wino4")) return e;
     ND_REQUIRE(nd_aligned16(s.p0) && nd_aligned16(s.p1) && nd_aligned16(d->weight) && nd_aligned16(s.mad) && nd_aligned16(d->out) &&
                nd_aligned16(d->bias), ND_E_ALIGN, "nd_conv3x3_wino4: pointers must be 16-byte aligned");
-    ND_REQUIRE(d->ldo >= d->cout && d->ldo % 4 == 0, ND_E_SHAPE, "nd_conv3x3_wino4: ldo must be >= cout and a multiple of 4");
-    const bool aff = s.mode == ND_PRO_AFFINE_SILU || s.mode == ND_PRO_AFFINE_MAP_SILU || s.mode == ND_PRO_AFFINE_GENMAP_SILU;
-    ND_REQUIRE(s.mode == ND_PRO_NONE || aff || s.mode == ND_PRO_LEAKY || s.mode == ND_PRO_LEAKY_SECOND, ND_E_BADARG,
-               "nd_conv3x3_wino4: unsupported prologue %d", s.mode);
-    ND_REQUIRE(s.mode != ND_PRO_AFFINE_GENMAP_SILU || (ntg == 2 && s.map && s.gamma && s.beta && !s.upsample && !s.map_blocked && s.c1 == 0 && s.c0 % KC4 == 0 &&
-                                                     nd_aligned16(s.map) && nd_aligned16(s.gamma) && nd_aligned16(s.beta)), ND_E_BADARG,
-               "nd_conv3x3_wino4: the in-kernel map prologue needs silu(pos_emb) (map), mlp[1].weight (gamma) and mlp[1].bias (beta), 16-byte aligned, one source of whole "
-               "16-channel chunks, no upsample addressing, the 16 x 32-region form");
-    ND_REQUIRE(!aff || s.mad, ND_E_BADARG, "nd_conv3x3_wino4: affine prologue needs mad");
-    ND_REQUIRE(s.mode != ND_PRO_AFFINE_MAP_SILU || (s.map && !s.upsample && nd_aligned16(s.map)), ND_E_BADARG,
-               "nd_conv3x3_wino4: the map prologue needs a 16-byte aligned map and no upsample addressing");
-    ND_REQUIRE(s.mode != ND_PRO_AFFINE_MAP_SILU || (long)(d->B * (long)d->H + 2) * d->W * 2 * (s.c0 + s.c1) * 4 < (1L << 30) - 65536, ND_E_SHAPE,
-               "nd_conv3x3_wino4: a scale / shift map of 1 GiB or more");
+    ND_REQUIRE(s.mode != ND_PRO_AFFINE_GENMAP_SILU || (s.map && s.gamma && s.beta && nd_aligned16(s.map) && nd_aligned16(s.gamma) && nd_aligned16(s.beta)),
+               ND_E_BADARG, "nd_conv3x3_wino4: %s", ND_W4_GENMAP_NEEDS);
+    ND_REQUIRE((s.mode != ND_PRO_AFFINE_SILU && s.mode != ND_PRO_AFFINE_MAP_SILU && s.mode != ND_PRO_AFFINE_GENMAP_SILU) || s.mad, ND_E_BADARG,
+               "nd_conv3x3_wino4: affine prologue needs mad");
+    ND_REQUIRE(s.mode != ND_PRO_AFFINE_MAP_SILU || (s.map && nd_aligned16(s.map)), ND_E_BADARG, "nd_conv3x3_wino4: %s", ND_W4_MAP_NEEDS);
     ND_REQUIRE(s.mode != ND_PRO_LEAKY_SECOND || s.p1, ND_E_BADARG, "nd_conv3x3_wino4: LEAKY_SECOND needs a second source");
-    ND_REQUIRE(!s.map_blocked || (s.mode == ND_PRO_AFFINE_MAP_SILU && (s.c0 + s.c1) % 16 == 0), ND_E_BADARG,
-               "nd_conv3x3_wino4: map_blocked needs the map prologue and a channel count that is a multiple of 16");
-    ND_REQUIRE(!s.unshuffle, ND_E_BADARG, "nd_conv3x3_wino4: no unshuffle addressing");
-    ND_REQUIRE(!s.upsample || (d->H % 2 == 0 && d->W % 2 == 0 && s.c1 == 0), ND_E_SHAPE,
-               "nd_conv3x3_wino4: nearest-x2 upsample addressing needs even H, W and a single source");
     ND_REQUIRE((d->stats == nullptr) == (d->slot_count == nullptr), ND_E_BADARG, "nd_conv3x3_wino4: stats and slot_count go together");
-    ND_REQUIRE(s.c1 == 0 || s.c0 % KC4 == 0, ND_E_SHAPE,
-               "nd_conv3x3_wino4: first concat source has %d channels; a 16-channel K chunk must not straddle the sources", s.c0);
-    ND_REQUIRE(d->W <= 2048 && d->H <= 32768, ND_E_SHAPE, "nd_conv3x3_wino4: image wider than 2048 (16-bit border table)");
-    {
-        const long px = (long)(d->B) * (d->H >> (s.upsample ? 1 : 0)) * (d->W >> (s.upsample ? 1 : 0));
-        // byte offsets (region base + relative pixel x stride + the out-of-range bias 0x7FFFFFF0) stay below 2^32, pixels below 2^24
-        const long ext = px + (d->W >> (s.upsample ? 1 : 0)) + 2;
-        ND_REQUIRE(ext * s.ld0 * 4 < (1L << 30) - 65536 && ext * s.ld1 * 4 < (1L << 30) - 65536 && ext < (1L << 24), ND_E_SHAPE,
-                   "nd_conv3x3_wino4: a source tensor of 1 GiB or 16 M pixels or more");
-    }
-
-    ND_REQUIRE((long)d->B * d->H * d->W * d->ldo * 4 < (1L << 32) - 65536, ND_E_SHAPE, "nd_conv3x3_wino4: an output tensor of 4 GiB or more");
+    if (int e = nd_conv3x3_wino4_shape(d, ntg, split, splits, "nd_conv3x3_wino4", who)) return e;
 
     a.d = *d;
     a.tiles_x = nd_cdiv(d->W, 16);
@@ -1237,16 +1207,10 @@ static int w4_prepare(const nd_conv3x3* d, Wino4Args& a, int ntg = 2) {
 // split-K launch shared by the entry points of both product forms: SPLIT instances into `workspace`, then the reduction (+ bias, + statistics)
 static int w4_splitk(const nd_conv3x3* d, float* workspace, int splits, void* stream, int ntg, const char* who) {
     Wino4Args a;
-    if (int e = w4_prepare(d, a, ntg)) return e;
+    if (int e = w4_prepare(d, a, ntg, true, splits, who)) return e;
     ND_REQUIRE(workspace && nd_aligned16(workspace), ND_E_BADARG, "%s: the workspace must be a 16-byte aligned pointer", who);
-    ND_REQUIRE(d->src.mode == ND_PRO_NONE || d->src.mode == ND_PRO_AFFINE_SILU, ND_E_BADARG,
-               "%s: plain or GroupNorm-affine + SiLU sources (no map / LeakyReLU prologue)", who);
     const int n_chunks = nd_cdiv(d->cin, KC4);
-    ND_REQUIRE((splits == 2 || splits == 4 || splits == 8) && d->cin % KC4 == 0 && n_chunks % splits == 0 && n_chunks / splits >= 2, ND_E_SHAPE,
-               "%s: splits=%d must be 2, 4 or 8 and divide cin=%d into ranges of at least two whole 16-channel chunks", who, splits, d->cin);
     const long npix = (long)d->B * d->H * d->W;
-    ND_REQUIRE((long)splits * npix * d->cout * 4 < (1L << 31), ND_E_SHAPE, "%s: partial sums of 2 GiB or more", who);
-    ND_REQUIRE(d->cout % 4 == 0, ND_E_SHAPE, "%s: cout must be a multiple of 4", who);
     const float* bias = d->bias;
     float* out = d->out;
     const int ldo = d->ldo;
@@ -1296,8 +1260,6 @@ extern "C" int nd_conv3x3_wino4_nhwc_f32(const nd_conv3x3* d, void* stream) {
 extern "C" int nd_conv3x3_wino4_16_nhwc_f32(const nd_conv3x3* d, void* stream) {
     Wino4Args a;
     if (int e = w4_prepare(d, a, 1)) return e;
-    ND_REQUIRE(d->src.mode == ND_PRO_NONE || d->src.mode == ND_PRO_AFFINE_SILU, ND_E_BADARG,
-               "nd_conv3x3_wino4_16: plain or GroupNorm-affine + SiLU sources (no map / LeakyReLU prologue)");
     hipStream_t st = (hipStream_t)stream;
     if (int rc = d->src.mode == ND_PRO_AFFINE_SILU ? launch4<ND_PRO_AFFINE_SILU, 1>(a, st) : launch4<ND_PRO_NONE, 1>(a, st)) return rc;
     return nd_launch_status("nd_conv3x3_wino4_16_nhwc_f32");

@@ -2,6 +2,7 @@
 #include <stdarg.h>
 #include <string.h>
 #include "nd_common.h"
+#include "conv3x3_desc.h"
 
 static thread_local char g_err[512] = "";
 
@@ -39,6 +40,13 @@ int nd_device_cus() {
 
 extern "C" int nd_version(void) { return 1000 * 0 + 2; }
 extern "C" const char* nd_last_error(void) { return g_err; }
+
+// The question the callers ask instead of restating a kernel's limits: that kernel's shape function, silent (conv3x3_desc.h)
+extern "C" int nd_conv3x3_takes(int kernel, const nd_conv3x3* d, int splits) {
+    if (!d || kernel < ND_CONV3X3_DIRECT || kernel > ND_CONV3X3_WINO4_16) return 0;
+    if (kernel >= ND_CONV3X3_WINO4) return nd_conv3x3_wino4_shape(d, kernel == ND_CONV3X3_WINO4 ? 2 : 1, splits > 1, splits, nullptr, nullptr) == 0;
+    return splits <= 1 && (kernel == ND_CONV3X3_WINO2 ? nd_conv3x3_wino2_shape(d, nullptr) : nd_conv3x3_f2_shape(d, nullptr)) == 0;
+}
 
 extern "C" int nd_device_arch(char* buf, int n) {
     ND_REQUIRE(buf && n > 0, ND_E_BADARG, "nd_device_arch: bad buffer");

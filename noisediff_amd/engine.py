@@ -30,6 +30,7 @@ from typing import Callable, Dict, List, Optional, Sequence, Tuple
 import torch
 
 from . import _lib as L
+from ._host import conv3x3_takes
 from .spec import (normalize_stage_attn, stage_attention_param_spec, ATTN_DIM_HEAD, ATTN_HEADS, ISO_DIM, ISO_TABLE_ROWS, POS_DIM, POS_GROUPS, RESNET_GROUPS, SHOT_GROUPS,
                    arch_param_spec, arch_traits, attention_param_spec, stage_dims)
 
@@ -51,7 +52,7 @@ WINO4 = os.environ.get("ND_WINO4", "1") != "0"           # A-B knob: 0 = never t
 # Low-latency mode for SMALL batches (opt-in: ND_SPLIT_K=1 or engine.SPLIT_K = True before the plans are recorded): plain-source F(4x4) layers whose
 # (sample, region, cout tile) items fill a fraction of the chip run on the split-K form (nd_conv3x3_wino4_splitk_nhwc_f32: one sample at 256 x 256 has 16
 # items for the 512 -> 512 layers at 32 x 32).  Off by default: the split count depends on the batch size, and with it the summation order over cin --
-# a sample's bits would depend on the batch it is sharded into, which the default path rules out (see _wino4_takes).  16 patches per GPU never split.
+# a sample's bits would depend on the batch it is sharded into, which the default path rules out (see conv3x3_form).  16 patches per GPU never split.
 SPLIT_K = os.environ.get("ND_SPLIT_K", "0") != "0"
 EIGHT_TILES_RULE = True  # layers with <= 8 tiles of the 16 x 32 form per sample go to the 16 x 16-region form (profiles/r3_eight_tiles_rule_ab.txt; was ND_W4_EIGHT_TILES)
 # r4: the F(4x4) kernel on 16 x 16-pixel regions with two co-resident workgroups per CU (nd_conv3x3_wino4_16_nhwc_f32).  "narrow" (default): where the
@@ -84,6 +85,71 @@ def _wino4_layer(cin: int, cout: int) -> bool:
     return cin > 16 and cin % 4 == 0 and cout % 4 == 0
 
 
+def conv3x3_form(B: int, H: int, W: int, cin: int, cout: int, c0: int, c1: int, ld0: int, ld1: int, mode: int, upsample: bool, packed4: bool, *,
+                 winograd=None, wino2=None, wino4=None, split_k=None, eight_tiles=None, wino4_16=None, wino4_16_split=None):
+    """The kernel of one 3x3 convolution of the sampling engine -> (form, splits, rows): the form "" (direct), "wino", "wino2", "wino4" (16 x 32-pixel regions, one workgroup
+    per CU) or "wino4_16" (16 x 16-pixel regions, two per CU), the K ranges of the split-K entry (1: the plain entry) and the samples ONE launch covers.  A pure function of
+    its integers; ``packed4``: the layer has a ``.weight.wino4`` packing; the module's knobs are keyword arguments (None: the module's value when the call is made)."""
+    knob = lambda value, default: default if value is None else value
+    k_winograd, k_wino2, k_wino4, k_split, k_eight = knob(winograd, WINOGRAD), knob(wino2, WINO2), knob(wino4, WINO4), knob(split_k, SPLIT_K), knob(eight_tiles, EIGHT_TILES_RULE)
+    k_16, k_16split = knob(wino4_16, WINO4_16), knob(wino4_16_split, WINO4_16_SPLIT)
+    # images of at least one 16x16 tile go through the Winograd F(2x2,3x3) kernel (2.25x fewer MFMAs)
+    if not (k_winograd and H >= 16 and W >= 16):
+        return "", 1, B
+
+    def piece(kernel: int, splits: int = 1, mode: int = mode) -> int:
+        """Samples one launch of ``kernel`` covers (0: it does not take the layer): the batch, else the largest piece the kernel takes, equalised over the launches -- same
+        kernel, weights and summation order per sample, so a sample's bits do not depend on the batch (the reference takes any --batch_size, test_diffusion.py:23-78)."""
+        takes = lambda b: b * H * W * cout * 4 < _LAUNCH_OUT_BYTES and conv3x3_takes(kernel, b, H, W, cin, cout, c0, c1, ld0, ld1, mode, upsample, splits=splits)
+        if takes(B):
+            return B
+        if not takes(1):
+            return 0
+        lo, hi = 1, B                              # largest b the kernel takes (its limits are monotone in B), then equal pieces
+        while lo < hi:
+            mid = (lo + hi + 1) // 2
+            lo, hi = (mid, hi) if takes(mid) else (lo, mid - 1)
+        return -(-B // -(-B // lo))
+
+    few = _few_items(H, W, cout)                                         # <= 8 items of the 16 x 32 form per SAMPLE
+    stored = L.PRO_AFFINE_MAP_SILU if mode == L.PRO_AFFINE_GENMAP_SILU else mode     # off the 16 x 32-region form the maps are stored, not formed in the kernel
+    form, rows = "", 0
+    # Every choice looks at ONE launch's piece, and the pieces are equal for every batch beyond a kernel's limits: the choice is a function of the sample's geometry alone.
+    # F(4x4,3x3) (1.78x fewer MFMAs than F(2x2,3x3); 16-channel K chunks) wherever a form of its kernel takes the layer, for the engine's own prologues
+    if k_wino4 and packed4 and mode in (L.PRO_NONE, L.PRO_AFFINE_SILU, L.PRO_AFFINE_MAP_SILU, L.PRO_AFFINE_GENMAP_SILU):
+        # the 16 x 16-region form: regions of any image are at least half used from W = 16 on (W % 16 == 0 or W >= 48)
+        if k_16 != "0" and (W % 16 == 0 or W >= 48) and (k_16 == "all" or W < 32 or (few and k_eight and not k_split)):
+            form, rows = "wino4_16", piece(L.CONV3X3_WINO4_16)
+        # Layers with at most eight F(4x4) workgroup tiles (16 x 32 pixels x 64 couts) per SAMPLE -- 256 -> 256 at 32 x 32 -- fill half of an
+        # MI355X at the usual 16 patches per GPU; F(2x2)'s 16 x 16-pixel tiles fill it (84 vs 114 us per layer).  The rule looks at the
+        # sample's geometry only: the kernel choice -- and with it the bits of a sample -- must not depend on the batch it is sharded into.
+        # (The opt-in low-latency mode, SPLIT_K, gives that up anyway and cuts these layers along cin instead.)
+        to_wino2 = not rows and k_wino2 and not k_split and k_eight and few and piece(L.CONV3X3_WINO2, mode=stored) > 0
+        # the 16 x 32-region form: images that fill its regions
+        if not rows and not to_wino2 and W >= 32 and (W % 32 == 0 or W >= 96):
+            form, rows = "wino4", piece(L.CONV3X3_WINO4)
+    splits = 1
+    if rows and form == "wino4" and k_split and mode in (L.PRO_NONE, L.PRO_AFFINE_SILU):
+        splits = int(L.load().nd_conv3x3_wino4_splitk_plan(B, H, W, cin, cout))
+    if rows and form == "wino4_16" and k_16split:     # few items per sample: K ranges by the SAMPLE's geometry (the batch never enters: a sample's bits stay batch-invariant)
+        splits = int(L.load().nd_conv3x3_wino4_16_splitk_plan(H, W, cin, cout))
+    if splits > 1:                                   # the partial sums of a launch stay below 2 GiB: smaller pieces, never another kernel
+        rows = piece(_FORM_KERNEL[form], splits)
+    if rows:
+        return form, splits, rows
+    # both F(2x2) kernels share weights, statistics slots and descriptor; wino2 (one resident wave per SIMD, all 16 position accumulators in registers) is the
+    # default, wino covers what it does not take, the direct kernel what neither does
+    for form in ("wino2", "wino") if k_wino2 else ("wino",):
+        rows = piece(_FORM_KERNEL[form], mode=stored)
+        if rows:
+            return form, 1, rows
+    return "", 1, B
+
+
+# Policy, not a kernel's limit (the F(4x4) entries take outputs up to 4 GiB): one launch writes less than 2 GiB.  The rule this function replaced held every
+# piece to the split-K partial-sum bound at ONE range too; kept, so that no layer's launches change.
+_LAUNCH_OUT_BYTES = 2 * 1024 ** 3
+_FORM_KERNEL = {"": L.CONV3X3_DIRECT, "wino": L.CONV3X3_WINO, "wino2": L.CONV3X3_WINO2, "wino4": L.CONV3X3_WINO4, "wino4_16": L.CONV3X3_WINO4_16}
 _MAP_PRODUCERS = ("pos_block1.mlp.1.weight", "pos_block2.mlp.1.weight")
 
 
@@ -483,8 +549,7 @@ class Plan:
             # the maps' consumers are pos_block{1,2}.block2.proj (d -> d, map prologue): formed inside conv3x3_wino4's 16 x 32-region form where that takes the layer
             # (a function of the sample's geometry alone), else stored -- in the blocked layout when the layer runs on conv3x3_wino4 at all
             self.posgen = (GENMAP and eng.traits.position and all(b + ".mlp.1.weight.gen" in eng.slots for b in ("pos_block1", "pos_block2")) and d % 16 == 0 and
-                           self._wino4_kind("pos_block1.block2.proj", L.PRO_AFFINE_GENMAP_SILU, False, d, 0, d, 0, d, d, H, W,
-                                            self._conv_rows(H, W, 0, d, 0, d, d, L.PRO_AFFINE_GENMAP_SILU)) == "wino4")
+                           conv3x3_form(B, H, W, d, d, d, 0, d, 0, L.PRO_AFFINE_GENMAP_SILU, False, "pos_block1.block2.proj.weight.wino4" in eng.slots)[0] == "wino4")
             self.posmap1 = self.posmap2 = None
             if self.posgen:
                 self.pos_e = f(B, H, W, POS_DIM)             # silu(pos_emb): what ResnetBlock2.mlp = Sequential(SiLU, Conv2d) applies its 1x1 to (Diffusion_arch.py:177)
@@ -493,7 +558,7 @@ class Plan:
                 self.posmap1 = f(B, H, W, 2 * d)
                 self.posmap2 = f(B, H, W, 2 * d)
             self.posmap_blocked = (not self.posgen and MAP_BLOCKED and "pos_block1.mlp.1.weight.blk16" in eng.slots and
-                                   self._wino4_takes("pos_block1.block2.proj", L.PRO_AFFINE_MAP_SILU, False, d, 0, d, 0, d, d, H, W))
+                                   conv3x3_form(B, H, W, d, d, d, 0, d, 0, L.PRO_AFFINE_MAP_SILU, False, "pos_block1.block2.proj.weight.wino4" in eng.slots)[::2] == ("wino4", B))   # the batch in ONE launch
             self.iso_emb = f(B, ISO_DIM)
             self.attn_names = [p.name[:-len(".attn.to_v.weight")] for p in eng.spec if p.name.endswith(".attn.to_v.weight")]
             self.cb = {n: f(B, eng.slots[n + ".proj_out.bias"].shape[0]) for n in self.attn_names}
@@ -549,45 +614,15 @@ class Plan:
             setattr(s, k, v.data_ptr() if isinstance(v, torch.Tensor) else v)
         return s
 
-    def _conv_rows(self, H: int, W: int, up: int, ld0: int, ld1: int, cin: int, cout: int, mode: int, splits: int = 1) -> int:
-        """Samples ONE conv3x3 launch covers.  The Winograd kernels address their sources through 32-bit buffer offsets (sources below 1 GiB and 2^24 pixels,
-        outputs below 4 GiB, split-K partial sums below 2 GiB): a larger batch is cut into equal pieces of whole samples -- same kernel, same weights, same
-        summation order per sample, so a sample's bits do not depend on the batch (the reference takes any --batch_size, test_diffusion.py:23-78)."""
-        sh, sw, lim = H >> up, W >> up, (1 << 30) - (1 << 16)
-
-        def fits(b: int) -> bool:
-            px = b * sh * sw + sw + 2
-            return (px * 4 * max(ld0, ld1) < lim and px < (1 << 24) and b * H * W < (1 << 24) and b * H * W * cout * 4 < (1 << 32) - (1 << 16)
-                    and (mode != L.PRO_AFFINE_MAP_SILU or (b * H + 2) * W * 8 * cin < lim) and splits * b * H * W * cout * 4 < (1 << 31))
-        if fits(self.B):
-            return self.B
-        lo, hi = 1, self.B                         # largest b that fits (fits is monotone), then equal pieces
-        while lo < hi:
-            mid = (lo + hi + 1) // 2
-            lo, hi = (mid, hi) if fits(mid) else (lo, mid - 1)
-        if not fits(lo):
-            raise L.HipError(f"conv3x3 at {H} x {W} x {max(ld0, ld1)}: one sample exceeds the kernels' 1 GiB source limit")
-        pieces = -(-self.B // lo)
-        return -(-self.B // pieces)
-
     def conv3(self, name: str, src: L.Src, cin: int, cout: int, H: int, W: int, stats: bool):
         """nn.Conv2d(cin, cout, 3, padding=1); returns (out, stats, slot_count, slots)."""
         e = self.e
         out = self._alloc(self.B, H, W, cout)
-        # images of at least one 16x16 tile go through the Winograd F(2x2,3x3) kernel (2.25x fewer MFMAs)
-        wino = WINOGRAD and H >= 16 and W >= 16
         up = 1 if src.upsample else 0
-        # rows per launch (the whole batch at the bench sizes).  Every kernel choice below looks at ONE launch's piece, and the pieces are equal for every
-        # batch beyond the limit: the choice is a function of the sample's geometry alone
-        rows = self._conv_rows(H, W, up, src.ld0, src.ld1, cin, cout, src.mode) if wino else self.B
-        # both Winograd kernels share weights, statistics slots and descriptor; wino2 (one resident wave per SIMD,
-        # all 16 position accumulators in registers) is the default, wino covers what it does not take
-        wino2 = (wino and WINO2 and not (src.mode == L.PRO_AFFINE_MAP_SILU and src.upsample)
-                 and (src.c1 == 0 or src.c0 % 32 == 0) and rows * H * W < (1 << 24)
-                 and rows * H * W * 4 * max(src.ld0, src.ld1, 2 * cin if src.mode == L.PRO_AFFINE_MAP_SILU else 0) < (1 << 31))
-        w4kind = self._wino4_kind(name, src.mode, bool(src.upsample), src.c0, src.c1, src.ld0, src.ld1, cin, cout, H, W, rows) if wino else ""
-        wino4 = bool(w4kind)
-        if src.mode == L.PRO_AFFINE_GENMAP_SILU and w4kind != "wino4":
+        # the kernel form, the K ranges of its split-K entry and the rows per launch (the whole batch at the bench sizes)
+        form, splits, rows = conv3x3_form(self.B, H, W, cin, cout, src.c0, src.c1, src.ld0, src.ld1, src.mode, bool(src.upsample), (name + ".weight.wino4") in e.slots)
+        wino, wino2, wino4 = form != "", form == "wino2", form.startswith("wino4")
+        if src.mode == L.PRO_AFFINE_GENMAP_SILU and form != "wino4":
             raise L.HipError(f"{name}: maps formed in the kernel need conv3x3_wino4's 16 x 32-region form (Plan.posgen decides by the same rule)")
         if wino and not wino4 and (name + ".weight.wino4") in e.slots and src.mode in (L.PRO_NONE, L.PRO_AFFINE_SILU, L.PRO_AFFINE_MAP_SILU) and not _few_items(H, W, cout):
             _log.warning("%s (%d -> %d at %d x %d, batch %d): not on the F(4x4) kernel", name, cin, cout, H, W, self.B)
@@ -601,16 +636,9 @@ class Plan:
         if src.map_blocked and not wino4:
             raise L.HipError(f"{name}: the scale / shift map was produced in the blocked layout but the layer does not run on conv3x3_wino4")
         # ONE packing of the weight is read (and marked for the weight broadcast): F(4x4), F(2x2) or the direct form
-        lowlat_split = SPLIT_K and w4kind == "wino4" and src.mode in (L.PRO_NONE, L.PRO_AFFINE_SILU) and int(e.lib.nd_conv3x3_wino4_splitk_plan(self.B, H, W, cin, cout)) > 1
         weight = e.p(name + (".weight.wino4" if wino4 else ".weight.wino" if wino else ".weight"))
-        entry = (f"nd_conv3x3_{w4kind}_nhwc_f32" if wino4 else "nd_conv3x3_wino2_nhwc_f32" if wino2 else
-                 "nd_conv3x3_wino_nhwc_f32" if wino else "nd_conv3x3_nhwc_f32")
-        tiling = (9016 if w4kind == "wino4_16" else 9004) if wino4 else 9002 if wino2 else 9001 if wino else e.lib.nd_conv3x3_tiling_id(self.B, H, W, cout)
-        splits = int(e.lib.nd_conv3x3_wino4_splitk_plan(self.B, H, W, cin, cout)) if lowlat_split else 1
-        if w4kind == "wino4_16" and WINO4_16_SPLIT:      # few items per sample: K ranges by the SAMPLE's geometry (the batch never enters: a sample's bits stay batch-invariant)
-            splits = int(e.lib.nd_conv3x3_wino4_16_splitk_plan(H, W, cin, cout))
-        if splits > 1:                                   # the partial sums of a launch stay below 2 GiB: smaller pieces, never another kernel
-            rows = self._conv_rows(H, W, up, src.ld0, src.ld1, cin, cout, src.mode, splits)
+        entry = f"nd_conv3x3_{form}_nhwc_f32" if form else "nd_conv3x3_nhwc_f32"
+        tiling = (9016 if form == "wino4_16" else 9004) if wino4 else 9002 if wino2 else 9001 if wino else e.lib.nd_conv3x3_tiling_id(self.B, H, W, cout)
         ws = self._alloc(splits * rows * H * W * cout) if splits > 1 else None
         sh, sw, ctot = H >> up, W >> up, src.c0 + src.c1
         for b0 in range(0, self.B, rows):                # one launch per piece of `rows` samples (one piece at the bench sizes)
@@ -632,56 +660,13 @@ class Plan:
             meta = {"layer": name, "B": nb, "H": H, "W": W, "cin": cin, "cout": cout, "mode": int(src.mode), "tiling": tiling}
             if splits > 1:
                 meta["splits"] = splits
-                entry_s = "nd_conv3x3_wino4_16_splitk_nhwc_f32" if w4kind == "wino4_16" else "nd_conv3x3_wino4_splitk_nhwc_f32"
-                self._add(entry_s, C.byref(d), ws.data_ptr(), splits, e.stream, meta=meta)
+                self._add(f"nd_conv3x3_{form}_splitk_nhwc_f32", C.byref(d), ws.data_ptr(), splits, e.stream, meta=meta)
             else:
                 self._add(entry, C.byref(d), e.stream, meta=meta)
             self._keep.append(d)
         if ws is not None:
             self._release(ws)
         return out, st, sc, slots
-
-    def _wino4_kind(self, name: str, mode: int, upsample: bool, c0: int, c1: int, ld0: int, ld1: int, cin: int, cout: int, H: int, W: int, rows: Optional[int] = None) -> str:
-        """"wino4" (16 x 32-pixel regions, one workgroup per CU), "wino4_16" (16 x 16-pixel regions, two per CU) or "" (another kernel).
-        F(4x4,3x3) (1.78x fewer MFMAs than F(2x2,3x3); 16-channel K chunks) wherever a form of its kernel takes the
-        layer: plain / GroupNorm-affine (+ per-pixel map) + SiLU inputs, concat on a chunk boundary, images that fill its regions,
-        sources below 1 GiB and 2^24 pixels (the host checks of nd_conv3x3_wino4_nhwc_f32)."""
-        up = 1 if upsample else 0
-        rows = self.B if rows is None else rows                          # samples of one launch (conv3 cuts a batch beyond the kernels' limits into pieces)
-        src_px = rows * (H >> up) * (W >> up) + (W >> up) + 2            # the kernel's buffer resource starts one row + one pixel in front of the tensor
-        src_bytes = src_px * 4 * max(ld0, ld1)
-        common = (WINOGRAD and WINO4 and H >= 16 and W >= 16 and cout <= 2048 and (name + ".weight.wino4") in self.e.slots
-                  and W <= 2048 and (c1 == 0 or (c0 % 16 == 0 and not up)) and src_bytes < (1 << 30) - (1 << 16) and src_px < (1 << 24)
-                  and (not up or (H % 2 == 0 and W % 2 == 0)))
-        if not common:
-            return ""
-        # the 16 x 16-region form: plain and affine + SiLU sources; regions of any image are at least half used from W = 16 on (W % 16 == 0 or W >= 48)
-        takes16 = WINO4_16 != "0" and mode in (L.PRO_NONE, L.PRO_AFFINE_SILU) and (W % 16 == 0 or W >= 48)
-        few = _few_items(H, W, cout)                                     # <= 8 items of the 16 x 32 form per SAMPLE
-        if takes16 and (WINO4_16 == "all" or W < 32 or (few and EIGHT_TILES_RULE and not SPLIT_K)):
-            return "wino4_16"
-        return "wino4" if self._wino4_takes(name, mode, upsample, c0, c1, ld0, ld1, cin, cout, H, W, rows) else ""
-
-    def _wino4_takes(self, name: str, mode: int, upsample: bool, c0: int, c1: int, ld0: int, ld1: int, cin: int, cout: int, H: int, W: int, rows: Optional[int] = None) -> bool:
-        """The 16 x 32-region form."""
-        up = 1 if upsample else 0
-        # Layers with at most eight F(4x4) workgroup tiles (16 x 32 pixels x 64 couts) per SAMPLE -- 256 -> 256 at 32 x 32 -- fill half of an
-        # MI355X at the usual 16 patches per GPU; F(2x2)'s 16 x 16-pixel tiles fill it (84 vs 114 us per layer).  The rule looks at the
-        # sample's geometry only: the kernel choice -- and with it the bits of a sample -- must not depend on the batch it is sharded into.
-        # (The opt-in low-latency mode, SPLIT_K, gives that up anyway and cuts these layers along cin instead.)
-        if (WINO2 and not SPLIT_K and EIGHT_TILES_RULE and ((H + 15) // 16) * ((W + 31) // 32) * ((cout + 63) // 64) <= 8 and (c1 == 0 or c0 % 32 == 0)
-                and not (mode == L.PRO_AFFINE_MAP_SILU and up)):
-            return False
-        rows = self.B if rows is None else rows
-        src_px = rows * (H >> up) * (W >> up) + (W >> up) + 2            # the kernel's buffer resource starts one row + one pixel in front of the tensor
-        src_bytes = src_px * 4 * max(ld0, ld1)
-        return (WINOGRAD and WINO4 and H >= 16 and W >= 16 and cout <= 2048 and (name + ".weight.wino4") in self.e.slots
-                and mode in (L.PRO_NONE, L.PRO_AFFINE_SILU, L.PRO_AFFINE_MAP_SILU, L.PRO_AFFINE_GENMAP_SILU)
-                and not (mode == L.PRO_AFFINE_MAP_SILU and (up or (rows * H + 2) * W * 8 * cin >= (1 << 30) - (1 << 16)))
-                and not (mode == L.PRO_AFFINE_GENMAP_SILU and (up or c1 or cin % 16))
-                and W >= 32 and (W % 32 == 0 or W >= 96) and W <= 2048 and (c1 == 0 or (c0 % 16 == 0 and not up))
-                and src_bytes < (1 << 30) - (1 << 16) and src_px < (1 << 24)
-                and (not up or (H % 2 == 0 and W % 2 == 0)))
 
     def pw(self, name: str, src: L.Src, cin: int, cout: int, HW: int, W: int, act=L.ACT_NONE, bias=True,
            res0=None, res1=None, vec=None, gn_t=None, gn_mad=None, out=None, variant: str = "") -> torch.Tensor:
@@ -778,7 +763,7 @@ class Plan:
         if tail is not None and not split:
             raise L.HipError(f"{name}: the tail prologue is a form of the split chain only")
         # the split kernel addresses its tensors through 32-bit buffer offsets (below 4 GiB): a larger batch runs as equal pieces of whole samples -- same kernel,
-        # same arithmetic per pixel, so a sample's bits do not depend on the batch (as Plan._conv_rows does for the convolutions)
+        # same arithmetic per pixel, so a sample's bits do not depend on the batch (as conv3x3_form does for the convolutions)
         rows = self.B
         if split:
             per = 4 * HW * max(src.ld0, src.ld1, ldo, *([t.shape[-1] for t in tail[1:] if t is not None] if tail else []))

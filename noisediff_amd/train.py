@@ -206,10 +206,10 @@ def conv3x3_with_stats(x: torch.Tensor, weight: torch.Tensor, bias: Optional[tor
 
 def cat_sources_ok(x0: torch.Tensor, x1: torch.Tensor, cout: Optional[int] = None) -> bool:
     """Can conv3x3_cat / conv1x1_cat take this pair (else the caller concatenates)?  The F(4x4) kernel's geometry and whole 16-channel chunks per source;
-    ``cout`` (when given): a multiple of 8 within the kernel's bias table (2048)."""
+    ``cout`` (when given): a multiple of 8 (within the kernel's bias table: conv3x3_kind's question)."""
     B, c0, H, W = x0.shape
     c1 = x1.shape[1]
-    if cout is not None and (cout % 8 or cout > 2048):
+    if cout is not None and cout % 8:
         return False
     return (x0.is_cuda and x1.is_cuda and x0.dim() == 4 and tuple(x1.shape[2:]) == (H, W) and x1.shape[0] == B and c0 % 16 == 0 and c1 % 16 == 0
             and conv3x3_kind(B, H, W, c0 + c1, cout or 8, c0, c1, c0 + c1) == "wino4")      # ld = c0 + c1 as in _conv3x3_nhwc; no cout: 8

@@ -42,6 +42,8 @@ ENTRIES = {
     "wino4_splitk": ("nd_conv3x3_wino4_splitk_nhwc_f32", "nd_pack_conv3x3_wino4_weight", 4, 16, True, True, (16, 16)),
     "wino4_16_splitk": ("nd_conv3x3_wino4_16_splitk_nhwc_f32", "nd_pack_conv3x3_wino4_weight", 4, 16, True, True, (16, 16)),
 }
+KERNELS = {"direct": L.CONV3X3_DIRECT, "wino": L.CONV3X3_WINO, "wino2": L.CONV3X3_WINO2, "wino4": L.CONV3X3_WINO4, "wino4_16": L.CONV3X3_WINO4_16,
+           "wino4_splitk": L.CONV3X3_WINO4, "wino4_16_splitk": L.CONV3X3_WINO4_16}
 MODES = {"none": L.PRO_NONE, "concat": L.PRO_NONE, "upsample": L.PRO_NONE, "affine": L.PRO_AFFINE_SILU, "map": L.PRO_AFFINE_MAP_SILU, "map_blocked": L.PRO_AFFINE_MAP_SILU,
          "genmap": L.PRO_AFFINE_GENMAP_SILU, "leaky": L.PRO_LEAKY, "leaky_second": L.PRO_LEAKY_SECOND}
 STATS_PROLOGUES = ("none", "affine", "map", "map_blocked", "genmap", "concat")      # what the sampler puts in front of a convolution whose output a GroupNorm follows
@@ -208,6 +210,12 @@ def launch(ctx, entry, inp, stats, splits=0):
         rc, msg = 1, str(e)
     if rc > 0:          # a HIP error, not a refusal (those are negative): the device may have faulted -- nothing more runs on it from this file
         pytest.exit(f"{entry} {inp['case']} {inp['pro']}: HIP error {rc}: {msg}", returncode=3)
+    # The library's own answer for this entry and descriptor agrees with what the entry did: every pointer of this file is valid and aligned, so a refusal here
+    # is a refusal of the shape.  (A split-K entry called with splits <= 1 refuses; the question at splits <= 1 is about the plain entry and is not asked.)
+    if not ENTRIES[entry][5] or splits > 1:
+        takes = ctx.lib.nd_conv3x3_takes(KERNELS[entry], C.byref(d), splits if ENTRIES[entry][5] else 1)
+        assert takes == (rc == 0), f"{entry} {inp['case']} {inp['pro']}: nd_conv3x3_takes says {takes}, the entry returned {rc} '{msg}'"
+        assert not rc or ctx.lib.nd_last_error().decode() == msg, "nd_conv3x3_takes wrote to nd_last_error"
     del src
     return rc, msg, out, st, sc, ws
 

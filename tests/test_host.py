@@ -443,6 +443,134 @@ def test_conv3x3_kind_keeps_the_train_and_lsid_decisions_at_their_limits():
     assert kind(2, 64, 40, 64, 64, 64, 0, 64) == "wino2"
 
 
+def _takes(kernel, B=2, H=32, W=32, cin=64, cout=64, c0=None, c1=0, ld0=None, ld1=None, **kw):
+    from noisediff_amd._host import conv3x3_takes
+    c0 = cin - c1 if c0 is None else c0
+    return conv3x3_takes(kernel, B, H, W, cin, cout, c0, c1, c0 if ld0 is None else ld0, (c1 if ld1 is None else ld1), **kw)
+
+
+def test_conv3x3_takes_answers_on_both_sides_of_each_limit():
+    """nd_conv3x3_takes (host code, no GPU) just inside and just outside every limit of each kernel's shape function in csrc/conv3x3_desc.h."""
+    every = (L.CONV3X3_DIRECT, L.CONV3X3_WINO, L.CONV3X3_WINO2, L.CONV3X3_WINO4, L.CONV3X3_WINO4_16)
+    f2, f4 = every[:3], every[3:]
+    for k in every:                                                      # nd_conv3x3_common_shape
+        assert _takes(k) and not _takes(k, B=0) and not _takes(k, c0=60) and not _takes(k, cin=66, c0=62, c1=4, ld0=64)
+        assert _takes(k, ld0=68) and not _takes(k, ld0=60) and not _takes(k, ld0=66) and not _takes(k, cin=96, c1=32, ld1=28)
+        assert _takes(k, H=34, upsample=True) and not _takes(k, H=33, upsample=True) and not _takes(k, cin=96, c1=32, upsample=True)
+        assert _takes(k, mode=L.PRO_AFFINE_SILU) and not _takes(k, mode=L.PRO_LAYERNORM) and _takes(k, ldo=68) and not _takes(k, ldo=60)
+    for k in f2:                                                         # nd_conv3x3_f2_shape
+        assert _takes(k, cin=72) and not _takes(k, cin=60) and _takes(k, ldo=66)
+        assert _takes(k, mode=L.PRO_LEAKY_SECOND, cin=96, c1=32) and not _takes(k, mode=L.PRO_AFFINE_GENMAP_SILU)
+        assert _takes(k, mode=L.PRO_AFFINE_MAP_SILU) and not _takes(k, mode=L.PRO_AFFINE_MAP_SILU, map_blocked=True)
+        assert _takes(k, cin=8, cout=4100, H=8, W=8)                     # no cin > 16, no cout <= 2048, no 16 x 16 tile: those are F(4x4)'s / policy
+    for k in f2[:2]:                                                     # direct and wino: nothing of their own -- past wino2's limits they still take the layer
+        assert _takes(k, B=64, H=512, W=512) and _takes(k, cin=64, c0=16, c1=48) and _takes(k, mode=L.PRO_AFFINE_MAP_SILU, upsample=True)
+    k = L.CONV3X3_WINO2                                                  # nd_conv3x3_wino2_shape
+    assert not _takes(k, mode=L.PRO_AFFINE_MAP_SILU, upsample=True)
+    assert _takes(k, B=63, H=512, W=512, cin=8) and not _takes(k, B=64, H=512, W=512, cin=8)         # 2^24 pixels
+    lim = ((1 << 31) - 1) // (7 * 2048 + 7)
+    assert _takes(k, B=1, H=16, W=2048, ldo=lim) and not _takes(k, B=1, H=16, W=2048, ldo=lim + 1)   # (7 W + 7) ldo < 2^31
+    assert _takes(k, B=127, H=256, W=256) and not _takes(k, B=128, H=256, W=256)                     # sources 64 KB below 2 GiB ...
+    assert 4681 * 256 * 448 * 4 == (1 << 31) - 65536
+    assert _takes(k, B=4680, H=16, W=16, ld0=448) and not _takes(k, B=4681, H=16, W=16, ld0=448)     # ... to the byte
+    assert _takes(k, B=4681, H=16, W=16, ld0=444) and not _takes(k, B=4681, H=16, W=16, cin=96, c1=32, ld0=64, ld1=448)
+    assert _takes(k, B=63, H=256, W=256, mode=L.PRO_AFFINE_MAP_SILU) and not _takes(k, B=64, H=256, W=256, mode=L.PRO_AFFINE_MAP_SILU)    # the map: 2 cin floats per pixel
+    assert _takes(k, cin=96, c0=32, c1=64) and _takes(k, cin=96, c0=64, c1=32) and not _takes(k, cin=96, c0=48, c1=48)   # a 32-channel chunk must not straddle
+    for k in f4:                                                         # nd_conv3x3_wino4_shape
+        assert _takes(k, cin=20) and not _takes(k, cin=16) and not _takes(k, cout=62) and _takes(k, cout=2048) and not _takes(k, cout=2052)
+        assert not _takes(k, ldo=66) and _takes(k, cin=96, c0=48, c1=48) and not _takes(k, cin=96, c0=40, c1=56)
+        assert _takes(k, B=1, H=16, W=2048) and not _takes(k, B=1, H=16, W=2052)
+        assert _takes(k, B=1, H=32768, W=32) and not _takes(k, B=1, H=32770, W=32)
+        assert _takes(k, B=63, H=256, W=256) and not _takes(k, B=64, H=256, W=256)                   # sources 64 KB below 1 GiB, counted from one row + one pixel ahead (with at least 16 channels per source the 2^24-pixel bound lies behind it)
+        assert _takes(k, B=31, H=256, W=256, ld0=128) and not _takes(k, B=32, H=256, W=256, ld0=128)
+        assert _takes(k, B=63, H=256, W=256, cin=96, c0=64, c1=32) and not _takes(k, B=32, H=256, W=256, cin=96, c0=64, c1=32, ld1=128)
+        assert _takes(k, B=63, H=256, W=256, cin=32, cout=256) and not _takes(k, B=64, H=256, W=256, cin=32, cout=256)  # outputs 64 KB below 4 GiB
+        assert _takes(k, B=127, H=256, W=256, cin=32, cout=64, upsample=True) and not _takes(k, B=32, H=256, W=256, cin=32, cout=256, ldo=512)
+        assert not _takes(k, map_blocked=True) and not _takes(k, mode=L.PRO_AFFINE_MAP_SILU, upsample=True)
+        for s in (2, 4, 8):                                              # split-K: 2, 4 or 8 ranges of at least two whole chunks, plain / affine sources, partial sums below 2 GiB
+            assert _takes(k, cin=32 * s, splits=s) and not _takes(k, cin=16 * s, splits=s) and not _takes(k, cin=32 * s + 16, splits=s) and not _takes(k, cin=32 * s + 8, splits=s)
+            assert _takes(k, B=128 // s - 1, H=256, W=256, cin=32 * s, splits=s) and not _takes(k, B=128 // s, H=256, W=256, cin=32 * s, splits=s)
+        assert _takes(k, B=63, H=256, W=256, splits=2)
+        assert not _takes(k, cin=96, splits=3) and not _takes(k, cin=512, splits=16) and _takes(k, mode=L.PRO_AFFINE_SILU, splits=2)
+    k = L.CONV3X3_WINO4                                                  # the 16 x 32-region form alone: every prologue of the family
+    assert _takes(k, mode=L.PRO_LEAKY) and _takes(k, mode=L.PRO_LEAKY_SECOND, cin=96, c1=32) and not _takes(k, mode=L.PRO_LEAKY, splits=2)
+    assert _takes(k, B=31, H=256, W=256, mode=L.PRO_AFFINE_MAP_SILU) and not _takes(k, B=32, H=256, W=256, mode=L.PRO_AFFINE_MAP_SILU)    # a map 64 KB below 1 GiB
+    assert _takes(k, mode=L.PRO_AFFINE_MAP_SILU, map_blocked=True) and not _takes(k, cin=72, mode=L.PRO_AFFINE_MAP_SILU, map_blocked=True)
+    assert _takes(k, mode=L.PRO_AFFINE_GENMAP_SILU) and not _takes(k, cin=72, mode=L.PRO_AFFINE_GENMAP_SILU) and not _takes(k, mode=L.PRO_AFFINE_GENMAP_SILU, splits=2)
+    assert not _takes(k, cin=96, c1=32, mode=L.PRO_AFFINE_GENMAP_SILU) and not _takes(k, mode=L.PRO_AFFINE_GENMAP_SILU, upsample=True)
+    k = L.CONV3X3_WINO4_16                                               # the 16 x 16-region form: plain and affine + SiLU sources
+    for mode in (L.PRO_AFFINE_MAP_SILU, L.PRO_AFFINE_GENMAP_SILU, L.PRO_LEAKY, L.PRO_LEAKY_SECOND):
+        assert not _takes(k, cin=96, c1=32 if mode == L.PRO_LEAKY_SECOND else 0, mode=mode)
+    assert not _takes(5) and not _takes(-1)                              # no such kernel
+
+
+def test_a_question_is_not_a_failure():
+    """nd_conv3x3_takes answering 0 leaves nd_last_error as the last refusal wrote it."""
+    lib = L.load()
+    assert lib.nd_conv3x3_wino_nhwc_f32(None, None) == -1               # a host-only refusal: returns before any HIP call
+    said = lib.nd_last_error()
+    assert b"nd_conv3x3_wino: null descriptor" in said
+    for k in (L.CONV3X3_DIRECT, L.CONV3X3_WINO, L.CONV3X3_WINO2, L.CONV3X3_WINO4, L.CONV3X3_WINO4_16):
+        assert not _takes(k, cin=12) and not _takes(k, H=33, upsample=True) and not _takes(k, ldo=60) and not _takes(k, splits=3)
+        assert lib.nd_last_error() == said
+    assert lib.nd_conv3x3_takes(L.CONV3X3_WINO4, None, 1) == 0 and lib.nd_last_error() == said
+
+
+def test_conv3x3_kind_answers_a_repeated_shape_from_its_cache():
+    from noisediff_amd._host import conv3x3_kind
+    shape = (3, 48, 80, 64, 64, 64, 0, 64)
+    first = conv3x3_kind(*shape)
+    before = conv3x3_kind.cache_info()
+    assert conv3x3_kind(*shape) == first == "wino2"
+    after = conv3x3_kind.cache_info()
+    assert (after.hits, after.misses) == (before.hits + 1, before.misses)
+
+
+_FORM_KERNEL = {"": L.CONV3X3_DIRECT, "wino": L.CONV3X3_WINO, "wino2": L.CONV3X3_WINO2, "wino4": L.CONV3X3_WINO4, "wino4_16": L.CONV3X3_WINO4_16}
+_KIND_KERNEL = dict(_FORM_KERNEL, direct=L.CONV3X3_DIRECT)
+
+
+def conv3x3_selection_differences():
+    """Rows of tests/golden/conv3x3_selection.json this tree decides otherwise: (rule, inputs, recorded, now, permitted).  Permitted is only a row whose
+    recorded choice raises or names a kernel that refuses the descriptor (nd_conv3x3_takes says 0 for it); for the F(2x2) and direct forms `rows` may grow
+    (never more launches) where the form and the split count are the recorded ones."""
+    import json
+    from noisediff_amd import engine, train
+    from noisediff_amd._host import conv3x3_kind, conv3x3_takes
+    table = json.load(open(os.path.join(REPO, "tests", "golden", "conv3x3_selection.json")))
+    out = []
+    for *row, form, splits, rows in table["form"]:                      # a row: the inputs, then what was decided
+        B, H, W, cin, cout, c0, c1, ld0, ld1, mode, up, packed, split_k, w16 = row
+        old = [form, splits, rows]
+        try:
+            new = list(engine.conv3x3_form(B, H, W, cin, cout, c0, c1, ld0, ld1, mode, bool(up), bool(packed), split_k=bool(split_k), wino4_16=("narrow", "all", "0")[w16]))
+        except L.HipError:
+            new = ["raise", 0, 0]
+        same = new == old or (new[:2] == old[:2] and not old[0].startswith("wino4") and old[0] != "raise" and new[2] >= old[2] and -(-B // new[2]) <= -(-B // old[2]))
+        if not same:
+            refused = old[0] == "raise" or not conv3x3_takes(_FORM_KERNEL[old[0]], old[2], H, W, cin, cout, c0, c1, ld0, ld1, mode, bool(up), splits=old[1])
+            out.append(("form", row, old, new, refused))
+    for *row, old in table["kind"]:
+        B, H, W, cin, cout, c0, c1, ld, w4 = row
+        new = conv3x3_kind(B, H, W, cin, cout, c0, c1, ld, wino4=bool(w4))
+        if new != old:
+            out.append(("kind", row, old, new, not conv3x3_takes(_KIND_KERNEL[old], B, H, W, cin, cout, c0, c1, ld, ld if c1 else 0)))
+    for *row, old in table["cat"]:
+        B, c0, c1, H, W, cout = row
+        new = bool(train.cat_sources_ok(_cuda_like(B, c0, H, W), _cuda_like(B, c1, H, W), cout))
+        if new != old:
+            out.append(("cat", row, old, new, old and not conv3x3_takes(L.CONV3X3_WINO4, B, H, W, c0 + c1, cout or 8, c0, c1, c0 + c1, c0 + c1)))
+    return table, out
+
+
+def test_conv3x3_rules_decide_what_the_recorded_table_says():
+    """engine.conv3x3_form, _host.conv3x3_kind and train.cat_sources_ok against the table recorded (tools/record_conv3x3_selection.py) when every limit was
+    still spelled out in Python: the same form, split count and rows per launch, except where the recorded choice raised or picked a kernel that refuses."""
+    table, diff = conv3x3_selection_differences()
+    assert len(table["form"]) > 1500 and len(table["kind"]) > 800 and len(table["cat"]) > 200
+    assert [d for d in diff if not d[4]] == []
+
+
 def test_sampling_split_k_plan_looks_at_the_sample_geometry_only():
     """nd_conv3x3_wino4_16_splitk_plan (host code, no GPU) has no batch argument: BASELINE config 2's 16 x 16 and 32 x 32 stages are cut into K ranges
     (about 32 items per sample, at least four 16-channel chunks per range), the layers of the 256 x 256 workload that reach the 16 x 16-region form
