@@ -32,6 +32,40 @@ def full(shape, value=float("nan")):
     return _settle(torch.full(shape, value, device=DEV))
 
 
+GUARD = 64
+
+
+class Guarded:
+    """A device allocation around a host tensor: NaN everywhere but the tensor.  NHWC images ([B][H][W][C], ``pad`` unused columns per pixel): [1 + B H + 1][W][C + pad];
+    anything else flat with GUARD floats on each side.  ``ptr`` addresses the tensor's first element (16-byte aligned: strides are multiples of 4 floats)."""
+
+    def __init__(self, t, pad=None):
+        self.shape = tuple(t.shape)
+        if pad is None:
+            host = torch.full((t.numel() + 2 * GUARD,), float("nan"))
+            host[GUARD: GUARD + t.numel()] = t.reshape(-1)
+            self.region, first = (slice(GUARD, GUARD + t.numel()),), GUARD
+        else:
+            B, H, W, Cc = t.shape
+            self.ld = Cc + pad
+            host = torch.full((B * H + 2, W, self.ld), float("nan"))
+            host[1:-1, :, :Cc] = t.reshape(B * H, W, Cc)
+            self.region, first = (slice(1, -1), slice(None), slice(0, Cc)), W * self.ld
+        self.dev = dev(host)
+        self.ptr = self.dev.data_ptr() + 4 * first
+        assert self.ptr % 16 == 0
+
+    def host(self):
+        return self.dev.cpu()
+
+    def tensor(self, buf=None):
+        return (self.host() if buf is None else buf)[self.region].reshape(self.shape)
+
+
+def nan_like(shape, pad=None):
+    return Guarded(torch.full(shape, float("nan")), pad)
+
+
 def nhwc(t):           # NCHW cpu -> NHWC gpu
     return _settle(t.permute(0, 2, 3, 1).contiguous().to(DEV))
 

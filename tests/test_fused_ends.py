@@ -162,7 +162,8 @@ def _chain_desc(ctx, case, widths, keep):
 @pytest.mark.parametrize("with_r1", [True, False])
 @pytest.mark.parametrize("widths", [[64, 64, 4], [48, 48, 4]])
 def test_chain_tail_prologue_matches_float64_and_the_two_launches(ctx, widths, with_r1):
-    """B = 3, HW = 96: three 32-pixel tiles per sample, waves cross sample boundaries (the M | A | D stash is reloaded); inputs in +-2.  References:
+    """B = 3, HW = 96: three 32-pixel tiles per sample, nine in all: on any part with two or more CUs every wave holds at most one tile, so each stashes M | A | D once (a wave
+    that crosses a sample boundary and reloads the stash: tests/test_pointwise_float64.py, the chain's second trip); inputs in +-2.  References:
     fc2(gelu(fc1(silu(affine(t)) + r0 + r1))) in float64, and nd_affine_silu_add_f32 followed by the split chain on the same inputs."""
     import hiputil as hu
     B, HW, Cc = 3, 96, widths[0]
