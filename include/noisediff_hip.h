@@ -839,7 +839,9 @@ int nd_rmsnorm_backward_f32(const float* dy, int lddy, const float* x, int ldx, 
  * for all parameters of a group in ONE launch -- PyTorch's foreach form makes ~10 passes over the parameters.  `items_dev`: n_items records
  * in DEVICE memory, one per parameter: p, m (exp_avg), v (exp_avg_sq) are updated in place from g; step_size = lr / (1 - beta1^t) and
  * bias2_sqrt = sqrt(1 - beta2^t) with the parameter's own step count t (after the increment), computed by the caller in double precision;
- * vec4 != 0 promises that the four tensors are 16-byte aligned.  `chunks_dev`: n_chunks pairs (item index, chunk index) of int32 in device
+ * vec4 != 0 promises that the four tensors are 16-byte aligned (with vec4 == 0 every chunk, whole ones included, takes the scalar path).
+ * beta1, beta2 are the DOUBLES the caller gave the optimizer: the kernels use (float)(1.0 - beta1), (float)(1.0 - beta2) and (float)beta2 --
+ * the complements taken in double and rounded once, as torch.optim.Adam does; the capturable forms take pow of the doubles.  `chunks_dev`: n_chunks pairs (item index, chunk index) of int32 in device
  * memory, one per nd_adam_chunk_elements() elements of a parameter (the last chunk of a parameter may be short).  noisediff_amd.train.Adam
  * is the host side (a torch.optim.Adam subclass with the same state dict). */
 typedef struct nd_adam_item {
@@ -853,17 +855,17 @@ typedef struct nd_adam_item {
     float*       step;        /* capturable form only: the parameter's step counter (one float in device memory) */
 } nd_adam_item;
 int nd_adam_chunk_elements(void);
-int nd_adam_step_f32(const nd_adam_item* items_dev, int n_items, const int32_t* chunks_dev, int n_chunks, float beta1, float beta2, float eps,
+int nd_adam_step_f32(const nd_adam_item* items_dev, int n_items, const int32_t* chunks_dev, int n_chunks, double beta1, double beta2, float eps,
                      float weight_decay, void* stream);
 /* The same with nothing computed on the host (a training step captured as one graph): item.step points at the parameter's step counter in device
  * memory (a float, as torch.optim.Adam(capturable=True) keeps it); the call adds one to every counter and derives step_size / bias2_sqrt from it
  * (item.step_size, item.bias2_sqrt are ignored).  Two launches. */
-int nd_adam_step_capturable_f32(const nd_adam_item* items_dev, int n_items, const int32_t* chunks_dev, int n_chunks, float lr, float beta1, float beta2,
+int nd_adam_step_capturable_f32(const nd_adam_item* items_dev, int n_items, const int32_t* chunks_dev, int n_chunks, float lr, double beta1, double beta2,
                                 float eps, float weight_decay, void* stream);
 /* The capturable form with the learning rate read from device memory: lr = (double)*lr_dev, one float (PyTorch's tensor lr, which schedulers fill in
  * place), read in the kernel -- a captured step follows a changed rate without a new capture.  A null lr_dev is ND_E_BADARG. */
-int nd_adam_step_capturable_lr_f32(const nd_adam_item* items_dev, int n_items, const int32_t* chunks_dev, int n_chunks, const float* lr_dev, float beta1,
-                                   float beta2, float eps, float weight_decay, void* stream);
+int nd_adam_step_capturable_lr_f32(const nd_adam_item* items_dev, int n_items, const int32_t* chunks_dev, int n_chunks, const float* lr_dev, double beta1,
+                                   double beta2, float eps, float weight_decay, void* stream);
 
 /* ------------------------------------------------------------------ shadow-model (EMA) update of a training run (ema.hip)
  * ema_pytorch's EMA.update, the reference's self.ema.update (models/trainer_diffusion.py:63-69,191), for all tensors in one pass, decided on the

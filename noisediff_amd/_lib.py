@@ -177,9 +177,9 @@ SIGNATURES = {
     "nd_conv7x7_c4_wgrad_workspace_floats": (i64, [i32, i32, i32, i32]),
     "nd_conv7x7_c4_wgrad_f32": (i32, [vp, vp, i32, vp, vp, vp, i32, i32, i32, i32, vp]),
     "nd_adam_chunk_elements": (i32, []),
-    "nd_adam_step_f32": (i32, [vp, i32, vp, i32, f32, f32, f32, f32, vp]),
-    "nd_adam_step_capturable_f32": (i32, [vp, i32, vp, i32, f32, f32, f32, f32, f32, vp]),
-    "nd_adam_step_capturable_lr_f32": (i32, [vp, i32, vp, i32, vp, f32, f32, f32, f32, vp]),
+    "nd_adam_step_f32": (i32, [vp, i32, vp, i32, f64, f64, f32, f32, vp]),
+    "nd_adam_step_capturable_f32": (i32, [vp, i32, vp, i32, f32, f64, f64, f32, f32, vp]),
+    "nd_adam_step_capturable_lr_f32": (i32, [vp, i32, vp, i32, vp, f64, f64, f32, f32, vp]),
     "nd_ema_chunk_elements": (i32, []),
     "nd_ema_update_f32": (i32, [vp, i32, vp, i32, vp, vp, vp, f64, i64, i64, f64, f64, f64, vp]),
     "nd_diffusion_noising_f32": (i32, [C.POINTER(DiffusionNoising), vp]),

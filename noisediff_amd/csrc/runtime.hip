@@ -38,7 +38,7 @@ int nd_device_cus() {
     return cus;
 }
 
-extern "C" int nd_version(void) { return 1000 * 0 + 2; }
+extern "C" int nd_version(void) { return 1000 * 0 + 3; }
 extern "C" const char* nd_last_error(void) { return g_err; }
 
 // The question the callers ask instead of restating a kernel's limits: that kernel's shape function, silent (conv3x3_desc.h)

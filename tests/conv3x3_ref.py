@@ -203,6 +203,40 @@ def references(case, pro, kind, c0=0, ranges=None, shape=None):
     return _references(case, pro, c0, str(kind), tuple(ranges) if ranges else None, shape)
 
 
+# ---------------------------------------------------------------------------------------------------------------- F(4x4) packed weights
+
+def wino4_U(g, dtype):
+    """U = G g G^T of an OIHW operator ``g`` [cout][cin][3][3] in ``dtype`` -> [cout][cin][6][6].  float64: G's rationals 1/4, +-1/6, 1/24, +-1/12, 1 as float64
+    literals (exact to 2^-53); fp32: G rounded to fp32, G g first, then G^T -- ref32_winograd's order."""
+    G = torch.tensor(WINO[4][1], dtype=dtype)
+    return torch.einsum("ocip,jp->ocij", torch.einsum("ip,ocpq->ociq", G, g.to(dtype)), G)
+
+
+def _wino4_blocks(cin, cout):
+    return 2 * cdiv(cdiv(cin, 8), 2), 4 * cdiv(cout, 64)              # whole 16-channel chunks of cin, whole 64-channel tiles of cout in groups of 16
+
+
+def wino4_pack_layout(U, cin, cout):
+    """``U`` [cout][cin][6][6] -> the flat buffer nd_pack_conv3x3_wino4_weight documents: blocks [cin / 8][coutP / 16][18 position pairs][64 lanes][4], lane
+    (cout = l & 15, k = l >> 4) holding {U[2pp][ch 2k], U[2pp][ch 2k + 1], U[2pp + 1][ch 2k], U[2pp + 1][ch 2k + 1]} of its block, position = 6 xi + nu;
+    padded channels zero."""
+    n_c8, n_cg = _wino4_blocks(cin, cout)
+    full = U.new_zeros(n_cg * 16, n_c8 * 8, 36)
+    full[:cout, :cin] = U.reshape(cout, cin, 36)
+    # [cg][col][c8][k][c][pp][ph] -> [c8][cg][pp][k][col][ph][c]
+    return full.reshape(n_cg, 16, n_c8, 4, 2, 18, 2).permute(2, 0, 5, 3, 1, 6, 4).reshape(-1).contiguous()
+
+
+def wino4_unpack(packed, cin, cout):
+    """The inverse of ``wino4_pack_layout``: (U [cout][cin][6][6], the entries of the padded channels as one flat tensor)."""
+    n_c8, n_cg = _wino4_blocks(cin, cout)
+    assert packed.numel() == n_c8 * n_cg * 18 * 256
+    full = packed.reshape(n_c8, n_cg, 18, 4, 16, 2, 2).permute(1, 4, 0, 3, 6, 2, 5).reshape(n_cg * 16, n_c8 * 8, 36)
+    real = torch.zeros(n_cg * 16, n_c8 * 8, dtype=torch.bool)
+    real[:cout, :cin] = True
+    return full[:cout, :cin].reshape(cout, cin, 6, 6).contiguous(), full[~real].reshape(-1).contiguous()
+
+
 # ---------------------------------------------------------------------------------------------------------------- statistics
 
 def _tiles(out, th, tw):

@@ -169,3 +169,35 @@ def test_statistics_mutations_are_rejected(case, per_slot, pivoted):
     m = st.clone()                                                    # one channel's sum of one slot taken over one pixel less
     m[0, 0, 0, 0] -= r32[0, 0, 0, 0]
     rejected(check_st, m, sc, r64, r32, per_slot, pivot)
+
+
+# ---------------------------------------------------------------------------------------------------------------- F(4x4) packed weights
+
+@pytest.mark.parametrize("cin,cout", [(24, 8), (72, 40), (64, 64)])
+def test_the_wino4_layout_helpers_invert_each_other_and_follow_the_header(cin, cout):
+    """wino4_unpack(wino4_pack_layout(U)) gives U back with zero padding, and the encode puts every entry where the header's index formula says:
+    float 4 l + e of position pair pp of block (c8, cg) holds U[position 2 pp + (e >> 1)] of (cout 16 cg + (l & 15), channel 8 c8 + 2 (l >> 4) + (e & 1))."""
+    U = torch.rand(cout, cin, 6, 6, generator=torch.Generator().manual_seed(cin + cout)) + 0.5          # (no zero: padding is told from data)
+    packed = R.wino4_pack_layout(U, cin, cout)
+    back, pad = R.wino4_unpack(packed, cin, cout)
+    assert torch.equal(back, U) and not pad.any()
+    assert pad.numel() + U.numel() == packed.numel() == 2 * R.cdiv(R.cdiv(cin, 8), 2) * 4 * R.cdiv(cout, 64) * 18 * 256
+    n_cg = 4 * R.cdiv(cout, 64)
+    for i in torch.randint(0, packed.numel(), (2000,), generator=torch.Generator().manual_seed(1)).tolist() + [0, packed.numel() - 1]:
+        e, l, pp, blk = i % 4, (i // 4) % 64, (i // 256) % 18, i // (18 * 256)
+        cg, c8 = blk % n_cg, blk // n_cg
+        co, ch, pos = 16 * cg + (l & 15), 8 * c8 + 2 * (l >> 4) + (e & 1), 2 * pp + (e >> 1)
+        want = float(U[co, ch, pos // 6, pos % 6]) if co < cout and ch < cin else 0.0
+        assert float(packed[i]) == want, (i, co, ch, pos)
+
+
+def test_wino4_U_in_float64_is_exact_to_rounding():
+    """G g G^T with float64 G against the same product in exact rational arithmetic on one filter."""
+    from fractions import Fraction as Fr
+    G = [[Fr(1, 4), 0, 0], [Fr(-1, 6), Fr(-1, 6), Fr(-1, 6)], [Fr(-1, 6), Fr(1, 6), Fr(-1, 6)], [Fr(1, 24), Fr(1, 12), Fr(1, 6)], [Fr(1, 24), Fr(-1, 12), Fr(1, 6)], [0, 0, 1]]
+    g = torch.rand(1, 1, 3, 3, generator=torch.Generator().manual_seed(2)) - 0.5
+    U = R.wino4_U(g, torch.float64)[0, 0]
+    for xi in range(6):
+        for nu in range(6):
+            exact = sum(G[xi][r] * Fr(float(g[0, 0, r, s])) * G[nu][s] for r in range(3) for s in range(3))
+            assert abs(Fr(float(U[xi, nu])) - exact) <= Fr(1, 2 ** 50) * max(abs(exact), Fr(1, 100))
