@@ -192,21 +192,27 @@ int nd_conv3x3_wino4_16_splitk_nhwc_f32(const nd_conv3x3* d, float* workspace, i
  * Exact-fp32 MFMA; the split over pixel tiles depends on the shape only and the partial sums are added in a fixed order, so the
  * result is bitwise repeatable.  `workspace`: nd_conv3x3_wgrad_workspace_floats(...) floats.  `dbias` (may be NULL): the bias
  * gradient db[co] = sum_{b,y,x} dy[b][y][x][co], from the same dy tiles (same fixed order).
- * Two forms, chosen by the shape alone.  H % 4 == 0, W % 16 == 0 and both channel counts multiples of 32: the Winograd-domain F(4x4,3x3)
+ * Two forms, chosen by the shape alone.  H % 4 == 0, W % 16 == 0, both channel counts multiples of 16, fewer than 2^30 pixels and each tensor below
+ * 1 GiB per sample: the Winograd-domain F(4x4,3x3)
  * form -- per 4 x 4 pixel tile the 6 x 6 transforms of the input patch and of the dY block, 36 position-wise products (a quarter of the
  * nine-tap form's MFMAs), one back-transform G^T M G at the end; error ~4e-6 of max|dW| against a float64 sum.  Anything else: nine tap
  * GEMMs over the pixels (4e-7).  ND_WGRAD_WINO=0 forces the nine-tap form (A/B); nd_conv3x3_wgrad_form pins any of them.
+ * These limits are written once, in csrc/conv3x3_wgrad.hip; callers ask nd_conv3x3_wgrad_plan / nd_conv3x3_wgrad_cat_takes (no HIP call, nd_last_error untouched).
  * The DATA gradient of the same layer is the forward operator itself: nd_conv3x3_*_nhwc_f32 on weights packed by
  * nd_pack_conv3x3_*_weight_dgrad (taps flipped, channel roles swapped) -- see noisediff_amd/train.py. */
 int64_t nd_conv3x3_wgrad_workspace_floats(int B, int H, int W, int cin, int cout);
 /* Tests and A/B tools: pin the form -- 0 by the shape (default), 1 nine taps, 2 Winograd domain on four waves, 3 on eight waves (cout % 64 == 0;
  * else four); anything else only queries.  Returns the previous setting.  Process-wide; ask for the workspace size AFTER setting it. */
 /* The same for an input that is the virtual concatenation cat((x0, x1), channels) -- the up path's skip connections -- without the concatenated
- * tensor: dw (cout, c0 + c1, 3, 3).  Winograd-domain forms only (H % 4 == 0, W % 16 == 0, c0, c1, cout multiples of 32): ND_E_SHAPE otherwise
- * (concatenate and call nd_conv3x3_wgrad_nhwc_f32).  Workspace: nd_conv3x3_wgrad_workspace_floats(B, H, W, c0 + c1, cout). */
+ * tensor: dw (cout, c0 + c1, 3, 3).  Winograd-domain forms only (the limits above with c0 and c1 multiples of 32, cout of 16; never under pin 1):
+ * ND_E_SHAPE otherwise (one nd_conv3x3_wgrad_nhwc_f32 per source).  nd_conv3x3_wgrad_cat_takes: 1 exactly where this entry does not refuse the shape.
+ * Workspace: nd_conv3x3_wgrad_workspace_floats(B, H, W, c0 + c1, cout). */
 int nd_conv3x3_wgrad_cat_nhwc_f32(const float* x0, int ldx0, int c0, const float* x1, int ldx1, int c1, const float* dy, int ldy, float* dw_oihw,
                                   float* dbias, float* workspace, int B, int H, int W, int cout, void* stream);
+int nd_conv3x3_wgrad_cat_takes(int B, int H, int W, int c0, int c1, int cout, int ldx0, int ldx1, int ldy);
 int nd_conv3x3_wgrad_form(int form);
+/* The form nd_conv3x3_wgrad_nhwc_f32 runs on dense tensors of this shape under the current pin: 1, 2 or 3 as nd_conv3x3_wgrad_form numbers them. */
+int nd_conv3x3_wgrad_plan(int B, int H, int W, int cin, int cout);
 int nd_conv3x3_wgrad_nhwc_f32(const float* x, int ldx, const float* dy, int ldy, float* dw_oihw, float* dbias, float* workspace,
                               int B, int H, int W, int cin, int cout, void* stream);
 /* LSID training (models/archs/SID_arch.py:105-175; noisediff_amd/lsid_train.py): the same weight gradients for an input that is LeakyReLU(0.2) of the
@@ -233,7 +239,10 @@ int nd_leaky_grad_join_f32(const float* z, float* dz, const float* d_direct, int
  * square root, affine weight and bias -- torch.nn.functional.group_norm's definition.  Forward: y = (x - mean) rstd gamma + beta and
  * `mean_rstd` [B][groups][2] for the backward.  Backward: dx, dgamma [C], dbeta [C] from dy, x and the saved statistics.
  * Every pass streams NHWC once (partial sums per pixel slot, fp64 finalize, one elementwise pass); fixed summation order.
- * `workspace`: nd_groupnorm_train_workspace_floats(B, HW, C) floats, shared by both directions. */
+ * `workspace`: nd_groupnorm_train_workspace_floats(B, HW, C) floats, shared by both directions.
+ * nd_groupnorm_train_takes(C, groups): 1 / 0, the channel counts these entries and the nd_groupnorm_silu_train_* ones take (C a multiple of 4 and of groups,
+ * <= 1024, at most 512 per group) -- the only statement of that limit, like nd_conv3x3_takes. */
+int nd_groupnorm_train_takes(int C, int groups);
 int64_t nd_groupnorm_train_workspace_floats(int B, int HW, int C);
 int nd_groupnorm_train_forward_f32(const float* x, int ldx, const float* gamma, const float* beta, float* y, int ldy, float* mean_rstd,
                                    float* workspace, int B, int HW, int C, int groups, float eps, void* stream);
@@ -263,15 +272,18 @@ int nd_modulate_silu_backward_f32(const float* dy, int lddy, const float* n, int
                                   int64_t N, int C, void* stream);
 
 /* out[b][c] = sum over the HW tokens of x[b][p][c]: the gradient of a per-sample vector broadcast over the tokens -- AttnBlock's one-token ISO
- * cross attention adds to_out(to_v(ctx)) to every token (Diffusion_arch.py:435-437).  Fixed order; workspace: nd_token_sum_workspace_floats. */
+ * cross attention adds to_out(to_v(ctx)) to every token (Diffusion_arch.py:435-437).  Fixed order; workspace: nd_token_sum_workspace_floats.
+ * nd_token_sum_takes(C): 1 / 0, the widths it takes (a multiple of 4 up to 1024). */
+int nd_token_sum_takes(int C);
 int64_t nd_token_sum_workspace_floats(int B, int HW, int C);
 int nd_token_sum_f32(const float* x, int ldx, float* out, float* workspace, int B, int HW, int C, void* stream);
 
 /* nn.LayerNorm(C) over the channels of NHWC tokens for training (AttnBlock.norm1 / norm2, Diffusion_arch.py:427-428): forward
  * y = (x - mean) rstd gamma + beta with `stats` [N][2] = {mean, rstd} per token saved for the backward; backward dx, dgamma [C],
- * dbeta [C].  C = 64, 128 or a multiple of 256 up to 1024 (a row lives in 16 / 32 / 64 lanes); eps inside the square root, biased
+ * dbeta [C].  C a multiple of 4 in 16 .. 1024 (a row lives in 16 / 32 / 64 lanes; nd_layernorm_train_takes(C) answers 1 / 0); eps inside the square root, biased
  * variance -- torch.nn.functional.layer_norm's definition.  One streaming pass per direction, fixed summation order.
  * `workspace` (backward): nd_layernorm_train_workspace_floats(N, C) floats. */
+int nd_layernorm_train_takes(int C);
 int64_t nd_layernorm_train_workspace_floats(int64_t N, int C);
 int nd_layernorm_train_forward_f32(const float* x, int ldx, const float* gamma, const float* beta, float* y, int ldy, float* stats,
                                    int64_t N, int C, float eps, void* stream);
@@ -572,8 +584,12 @@ int nd_pack_pointwise_weights_batch(const nd_pack_item* items_dev, int n_items, 
  * the same reference layers as nd_pointwise_gemm_nhwc_f32 where they are wide: FeedForward's Linears and AttnBlock.proj_out at C >= 128
  * (Diffusion_arch.py:405-443), res_conv of the up path (:156), Attention.to_qkv / to_out (:252-253).  `weight`: nd_pack_pointwise_weight_split
  * ((cout, cin) row-major -> [cin/16][term 3][cout/32][64 lanes][8 bf16]).  Takes: cin % 32 == 0, cin >= 64, cout % 128 == 0, plain pixel
- * addressing, LayerNorm with src.rowstats, a concat on a 32-channel boundary (nd_pointwise_gemm_split_takes); anything else: ND_E_SHAPE. */
+ * addressing, LayerNorm with src.rowstats, a concat on a 32-channel boundary; anything else: ND_E_SHAPE.
+ * The questions, like nd_conv3x3_takes (1 / 0, no HIP call, nd_last_error untouched; the only statement of the limits, csrc/pointwise.hip): does
+ * nd_pointwise_gemm_nhwc_f32 / nd_pointwise_gemm_split_nhwc_f32 take a layer of this shape?  They read the descriptor's sizes, widths, strides and modes and,
+ * of its pointers, only whether src.rowstats is given; the split question includes the fp32 one. */
 int nd_pointwise_gemm_split_nhwc_f32(const nd_pointwise* d, void* stream);
+int nd_pointwise_gemm_takes(const nd_pointwise* d);
 int nd_pointwise_gemm_split_takes(const nd_pointwise* d);
 int64_t nd_pack_pointwise_weight_split_floats(int cin, int cout);
 int nd_pack_pointwise_weight_split(const float* w, float* packed, int cin, int cout, void* stream);
@@ -624,6 +640,7 @@ typedef struct nd_chain {
 } nd_chain;
 int nd_pointwise_chain_nhwc_f32(const nd_chain* d, void* stream);
 int nd_pointwise_chain_supported(int cin, int n1, int n2, int n3);   /* n3 = 0: two stages */
+int nd_pointwise_chain_takes(int HW, int cin, int n1, int n2, int n3);   /* the same and HW a positive multiple of 32: what both chain entries take */
 int64_t nd_pack_chain_weight_floats(int cin, int cout, int first_stage);
 int nd_pack_chain_weight(const float* w, float* packed, int cin, int cout, int first_stage, void* stream);
 /* The same chains (same descriptor, widths, prologues, residuals, errors) with the products on the bf16 matrix cores at full fp32 significand
@@ -829,7 +846,8 @@ int nd_linear_attention_backward_f32(const float* qkv, int ld_qkv, const float* 
 /* Backward of RMSNorm (Diffusion_arch.py:84-90; forward nd_rmsnorm_nhwc_f32 / nd_rmsnorm_add_nhwc_f32), the norm recomputed from x:
  * dx [B][HW][C] and dg [C] (per-workgroup partials, then fp64 in a fixed order).  Where |x| < 1e-12 the clamp makes the norm a constant and
  * dx = g dy sqrt(C) / 1e-12, as autograd of F.normalize gives it (no 0/0).  The residual of the _add form receives dy itself: no kernel.
- * C % 4 == 0, C <= 1024.  `workspace`: nd_rmsnorm_backward_workspace_floats(B * HW, C) floats. */
+ * C % 4 == 0, C <= 1024 (nd_rmsnorm_train_takes(C): 1 / 0).  `workspace`: nd_rmsnorm_backward_workspace_floats(B * HW, C) floats. */
+int nd_rmsnorm_train_takes(int C);
 int64_t nd_rmsnorm_backward_workspace_floats(int64_t npix, int C);
 int nd_rmsnorm_backward_f32(const float* dy, int lddy, const float* x, int ldx, const float* g, float* dx, int lddx, float* dg, float* workspace,
                             int B, int HW, int C, void* stream);

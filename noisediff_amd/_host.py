@@ -63,6 +63,57 @@ def conv3x3_takes(kernel: int, B: int, H: int, W: int, cin: int, cout: int, c0: 
 
 
 @functools.lru_cache(maxsize=None)
+def conv3x3_trains(cin: int, cout: int) -> bool:
+    """Can a 3x3 layer of these widths train on the library?  Its forward and its data gradient (the same operator, widths swapped) at least on the direct kernel."""
+    return conv3x3_takes(L.CONV3X3_DIRECT, 1, 1, 1, cin, cout, cin, 0, cin, 0) and conv3x3_takes(L.CONV3X3_DIRECT, 1, 1, 1, cout, cin, cout, 0, cout, 0)
+
+
+# The other kernel families' questions: like conv3x3_takes the library's own answer, the only place a limit is written (host code: the built library, no GPU).
+# Cached, since a training step asks several hundred times.
+@functools.lru_cache(maxsize=None)
+def _asks(question: str, *dims: int) -> int:
+    return int(getattr(L.load(), question)(*dims))
+
+
+def group_norm_takes(C_: int, groups: int) -> bool:
+    """nd_groupnorm(_silu)_train_*_f32."""
+    return bool(_asks("nd_groupnorm_train_takes", C_, groups))
+
+
+def layer_norm_takes(C_: int) -> bool:
+    """nd_layernorm_train_*_f32."""
+    return bool(_asks("nd_layernorm_train_takes", C_))
+
+
+def rms_norm_takes(C_: int) -> bool:
+    """nd_rmsnorm_backward_f32 (the forward kernels take any multiple of 4)."""
+    return bool(_asks("nd_rmsnorm_train_takes", C_))
+
+
+def token_sum_takes(C_: int) -> bool:
+    return bool(_asks("nd_token_sum_takes", C_))
+
+
+def chain_takes(HW: int, cin: int, n1: int, n2: int, n3: int = 0) -> bool:
+    """nd_pointwise_chain(_split)_nhwc_f32: the instantiated widths over whole pixel tiles."""
+    return bool(_asks("nd_pointwise_chain_takes", HW, cin, n1, n2, n3))
+
+
+def conv3x3_wgrad_cat_takes(B: int, H: int, W: int, c0: int, c1: int, cout: int) -> bool:
+    """nd_conv3x3_wgrad_cat_nhwc_f32 on dense tensors.  Not cached: the answer follows the pin of nd_conv3x3_wgrad_form."""
+    return bool(L.load().nd_conv3x3_wgrad_cat_takes(B, H, W, c0, c1, cout, c0, c1, cout))
+
+
+@functools.lru_cache(maxsize=None)
+def pointwise_takes(cin: int, cout: int, c1: int = 0, split: bool = False) -> bool:
+    """Does nd_pointwise_gemm_nhwc_f32 (``split``: nd_pointwise_gemm_split_nhwc_f32) take a plain dense 1x1 / Linear layer of these widths, the last ``c1`` input
+    channels from a second source?  One pixel: no limit of either entry depends on the pixel count."""
+    d = L.Pointwise(B=1, HW=1, W=1, cin=cin, cout=cout, ldo=cout)
+    d.src.c0, d.src.c1, d.src.ld0, d.src.ld1 = cin - c1, c1, cin - c1, c1
+    return bool((L.load().nd_pointwise_gemm_split_takes if split else L.load().nd_pointwise_gemm_takes)(C.byref(d)))
+
+
+@functools.lru_cache(maxsize=None)
 def conv3x3_kind(B: int, H: int, W: int, cin: int, cout: int, c0: int, c1: int, ld: int, wino4: bool = True) -> str:
     """The kernel of a 3x3 convolution outside the sampling engine: 'wino4', 'wino2', 'wino' (F(2x2,3x3) past wino2's limits) or 'direct'.
     ``c0`` / ``c1``: the channels of the two sources (c1 = 0: one source); ``ld``: the pixel stride the source-size limits are computed with;

@@ -159,6 +159,14 @@ SIGNATURES = {
     "nd_pack_chain_weight_split": (i32, [vp, vp, i32, i32, i32, vp]),
     "nd_pointwise_gemm_split_nhwc_f32": (i32, [C.POINTER(Pointwise), vp]),
     "nd_pointwise_gemm_split_takes": (i32, [C.POINTER(Pointwise)]),
+    "nd_pointwise_gemm_takes": (i32, [C.POINTER(Pointwise)]),
+    "nd_pointwise_chain_takes": (i32, [i32, i32, i32, i32, i32]),
+    "nd_groupnorm_train_takes": (i32, [i32, i32]),
+    "nd_layernorm_train_takes": (i32, [i32]),
+    "nd_rmsnorm_train_takes": (i32, [i32]),
+    "nd_token_sum_takes": (i32, [i32]),
+    "nd_conv3x3_wgrad_plan": (i32, [i32, i32, i32, i32, i32]),
+    "nd_conv3x3_wgrad_cat_takes": (i32, [i32, i32, i32, i32, i32, i32, i32, i32, i32]),
     "nd_pack_pointwise_weight_split_floats": (i64, [i32, i32]),
     "nd_pack_pointwise_weight_split": (i32, [vp, vp, i32, i32, vp]),
     "nd_pointwise_chain_tail_split_nhwc_f32": (i32, [C.POINTER(ChainTail), vp]),
@@ -281,7 +289,9 @@ SIGNATURES = {
     "nd_raw_diffusion_batch_f32": (i32, [vp, i32, i32, i32, vp, f32, f32, vp, vp, vp, vp, i32, i32, i32, vp]),
 }
 
-_UNCHECKED = {"nd_conv3x3_takes", "nd_pointwise_chain_tail_takes", "nd_pointwise_narrow_fold_takes", "nd_pack_narrow_fold_floats", "nd_version", "nd_last_error", "nd_stream_device", "nd_conv3x3_wgrad_form", "nd_adam_chunk_elements", "nd_ema_chunk_elements", "nd_conv7x7_c4_wgrad_workspace_floats", "nd_conv3x3_stat_slots", "nd_conv3x3_tiling_id", "nd_pack_conv3x3_weight_floats",
+_UNCHECKED = {"nd_conv3x3_takes", "nd_pointwise_gemm_takes", "nd_pointwise_gemm_split_takes", "nd_pointwise_chain_supported", "nd_pointwise_chain_takes",
+              "nd_groupnorm_train_takes", "nd_layernorm_train_takes", "nd_rmsnorm_train_takes", "nd_token_sum_takes", "nd_conv3x3_wgrad_plan", "nd_conv3x3_wgrad_cat_takes",
+              "nd_pointwise_chain_tail_takes", "nd_pointwise_narrow_fold_takes", "nd_pack_narrow_fold_floats", "nd_version", "nd_last_error", "nd_stream_device", "nd_conv3x3_wgrad_form", "nd_adam_chunk_elements", "nd_ema_chunk_elements", "nd_conv7x7_c4_wgrad_workspace_floats", "nd_conv3x3_stat_slots", "nd_conv3x3_tiling_id", "nd_pack_conv3x3_weight_floats",
               "nd_pack_pointwise_weight_floats", "nd_linear_attention_workspace_floats", "nd_conv3x3_wino_stat_slots", "nd_conv3x3_wino4_stat_slots",
               "nd_pack_conv3x3_wino_weight_floats", "nd_pack_conv3x3_wino4_weight_floats", "nd_conv3x3_wino4_splitk_plan", "nd_conv3x3_wino4_16_splitk_plan", "nd_conv3x3_wino4_splitk_workspace_floats", "nd_token_sum_workspace_floats", "nd_cond_step_lds_bytes", "nd_conv3x3_wgrad_workspace_floats",
               "nd_groupnorm_train_workspace_floats", "nd_linear_wgrad_workspace_floats",

@@ -518,11 +518,14 @@ extern "C" int nd_linear_attention_backward_f32(const float* qkv, int ld_qkv, co
 
 extern "C" int64_t nd_rmsnorm_backward_workspace_floats(int64_t npix, int C) { return npix > 0 && C > 0 ? (int64_t)RMS_WGS * C : -1; }
 
+// What the RMSNorm backward takes: a row's quads over 64 lanes, at most RMS_MAXQ per lane.
+extern "C" int nd_rmsnorm_train_takes(int C) { return C > 0 && C % 4 == 0 && C <= 256 * RMS_MAXQ; }
+
 extern "C" int nd_rmsnorm_backward_f32(const float* dy, int lddy, const float* x, int ldx, const float* g, float* dx, int lddx, float* dg, float* workspace,
                                        int B, int HW, int C, void* stream) {
     ND_REQUIRE(dy && x && g && dx && dg && workspace, ND_E_BADARG, "nd_rmsnorm_backward: null pointer");
     ND_REQUIRE(B > 0 && HW > 0, ND_E_BADARG, "nd_rmsnorm_backward: non-positive size");
-    ND_REQUIRE(C > 0 && C % 4 == 0 && C <= 1024, ND_E_SHAPE, "nd_rmsnorm_backward: C=%d (a multiple of 4 up to 1024)", C);
+    ND_REQUIRE(nd_rmsnorm_train_takes(C), ND_E_SHAPE, "nd_rmsnorm_backward: C=%d (a multiple of 4 up to 1024)", C);
     ND_REQUIRE(lddy >= C && ldx >= C && lddx >= C && lddy % 4 == 0 && ldx % 4 == 0 && lddx % 4 == 0, ND_E_SHAPE,
                "nd_rmsnorm_backward: strides must be multiples of 4 floats >= C");
     ND_REQUIRE(nd_aligned16(dy) && nd_aligned16(x) && nd_aligned16(g) && nd_aligned16(dx), ND_E_ALIGN, "nd_rmsnorm_backward: alignment");

@@ -9,8 +9,6 @@
 constexpr int ND_W4_CHUNK = 16;          // F(4x4): channels per K chunk
 constexpr int ND_W4_MAX_COUT = 2048;     // F(4x4): the whole bias vector (padded to cout tiles) lives in LDS
 
-#define ND_DESC_REQUIRE(cond, code, fmt, ...) do { if (!(cond)) { if (who) nd_set_error("%s: " fmt, who, ##__VA_ARGS__); return (code); } } while (0)
-
 // ---------------------------------------------------------------- common to the four entries
 static inline int nd_conv3x3_common_shape(const nd_conv3x3* d, const char* who) {
     const nd_src& s = d->src;

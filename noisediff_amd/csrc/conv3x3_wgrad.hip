@@ -1007,6 +1007,12 @@ bool ww_takes(int B, int H, int W, int cin, int cout) {
     return ww_form() != 1 && H % WW_GH == 0 && W % WW_GW == 0 && cin % 16 == 0 && cout % 16 == 0 && (long)B * H * W < (1L << 30);      // (blocks of 32 channels, the last one may be half empty)
 }
 
+// ... and runs it: 32-bit offsets within a sample of every tensor (pixel strides ldx, ldx1 -- 0: one source --, ldy)
+bool ww_runs(int B, int H, int W, int cin, int cout, int ldx, int ldx1, int ldy) {
+    const long px = (long)H * W, lim = 1L << 30;
+    return ww_takes(B, H, W, cin, cout) && px * ldx * 4 < lim && px * ldx1 * 4 < lim && px * ldy * 4 < lim;
+}
+
 void ww_plan(int B, int H, int W, int cin, int cout, WwArgs& a) {
     a.B = B; a.H = H; a.W = W; a.cin = cin; a.cout = cout;
     // the eight-wave form ((64 couts x 32 cins) blocks): 20 % fewer cycles per tile group and block, but twice the accumulators per CU -- twice the
@@ -1054,15 +1060,31 @@ extern "C" int64_t nd_conv3x3_wgrad_workspace_floats(int B, int H, int W, int ci
 
 // lk0 / lk1: LeakyReLU(0.2) on the input of source 0 / 1 as it is staged (the nd_conv3x3_wgrad_*leaky* entries).  dw_cin / dw_ci0 (nine taps only): dw has
 // dw_cin input channels and this gradient fills dw_ci0 .. dw_ci0 + cin - 1 (0, 0: dw is (cout, cin, 3, 3)).
+// The shape part of the entries (no pointer read; `who` == nullptr: a question, nd_last_error untouched)
+static int wgrad_shape(int B, int H, int W, int cin, int cout, int c0, int ldx, int ldy, const char* who) {
+    ND_DESC_REQUIRE(B > 0 && H > 0 && W > 0 && cin > 0 && cout > 0, ND_E_BADARG, "non-positive size");
+    ND_DESC_REQUIRE(cin % 4 == 0 && cout % 4 == 0 && ldx >= c0 && ldy >= cout && ldx % 4 == 0 && ldy % 4 == 0, ND_E_SHAPE,
+                    "cin=%d, cout=%d and the pixel strides must be multiples of 4", cin, cout);
+    return 0;
+}
+
+// nd_conv3x3_wgrad_cat_nhwc_f32: one Winograd-domain gradient over both sources or none (a cin block of 32 never straddles them)
+static int wgrad_cat_shape(int B, int H, int W, int c0, int c1, int cout, int ldx0, int ldx1, int ldy, const char* who) {
+    ND_DESC_REQUIRE(c0 > 0 && c1 > 0 && c0 % 32 == 0 && c1 % 32 == 0 && ldx0 >= c0 && ldx1 >= c1 && ldx1 % 4 == 0, ND_E_SHAPE,
+                    "two sources of whole 32-channel blocks (c0=%d, c1=%d)", c0, c1);
+    if (int e = wgrad_shape(B, H, W, c0 + c1, cout, c0, ldx0, ldy, who ? "nd_conv3x3_wgrad" : nullptr)) return e;
+    ND_DESC_REQUIRE(ww_runs(B, H, W, c0 + c1, cout, ldx0, ldx1, ldy), ND_E_SHAPE,
+                    "two sources need the Winograd-domain form (H %% 4 == 0, W %% 16 == 0, channel counts %% 32 == 0, cout %% 16 == 0, tensors below 1 GiB per sample)");
+    return 0;
+}
+
 template <bool LK>
 static int wgrad_run_t(const float* x, int ldx, int c0, const float* x1, int ldx1, const float* dy, int ldy, float* dw_oihw, float* dbias, float* workspace,
                        int B, int H, int W, int cin, int cout, void* stream, int lk0, int lk1, int dw_cin, int dw_ci0) {
     ND_REQUIRE(x && dy && dw_oihw && workspace, ND_E_BADARG, "nd_conv3x3_wgrad: null pointer");
-    ND_REQUIRE(B > 0 && H > 0 && W > 0 && cin > 0 && cout > 0, ND_E_BADARG, "nd_conv3x3_wgrad: non-positive size");
-    ND_REQUIRE(cin % 4 == 0 && cout % 4 == 0 && ldx >= c0 && ldy >= cout && ldx % 4 == 0 && ldy % 4 == 0, ND_E_SHAPE,
-               "nd_conv3x3_wgrad: cin=%d, cout=%d and the pixel strides must be multiples of 4", cin, cout);
+    if (int e = wgrad_shape(B, H, W, cin, cout, c0, ldx, ldy, "nd_conv3x3_wgrad")) return e;
     ND_REQUIRE(nd_aligned16(x) && nd_aligned16(dy), ND_E_ALIGN, "nd_conv3x3_wgrad: x and dy must be 16-byte aligned");
-    if (dw_cin == 0 && ww_takes(B, H, W, cin, cout) && (long)H * W * ldx * 4 < (1L << 30) && (long)H * W * ldy * 4 < (1L << 30)) {     // F(4x4) Winograd-domain form (a quarter of the MFMAs); 32-bit offsets within a sample
+    if (dw_cin == 0 && ww_runs(B, H, W, cin, cout, ldx, x1 ? ldx1 : 0, ldy)) {     // F(4x4) Winograd-domain form (a quarter of the MFMAs); 32-bit offsets within a sample
         WwArgs w;
         ww_plan(B, H, W, cin, cout, w);
         w.x = x; w.dy = dy; w.ws = workspace; w.ldx = ldx; w.ldy = ldy;
@@ -1093,7 +1115,7 @@ static int wgrad_run_t(const float* x, int ldx, int c0, const float* x1, int ldx
         hipLaunchKernelGGL(wgrad_wino_reduce_kernel, dim3((unsigned)((total + 255) / 256 < 4096 ? (total + 255) / 256 : 4096)), dim3(256), 0, st, workspace, w.wsb, dw_oihw, dbias, cin, cout, w.coP, w.ciP);
         return nd_launch_status("nd_conv3x3_wgrad_nhwc_f32 (Winograd-domain reduce)");
     }
-    ND_REQUIRE(c0 == cin, ND_E_SHAPE, "nd_conv3x3_wgrad_cat_nhwc_f32: two sources need the Winograd-domain form (H %% 4 == 0, W %% 16 == 0, channel counts %% 32 == 0)");
+    ND_REQUIRE(c0 == cin, ND_E_STATE, "nd_conv3x3_wgrad: internal: two sources reached the nine-tap form");
     WgradArgs a;
     plan(B, H, W, cin, cout, a);
     a.x = x; a.dy = dy; a.ws = workspace; a.ldx = ldx; a.ldy = ldy;
@@ -1130,11 +1152,23 @@ extern "C" int nd_conv3x3_wgrad_nhwc_f32(const float* x, int ldx, const float* d
     return wgrad_run(x, ldx, cin, nullptr, 0, dy, ldy, dw_oihw, dbias, workspace, B, H, W, cin, cout, stream);
 }
 
+// The questions (no HIP call, nd_last_error untouched; the answers follow the pin of nd_conv3x3_wgrad_form).  The form nd_conv3x3_wgrad_nhwc_f32 runs on dense
+// tensors: 1 = nine taps, 2 = Winograd domain on four waves, 3 = on eight.  And: would nd_conv3x3_wgrad_cat_nhwc_f32 take these sources (1) or refuse (0)?
+extern "C" int nd_conv3x3_wgrad_plan(int B, int H, int W, int cin, int cout) {
+    if (wgrad_shape(B, H, W, cin, cout, cin, cin, cout, nullptr) || !ww_runs(B, H, W, cin, cout, cin, 0, cout)) return 1;
+    WwArgs w;
+    ww_plan(B, H, W, cin, cout, w);
+    return w.wide ? 3 : 2;
+}
+
+extern "C" int nd_conv3x3_wgrad_cat_takes(int B, int H, int W, int c0, int c1, int cout, int ldx0, int ldx1, int ldy) {
+    return wgrad_cat_shape(B, H, W, c0, c1, cout, ldx0, ldx1, ldy, nullptr) == 0;
+}
+
 extern "C" int nd_conv3x3_wgrad_cat_nhwc_f32(const float* x0, int ldx0, int c0, const float* x1, int ldx1, int c1, const float* dy, int ldy, float* dw_oihw,
                                              float* dbias, float* workspace, int B, int H, int W, int cout, void* stream) {
-    ND_REQUIRE(x0 && x1 && c0 > 0 && c1 > 0 && c0 % 32 == 0 && c1 % 32 == 0 && ldx0 >= c0 && ldx1 >= c1 && ldx1 % 4 == 0 && nd_aligned16(x1), ND_E_SHAPE,
-               "nd_conv3x3_wgrad_cat_nhwc_f32: two sources of whole 32-channel blocks (c0=%d, c1=%d)", c0, c1);
-    ND_REQUIRE((long)H * W * ldx1 * 4 < (1L << 30), ND_E_SHAPE, "nd_conv3x3_wgrad_cat_nhwc_f32: second source too large for 32-bit offsets within a sample");
+    ND_REQUIRE(x0 && x1 && nd_aligned16(x1), ND_E_SHAPE, "nd_conv3x3_wgrad_cat_nhwc_f32: two sources, the second 16-byte aligned");
+    if (int e = wgrad_cat_shape(B, H, W, c0, c1, cout, ldx0, ldx1, ldy, "nd_conv3x3_wgrad_cat_nhwc_f32")) return e;
     return wgrad_run(x0, ldx0, c0, x1, ldx1, dy, ldy, dw_oihw, dbias, workspace, B, H, W, c0 + c1, cout, stream);
 }
 
@@ -1151,8 +1185,7 @@ extern "C" int nd_conv3x3_wgrad_cat_leaky_second_nhwc_f32(const float* x0, int l
     ND_REQUIRE(x0 && x1 && c0 > 0 && c1 > 0 && c0 % 4 == 0 && c1 % 4 == 0 && ldx0 >= c0 && ldx1 >= c1 && ldx1 % 4 == 0 && nd_aligned16(x1), ND_E_SHAPE,
                "nd_conv3x3_wgrad_cat_leaky_second_nhwc_f32: c0=%d, c1=%d must be multiples of 4", c0, c1);
     const int cin = c0 + c1;
-    if (c0 % 32 == 0 && c1 % 32 == 0 && ww_takes(B, H, W, cin, cout) && (long)H * W * ldx0 * 4 < (1L << 30) && (long)H * W * ldx1 * 4 < (1L << 30) &&
-        (long)H * W * ldy * 4 < (1L << 30))                             // one Winograd-domain gradient over both sources (a cin block never straddles them)
+    if (wgrad_cat_shape(B, H, W, c0, c1, cout, ldx0, ldx1, ldy, nullptr) == 0)             // one Winograd-domain gradient over both sources
         return wgrad_run_t<true>(x0, ldx0, c0, x1, ldx1, dy, ldy, dw_oihw, dbias, workspace, B, H, W, cin, cout, stream, 0, 1, 0, 0);
     // nine taps: one gradient per source into its columns of dw; the bias gradient with the first
     if (int e = wgrad_run_t<false>(x0, ldx0, c0, nullptr, 0, dy, ldy, dw_oihw, dbias, workspace, B, H, W, c0, cout, stream, 0, 0, cin, 0)) return e;

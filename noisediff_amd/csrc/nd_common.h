@@ -24,6 +24,9 @@ void nd_set_error(const char* fmt, ...);
         }                                      \
     } while (0)
 
+// The same inside a shape function that takes `who`: an entry passes its name (refusal: message + code), a question nullptr (the code alone, nd_last_error untouched).
+#define ND_DESC_REQUIRE(cond, code, fmt, ...) do { if (!(cond)) { if (who) nd_set_error("%s: " fmt, who, ##__VA_ARGS__); return (code); } } while (0)
+
 static inline int nd_launch_status(const char* what) {
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) {

@@ -199,11 +199,20 @@ __global__ __launch_bounds__(256) void affine3_kernel(const float* __restrict__ 
 
 }  // namespace
 
+// What the GroupNorm training kernels take (all four entries; nd_groupnorm_train_takes asks silently): a group's channels of one pixel sit in one 256-lane
+// pass of float4s, a sample's coefficients in LDS.
+static int gn_train_shape(int B, int HW, int C, int groups, const char* who) {
+    ND_DESC_REQUIRE(B > 0 && HW > 0 && C > 0 && groups > 0 && C % groups == 0 && C % 4 == 0 && C <= 1024 && C / groups <= 512, ND_E_SHAPE,
+                    "C=%d groups=%d (C a multiple of 4 and of groups, <= 1024, at most 512 per group)", C, groups);
+    return 0;
+}
+
+extern "C" int nd_groupnorm_train_takes(int C, int groups) { return gn_train_shape(1, 1, C, groups, nullptr) == 0; }
+
 extern "C" int nd_groupnorm_train_forward_f32(const float* x, int ldx, const float* gamma, const float* beta, float* y, int ldy, float* mean_rstd,
                                               float* workspace, int B, int HW, int C, int groups, float eps, void* stream) {
     ND_REQUIRE(x && gamma && beta && y && mean_rstd && workspace, ND_E_BADARG, "nd_groupnorm_train_forward: null pointer");
-    ND_REQUIRE(B > 0 && HW > 0 && C > 0 && groups > 0 && C % groups == 0 && C % 4 == 0 && C <= 1024 && C / groups <= 512, ND_E_SHAPE,
-               "nd_groupnorm_train_forward: C=%d groups=%d (C a multiple of 4 and of groups, <= 1024)", C, groups);
+    if (int e = gn_train_shape(B, HW, C, groups, "nd_groupnorm_train_forward")) return e;
     ND_REQUIRE(ldx >= C && ldy >= C && ldx % 4 == 0 && ldy % 4 == 0 && nd_aligned16(x) && nd_aligned16(y) && nd_aligned16(workspace), ND_E_ALIGN,
                "nd_groupnorm_train_forward: strides must be multiples of 4 floats >= C, pointers 16-byte aligned");
     const int slots = gt_slots(HW);
@@ -227,8 +236,7 @@ extern "C" int nd_groupnorm_train_backward_f32(const float* dy, int lddy, const 
                                                float* dx, int lddx, float* dgamma, float* dbeta, float* workspace, int B, int HW, int C, int groups,
                                                void* stream) {
     ND_REQUIRE(dy && x && gamma && mean_rstd && dx && dgamma && dbeta && workspace, ND_E_BADARG, "nd_groupnorm_train_backward: null pointer");
-    ND_REQUIRE(B > 0 && HW > 0 && C > 0 && groups > 0 && C % groups == 0 && C % 4 == 0 && C <= 1024 && C / groups <= 512, ND_E_SHAPE,
-               "nd_groupnorm_train_backward: C=%d groups=%d (C a multiple of 4 and of groups, <= 1024)", C, groups);
+    if (int e = gn_train_shape(B, HW, C, groups, "nd_groupnorm_train_backward")) return e;
     ND_REQUIRE(lddy >= C && ldx >= C && lddx >= C && lddy % 4 == 0 && ldx % 4 == 0 && lddx % 4 == 0 && nd_aligned16(dy) && nd_aligned16(x) &&
                nd_aligned16(dx) && nd_aligned16(workspace), ND_E_ALIGN,
                "nd_groupnorm_train_backward: strides must be multiples of 4 floats >= C, pointers 16-byte aligned");
@@ -395,16 +403,18 @@ __global__ __launch_bounds__(256) void ln_dparam_kernel(const float* __restrict_
 constexpr int LT_BWD_WGS = 1024;                                         // fixed: the summation order must not depend on the device
 
 inline int lt_group(int C) { return C > 128 ? 64 : C > 64 ? 32 : 16; }             // lanes per row: 16, 32 or 64 (C / 4 quads over them, up to LT_MAXQ rounds)
-inline bool lt_ok(int C) { return C % 4 == 0 && C >= 16 && C <= 1024; }
 
 }  // namespace
+
+// What the LayerNorm training kernels take (both entries ask it): a row of float4s over 16, 32 or 64 lanes, at most LT_MAXQ rounds, no lane of the 16 idle.
+extern "C" int nd_layernorm_train_takes(int C) { return C % 4 == 0 && C >= 16 && C <= 256 * LT_MAXQ; }
 
 extern "C" int64_t nd_layernorm_train_workspace_floats(int64_t N, int C) { return N > 0 && C > 0 ? (int64_t)LT_BWD_WGS * C * 2 : -1; }
 
 extern "C" int nd_layernorm_train_forward_f32(const float* x, int ldx, const float* gamma, const float* beta, float* y, int ldy, float* stats,
                                               int64_t N, int C, float eps, void* stream) {
     ND_REQUIRE(x && gamma && beta && y && stats, ND_E_BADARG, "nd_layernorm_train_forward: null pointer");
-    ND_REQUIRE(N > 0 && lt_ok(C), ND_E_SHAPE, "nd_layernorm_train_forward: C=%d (a multiple of 4 in 16 .. 1024)", C);
+    ND_REQUIRE(N > 0 && nd_layernorm_train_takes(C), ND_E_SHAPE, "nd_layernorm_train_forward: C=%d (a multiple of 4 in 16 .. 1024)", C);
     ND_REQUIRE(ldx >= C && ldy >= C && ldx % 4 == 0 && ldy % 4 == 0 && nd_aligned16(x) && nd_aligned16(y) && nd_aligned16(gamma) && nd_aligned16(beta),
                ND_E_ALIGN, "nd_layernorm_train_forward: strides must be multiples of 4 floats >= C, pointers 16-byte aligned");
     const int G = lt_group(C), rows_per_pass = 4 * (64 / G);
@@ -420,7 +430,7 @@ extern "C" int nd_layernorm_train_forward_f32(const float* x, int ldx, const flo
 extern "C" int nd_layernorm_train_backward_f32(const float* dy, int lddy, const float* x, int ldx, const float* gamma, const float* stats,
                                                float* dx, int lddx, float* dgamma, float* dbeta, float* workspace, int64_t N, int C, void* stream) {
     ND_REQUIRE(dy && x && gamma && stats && dx && dgamma && dbeta && workspace, ND_E_BADARG, "nd_layernorm_train_backward: null pointer");
-    ND_REQUIRE(N > 0 && lt_ok(C), ND_E_SHAPE, "nd_layernorm_train_backward: C=%d (a multiple of 4 in 16 .. 1024)", C);
+    ND_REQUIRE(N > 0 && nd_layernorm_train_takes(C), ND_E_SHAPE, "nd_layernorm_train_backward: C=%d (a multiple of 4 in 16 .. 1024)", C);
     ND_REQUIRE(lddy >= C && ldx >= C && lddx >= C && lddy % 4 == 0 && ldx % 4 == 0 && lddx % 4 == 0 && nd_aligned16(dy) && nd_aligned16(x) &&
                nd_aligned16(dx) && nd_aligned16(gamma) && nd_aligned16(workspace), ND_E_ALIGN,
                "nd_layernorm_train_backward: strides must be multiples of 4 floats >= C, pointers 16-byte aligned");
@@ -581,12 +591,6 @@ __global__ __launch_bounds__(256) void gs_apply_kernel(const float* __restrict__
     }
 }
 
-int gs_check(const char* who, int B, int HW, int C, int groups) {
-    ND_REQUIRE(B > 0 && HW > 0 && C > 0 && groups > 0 && C % groups == 0 && C % 4 == 0 && C <= 1024 && C / groups <= 512, ND_E_SHAPE,
-               "%s: C=%d groups=%d (C a multiple of 4 and of groups, <= 1024)", who, C, groups);
-    return 0;
-}
-
 }  // namespace
 
 extern "C" int64_t nd_groupnorm_silu_train_workspace_floats(int B, int HW, int C) {
@@ -598,7 +602,7 @@ extern "C" int nd_groupnorm_silu_train_forward_f32(const float* x, int ldx, cons
                                                    float* y, int ldy, float* mean_rstd, float* mad, float* workspace, int B, int HW, int C, int groups, float eps,
                                                    void* stream) {
     ND_REQUIRE(x && gamma && beta && y && mean_rstd && mad && workspace, ND_E_BADARG, "nd_groupnorm_silu_train_forward: null pointer");
-    if (int e = gs_check("nd_groupnorm_silu_train_forward", B, HW, C, groups)) return e;
+    if (int e = gn_train_shape(B, HW, C, groups, "nd_groupnorm_silu_train_forward")) return e;
     ND_REQUIRE(ldx >= C && ldy >= C && ldx % 4 == 0 && ldy % 4 == 0 && nd_aligned16(x) && nd_aligned16(y) && nd_aligned16(workspace) && nd_aligned16(mad),
                ND_E_ALIGN, "nd_groupnorm_silu_train_forward: strides must be multiples of 4 floats >= C, pointers 16-byte aligned");
     ND_REQUIRE(!res || (ldr >= C && ldr % 4 == 0 && nd_aligned16(res)), ND_E_ALIGN, "nd_groupnorm_silu_train_forward: the residual's stride / alignment");
@@ -619,7 +623,7 @@ extern "C" int nd_groupnorm_silu_train_backward_f32(const float* dy, int lddy, c
                                                     void* stream) {
     ND_REQUIRE(dy && x && gamma && beta && mean_rstd && mad && dx && dgamma && dbeta && workspace, ND_E_BADARG, "nd_groupnorm_silu_train_backward: null pointer");
     ND_REQUIRE((scale_shift == nullptr) == (dscale_shift == nullptr), ND_E_BADARG, "nd_groupnorm_silu_train_backward: scale_shift and dscale_shift go together");
-    if (int e = gs_check("nd_groupnorm_silu_train_backward", B, HW, C, groups)) return e;
+    if (int e = gn_train_shape(B, HW, C, groups, "nd_groupnorm_silu_train_backward")) return e;
     ND_REQUIRE(lddy >= C && ldx >= C && lddx >= C && lddy % 4 == 0 && ldx % 4 == 0 && lddx % 4 == 0 && nd_aligned16(dy) && nd_aligned16(x) &&
                nd_aligned16(dx) && nd_aligned16(workspace) && nd_aligned16(mad), ND_E_ALIGN,
                "nd_groupnorm_silu_train_backward: strides must be multiples of 4 floats >= C, pointers 16-byte aligned");
@@ -717,9 +721,12 @@ extern "C" int64_t nd_token_sum_workspace_floats(int B, int HW, int C) {
     return (int64_t)B * gt_slots(HW) * C * 2;
 }
 
+// (the partial sums of gn_partials_kernel: a pixel's channels in one 256-lane pass of float4s)
+extern "C" int nd_token_sum_takes(int C) { return C > 0 && C % 4 == 0 && C <= 1024; }
+
 extern "C" int nd_token_sum_f32(const float* x, int ldx, float* out, float* workspace, int B, int HW, int C, void* stream) {
     ND_REQUIRE(x && out && workspace, ND_E_BADARG, "nd_token_sum: null pointer");
-    ND_REQUIRE(B > 0 && HW > 0 && C > 0 && C % 4 == 0 && C <= 1024 && ldx >= C && ldx % 4 == 0, ND_E_SHAPE, "nd_token_sum: C=%d (multiple of 4, <= 1024), stride", C);
+    ND_REQUIRE(B > 0 && HW > 0 && nd_token_sum_takes(C) && ldx >= C && ldx % 4 == 0, ND_E_SHAPE, "nd_token_sum: C=%d (multiple of 4, <= 1024), stride", C);
     ND_REQUIRE(nd_aligned16(x) && nd_aligned16(workspace), ND_E_ALIGN, "nd_token_sum: x and the workspace must be 16-byte aligned");
     const int slots = gt_slots(HW);
     hipStream_t st = (hipStream_t)stream;

@@ -1192,11 +1192,65 @@ extern "C" int nd_pack_pointwise_weights_batch(const nd_pack_item* items_dev, in
 }
 
 namespace {
+// What the 1x1 entries take, in two parts as in conv3x3_desc.h.  The SHAPE part reads no address: sizes, widths, strides, modes, and -- for the LayerNorm
+// prologue alone -- WHETHER src.rowstats is given (it names the kernel's variant, like a mode).  It is the only place these limits are written: an entry runs
+// it with its name, nd_pointwise_gemm_takes / nd_pointwise_gemm_split_takes with `who` == nullptr.  The POINTER part (null, alignment, p1 with c1, gamma / beta /
+// mad present, the strides of residual operands that are present) stays with the entry.
+int pw_shape(const nd_pointwise* d, const char* who) {
+    const nd_src& s = d->src;
+    ND_DESC_REQUIRE(d->B > 0 && d->HW > 0 && d->cin > 0 && d->cout > 0, ND_E_BADARG, "non-positive size");
+    ND_DESC_REQUIRE(d->cin % 4 == 0, ND_E_SHAPE, "cin=%d must be a multiple of 4", d->cin);
+    ND_DESC_REQUIRE(s.c0 + s.c1 == d->cin && s.c0 % 4 == 0 && s.c1 % 4 == 0 && s.c0 > 0, ND_E_SHAPE, "source channels %d+%d do not match cin=%d", s.c0, s.c1, d->cin);
+    ND_DESC_REQUIRE(s.ld0 % 4 == 0 && (s.c1 == 0 || s.ld1 % 4 == 0), ND_E_ALIGN, "pixel strides must be multiples of 4");
+    ND_DESC_REQUIRE(!s.upsample, ND_E_BADARG, "upsample is a conv3x3-only addressing mode");
+    if (s.unshuffle) {
+        ND_DESC_REQUIRE(s.c1 == 0 && d->W > 0 && d->HW % d->W == 0 && (s.c0 / 4) % 4 == 0 && s.mode == ND_PRO_NONE, ND_E_SHAPE,
+                        "unshuffle needs one source, W | HW, c0/4 %% 4 == 0, no prologue");
+        ND_DESC_REQUIRE(s.ld0 >= s.c0 / 4, ND_E_SHAPE, "ld0 < source channels");
+    } else {
+        ND_DESC_REQUIRE(s.ld0 >= s.c0 && (s.c1 == 0 || s.ld1 >= s.c1), ND_E_SHAPE, "ld < channels");
+    }
+    ND_DESC_REQUIRE(s.mode == ND_PRO_NONE || s.mode == ND_PRO_LAYERNORM || s.mode == ND_PRO_SILU || s.mode == ND_PRO_AFFINE_SILU || s.mode == ND_PRO_LEAKY, ND_E_BADARG,
+                    "unsupported prologue %d", s.mode);
+    ND_DESC_REQUIRE(d->shuffle_c <= 0 || (d->cout == 4 * d->shuffle_c && d->shuffle_c % 4 == 0 && d->W > 0 && d->HW % d->W == 0 && d->shuffle_h > 0 && d->shuffle_w > 0 &&
+                    d->ldo >= d->shuffle_c), ND_E_SHAPE, "shuffle_c=%d needs cout == 4*shuffle_c, W | HW, an output size and no residual operands", d->shuffle_c);
+    if (s.mode == ND_PRO_LAYERNORM) {
+        ND_DESC_REQUIRE(s.c1 == 0 && d->cin <= 1024, ND_E_SHAPE, "LayerNorm needs gamma/beta, one source, C <= 1024");
+        ND_DESC_REQUIRE(d->cin <= 64 || s.rowstats, ND_E_BADARG, "LayerNorm over C=%d > 64 needs src.rowstats (nd_layernorm_stats_f32)", d->cin);
+    }
+    ND_DESC_REQUIRE(s.mode != ND_PRO_AFFINE_SILU || s.c1 == 0, ND_E_BADARG, "affine prologue needs mad, one source");
+    ND_DESC_REQUIRE(d->ldo >= d->cout || d->shuffle_c > 0, ND_E_SHAPE, "ldo < cout");
+    ND_DESC_REQUIRE(d->ldo % 4 == 0, ND_E_ALIGN, "output / residual pixel strides must be multiples of 4");
+    ND_DESC_REQUIRE(d->act >= ND_ACT_NONE && d->act <= ND_ACT_SILU, ND_E_BADARG, "bad act");
+    return 0;
+}
+
+int pw_ptrs(const nd_pointwise* d, const char* who) {
+    const nd_src& s = d->src;
+    ND_DESC_REQUIRE(s.p0 && d->weight && d->out, ND_E_BADARG, "null tensor pointer");
+    ND_DESC_REQUIRE((s.c1 == 0) == (s.p1 == nullptr), ND_E_BADARG, "p1/c1 mismatch");
+    ND_DESC_REQUIRE(nd_aligned16(s.p0) && nd_aligned16(s.p1) && nd_aligned16(d->weight) && nd_aligned16(s.vec) && nd_aligned16(s.gamma) && nd_aligned16(s.beta) &&
+                    nd_aligned16(s.mad), ND_E_ALIGN, "pointers must be 16-byte aligned");
+    ND_DESC_REQUIRE(d->shuffle_c <= 0 || (!d->res0 && !d->res1 && !d->gn_t && !d->vec), ND_E_SHAPE,
+                    "shuffle_c=%d needs cout == 4*shuffle_c, W | HW, an output size and no residual operands", d->shuffle_c);
+    ND_DESC_REQUIRE(s.mode != ND_PRO_LAYERNORM || (s.gamma && s.beta), ND_E_SHAPE, "LayerNorm needs gamma/beta, one source, C <= 1024");
+    ND_DESC_REQUIRE(s.mode != ND_PRO_AFFINE_SILU || s.mad, ND_E_BADARG, "affine prologue needs mad, one source");
+    ND_DESC_REQUIRE((!d->res0 || d->ldr0 % 4 == 0) && (!d->res1 || d->ldr1 % 4 == 0) && (!d->gn_t || d->ldt % 4 == 0), ND_E_ALIGN,
+                    "output / residual pixel strides must be multiples of 4");
+    ND_DESC_REQUIRE(nd_aligned16(d->out) && nd_aligned16(d->res0) && nd_aligned16(d->res1) && nd_aligned16(d->gn_t) && nd_aligned16(d->bias) && nd_aligned16(d->vec) &&
+                    nd_aligned16(d->gn_mad), ND_E_ALIGN, "epilogue pointers must be 16-byte aligned");
+    ND_DESC_REQUIRE(!d->res0 || d->ldr0 >= d->cout, ND_E_SHAPE, "ldr0 < cout");
+    ND_DESC_REQUIRE(!d->res1 || d->ldr1 >= d->cout, ND_E_SHAPE, "ldr1 < cout");
+    ND_DESC_REQUIRE(!d->gn_t || (d->gn_mad && d->ldt >= d->cout), ND_E_BADARG, "gn_t needs gn_mad and ldt >= cout");
+    return 0;
+}
+
+// The kernel rules below run behind pw_shape and pw_ptrs: they restate neither (a second source is there and aligned wherever c1 > 0).
 bool pw_pipe_takes(const nd_pointwise* d) {
     // software-pipelined kernel: whole 32-channel chunks, LayerNorm statistics from the pre-pass, plain addressing
     static const bool use_pipe = !(getenv("ND_PW_PIPE") && atoi(getenv("ND_PW_PIPE")) == 0);   // A/B knob (tools/ only)
     const nd_src& s = d->src;
-    return use_pipe && d->cin % PKC == 0 && d->cin >= 2 * PKC && !s.unshuffle && (s.mode != ND_PRO_LAYERNORM || s.rowstats) && (s.c1 == 0 || nd_aligned16(s.p1));
+    return use_pipe && d->cin % PKC == 0 && d->cin >= 2 * PKC && !s.unshuffle && (s.mode != ND_PRO_LAYERNORM || s.rowstats);
 }
 // large tiles, one wave per SIMD: wide layers with enough 128-pixel tiles to fill the chip
 long pw_big_tiles(const nd_pointwise* d) {                                  // 0: another kernel takes the layer
@@ -1208,53 +1262,21 @@ long pw_big_tiles(const nd_pointwise* d) {                                  // 0
     return tiles >= nd_device_cus() ? tiles : 0;
 }
 
-// layers the SPLIT kernel takes: whole 32-channel chunks (at least two), 128-cout tiles, plain addressing, LayerNorm statistics from the pre-pass
-bool pw_split_takes(const nd_pointwise* d) {
+// the SPLIT kernel's own conditions: whole 32-channel chunks (at least two), 128-cout tiles, plain addressing, LayerNorm statistics from the pre-pass
+int pw_split_shape(const nd_pointwise* d, const char* who) {
     const nd_src& s = d->src;
-    return d->cin % SKC == 0 && d->cin >= 2 * SKC && d->cout % 128 == 0 && !s.unshuffle && d->shuffle_c == 0 && (s.mode != ND_PRO_LAYERNORM || s.rowstats) &&
-           (s.c1 == 0 || (s.c0 % SKC == 0 && nd_aligned16(s.p1)));
+    if (int e = pw_shape(d, who ? "nd_pointwise" : nullptr)) return e;
+    ND_DESC_REQUIRE(d->cin % SKC == 0 && d->cin >= 2 * SKC && d->cout % 128 == 0 && !s.unshuffle && d->shuffle_c == 0 && (s.mode != ND_PRO_LAYERNORM || s.rowstats) &&
+                    (s.c1 == 0 || s.c0 % SKC == 0), ND_E_SHAPE, "%d -> %d is not a layer of the split kernel (cin %% 32, cin >= 64, cout %% 128, plain "
+                    "addressing, LayerNorm with rowstats, concat on a 32-channel boundary: nd_pointwise_gemm_split_takes)", d->cin, d->cout);
+    return 0;
 }
 
 int pw_run(const nd_pointwise* d, void* stream, bool split = false, int uns_h = 0, int uns_w = 0) {
     ND_REQUIRE(d, ND_E_BADARG, "nd_pointwise: null descriptor");
     const nd_src& s = d->src;
-    ND_REQUIRE(s.p0 && d->weight && d->out, ND_E_BADARG, "nd_pointwise: null tensor pointer");
-    ND_REQUIRE(d->B > 0 && d->HW > 0 && d->cin > 0 && d->cout > 0, ND_E_BADARG, "nd_pointwise: non-positive size");
-    ND_REQUIRE(d->cin % 4 == 0, ND_E_SHAPE, "nd_pointwise: cin=%d must be a multiple of 4", d->cin);
-    ND_REQUIRE(s.c0 + s.c1 == d->cin && s.c0 % 4 == 0 && s.c1 % 4 == 0 && s.c0 > 0, ND_E_SHAPE,
-               "nd_pointwise: source channels %d+%d do not match cin=%d", s.c0, s.c1, d->cin);
-    ND_REQUIRE((s.c1 == 0) == (s.p1 == nullptr), ND_E_BADARG, "nd_pointwise: p1/c1 mismatch");
-    ND_REQUIRE(s.ld0 % 4 == 0 && (s.c1 == 0 || s.ld1 % 4 == 0), ND_E_ALIGN, "nd_pointwise: pixel strides must be multiples of 4");
-    ND_REQUIRE(nd_aligned16(s.p0) && nd_aligned16(s.p1) && nd_aligned16(d->weight) && nd_aligned16(s.vec) &&
-               nd_aligned16(s.gamma) && nd_aligned16(s.beta) && nd_aligned16(s.mad), ND_E_ALIGN, "nd_pointwise: pointers must be 16-byte aligned");
-    ND_REQUIRE(!s.upsample, ND_E_BADARG, "nd_pointwise: upsample is a conv3x3-only addressing mode");
-    if (s.unshuffle) {
-        ND_REQUIRE(s.c1 == 0 && d->W > 0 && d->HW % d->W == 0 && (s.c0 / 4) % 4 == 0 && s.mode == ND_PRO_NONE, ND_E_SHAPE,
-                   "nd_pointwise: unshuffle needs one source, W | HW, c0/4 %% 4 == 0, no prologue");
-        ND_REQUIRE(s.ld0 >= s.c0 / 4, ND_E_SHAPE, "nd_pointwise: ld0 < source channels");
-    } else {
-        ND_REQUIRE(s.ld0 >= s.c0 && (s.c1 == 0 || s.ld1 >= s.c1), ND_E_SHAPE, "nd_pointwise: ld < channels");
-    }
-    ND_REQUIRE(s.mode == ND_PRO_NONE || s.mode == ND_PRO_LAYERNORM || s.mode == ND_PRO_SILU || s.mode == ND_PRO_AFFINE_SILU ||
-               s.mode == ND_PRO_LEAKY, ND_E_BADARG, "nd_pointwise: unsupported prologue %d", s.mode);
-    if (d->shuffle_c > 0)
-        ND_REQUIRE(d->cout == 4 * d->shuffle_c && d->shuffle_c % 4 == 0 && d->W > 0 && d->HW % d->W == 0 && d->shuffle_h > 0 && d->shuffle_w > 0 &&
-                   d->ldo >= d->shuffle_c && !d->res0 && !d->res1 && !d->gn_t && !d->vec, ND_E_SHAPE,
-                   "nd_pointwise: shuffle_c=%d needs cout == 4*shuffle_c, W | HW, an output size and no residual operands", d->shuffle_c);
-    if (s.mode == ND_PRO_LAYERNORM) {
-        ND_REQUIRE(s.gamma && s.beta && s.c1 == 0 && d->cin <= 1024, ND_E_SHAPE, "nd_pointwise: LayerNorm needs gamma/beta, one source, C <= 1024");
-        ND_REQUIRE(d->cin <= 64 || s.rowstats, ND_E_BADARG, "nd_pointwise: LayerNorm over C=%d > 64 needs src.rowstats (nd_layernorm_stats_f32)", d->cin);
-    }
-    if (s.mode == ND_PRO_AFFINE_SILU) ND_REQUIRE(s.mad && s.c1 == 0, ND_E_BADARG, "nd_pointwise: affine prologue needs mad, one source");
-    ND_REQUIRE(d->ldo >= d->cout || d->shuffle_c > 0, ND_E_SHAPE, "nd_pointwise: ldo < cout");
-    ND_REQUIRE(d->ldo % 4 == 0 && (!d->res0 || d->ldr0 % 4 == 0) && (!d->res1 || d->ldr1 % 4 == 0) && (!d->gn_t || d->ldt % 4 == 0),
-               ND_E_ALIGN, "nd_pointwise: output / residual pixel strides must be multiples of 4");
-    ND_REQUIRE(nd_aligned16(d->out) && nd_aligned16(d->res0) && nd_aligned16(d->res1) && nd_aligned16(d->gn_t) && nd_aligned16(d->bias) &&
-               nd_aligned16(d->vec) && nd_aligned16(d->gn_mad), ND_E_ALIGN, "nd_pointwise: epilogue pointers must be 16-byte aligned");
-    ND_REQUIRE(!d->res0 || d->ldr0 >= d->cout, ND_E_SHAPE, "nd_pointwise: ldr0 < cout");
-    ND_REQUIRE(!d->res1 || d->ldr1 >= d->cout, ND_E_SHAPE, "nd_pointwise: ldr1 < cout");
-    ND_REQUIRE(!d->gn_t || (d->gn_mad && d->ldt >= d->cout), ND_E_BADARG, "nd_pointwise: gn_t needs gn_mad and ldt >= cout");
-    ND_REQUIRE(d->act >= ND_ACT_NONE && d->act <= ND_ACT_SILU, ND_E_BADARG, "nd_pointwise: bad act");
+    if (int e = split ? pw_split_shape(d, "nd_pointwise_gemm_split") : pw_shape(d, "nd_pointwise")) return e;
+    if (int e = pw_ptrs(d, "nd_pointwise")) return e;
 
     if (uns_h > 0 || uns_w > 0)
         ND_REQUIRE(s.unshuffle && uns_h > 0 && uns_w > 0 && uns_h <= 2 * (d->HW / d->W) && uns_w <= 2 * d->W, ND_E_SHAPE,
@@ -1263,8 +1285,6 @@ int pw_run(const nd_pointwise* d, void* stream, bool split = false, int uns_h = 
     a.d = *d;
     a.uns_h = uns_h;  a.uns_w = uns_w;
     if (split) {
-        ND_REQUIRE(pw_split_takes(d), ND_E_SHAPE, "nd_pointwise_gemm_split: %d -> %d is not a layer of the split kernel (cin %% 32, cin >= 64, cout %% 128, plain "
-                   "addressing, LayerNorm with rowstats, concat on a 32-channel boundary: nd_pointwise_gemm_split_takes)", d->cin, d->cout);
         a.cinP = d->cin;  a.coutP = d->cout;
         a.m_tiles = nd_cdiv(d->HW, 128);
         a.n_tiles = d->cout / 128;
@@ -1292,8 +1312,7 @@ int pw_run(const nd_pointwise* d, void* stream, bool split = false, int uns_h = 
     hipStream_t st = (hipStream_t)stream;
     // narrow outputs: a streaming dot product instead of an MFMA tile that is 15/16 padding (geometry only; A/B knob ND_PW_NARROW=0, tools/ only)
     static const bool use_narrow = !(getenv("ND_PW_NARROW") && atoi(getenv("ND_PW_NARROW")) == 0);
-    if (use_narrow && d->cout <= 8 && d->cout % 4 == 0 && d->cin <= 1024 && s.mode == ND_PRO_NONE && !s.unshuffle && d->shuffle_c == 0 && !d->gn_t && !d->vec &&
-        (s.c1 == 0 || nd_aligned16(s.p1))) {
+    if (use_narrow && d->cout <= 8 && d->cout % 4 == 0 && d->cin <= 1024 && s.mode == ND_PRO_NONE && !s.unshuffle && d->shuffle_c == 0 && !d->gn_t && !d->vec) {
         const long blocks = ((long)d->B * d->HW + 63) / 64;
         const int grid = (int)(blocks < 8L * nd_device_cus() ? blocks : 8L * nd_device_cus());
         if (d->cout <= 4) hipLaunchKernelGGL((pointwise_narrow_kernel<4>), dim3(grid), dim3(256), 0, st, a);
@@ -1337,7 +1356,9 @@ extern "C" int nd_pointwise_gemm_unshuffle_crop_nhwc_f32(const nd_pointwise* d, 
 // nd_pack_pointwise_weight_split packing.  Same prologues, epilogues and errors; takes the layers nd_pointwise_gemm_split_takes names.
 extern "C" int nd_pointwise_gemm_split_nhwc_f32(const nd_pointwise* d, void* stream) { return pw_run(d, stream, true); }
 
-extern "C" int nd_pointwise_gemm_split_takes(const nd_pointwise* d) { return d && pw_split_takes(d) ? 1 : 0; }
+// The questions (no HIP call, nd_last_error untouched): does the fp32 entry / the split entry take a layer of this shape?
+extern "C" int nd_pointwise_gemm_takes(const nd_pointwise* d) { return d && pw_shape(d, nullptr) == 0; }
+extern "C" int nd_pointwise_gemm_split_takes(const nd_pointwise* d) { return d && pw_split_shape(d, nullptr) == 0; }
 
 // ---- two 1x1 layers with only an addition between them, the second one narrow, as ONE streaming dot product (pointwise_narrow_fold_kernel above)
 extern "C" int nd_pointwise_narrow_fold_takes(int c0, int c1, int c2, int cout) {

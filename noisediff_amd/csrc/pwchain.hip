@@ -477,16 +477,31 @@ extern "C" int nd_pack_chain_weight(const float* w, float* packed, int cin, int 
     return nd_launch_status("nd_pack_chain_weight");
 }
 
-// the (K0, N1, N2, N3) shapes this build instantiates: NoiseDiffNet's Mlp / AttnBlock chains at dim 16, 32, 48, 64
-extern "C" int nd_pointwise_chain_supported(int cin, int n1, int n2, int n3) {
-    const int K0 = nd_round_up(cin, 8), N1 = nd_round_up(n1, 32), N2 = nd_round_up(n2, 32), N3 = n3 > 0 ? nd_round_up(n3, 32) : 0;
-    static const int table[][4] = {{8, 32, 32, 0},  {16, 32, 32, 0}, {16, 32, 32, 32}, {32, 32, 32, 0}, {32, 64, 32, 32},
-                                   {8, 64, 64, 0},  {48, 64, 64, 0}, {48, 96, 64, 64}, {64, 64, 64, 0}, {64, 128, 64, 64},
-                                   {64, 64, 32, 0}, {32, 32, 32, 32}, {48, 64, 32, 0}};
-    for (const auto& e : table)
-        if (e[0] == K0 && e[1] == N1 && e[2] == N2 && e[3] == N3) return 1;
-    return 0;
+// The (K0, N1, N2, N3) shapes this build instantiates, listed once: NoiseDiffNet's Mlp / AttnBlock chains at dim 16, 32, 48, 64.  K0 is the input width in the
+// fp32 kernel's 8-channel K steps; the split kernel takes whole 16-channel steps, so its K0 is the row's rounded up to 16 (chain_k0).
+#define ND_CHAIN_ROWS(X) \
+    X(8, 32, 32, 0)  X(16, 32, 32, 0) X(16, 32, 32, 32) X(32, 32, 32, 0) X(32, 32, 32, 32) X(32, 64, 32, 32) X(8, 64, 64, 0) \
+    X(48, 64, 64, 0) X(48, 96, 64, 64) X(64, 64, 64, 0) X(64, 64, 32, 0) X(48, 64, 32, 0)  X(64, 128, 64, 64)
+
+constexpr int chain_k0(int k0, bool split) { return split ? (k0 + 15) / 16 * 16 : k0; }
+
+// the row of these widths launched (`a` given) or only looked up (`a` == nullptr): 0, or ND_E_SHAPE where no row matches
+template <bool SPLIT>
+static int chain_row(int cin, int n1, int n2, int n3, const ChainArgs* a, hipStream_t st) {
+    const int K0 = nd_round_up(cin, SPLIT ? 16 : 8), N1 = nd_round_up(n1, 32), N2 = nd_round_up(n2, 32), N3 = n3 > 0 ? nd_round_up(n3, 32) : 0;
+#define ND_CHAIN_ROW(k0, r1, r2, r3) \
+    if (K0 == chain_k0(k0, SPLIT) && N1 == r1 && N2 == r2 && N3 == r3) return a ? launch_mode<chain_k0(k0, SPLIT), r1, r2, r3, SPLIT>(*a, st) : 0;
+    ND_CHAIN_ROWS(ND_CHAIN_ROW)
+#undef ND_CHAIN_ROW
+    return ND_E_SHAPE;
 }
+
+static inline bool chain_pixels_ok(int HW) { return HW > 0 && HW % 32 == 0; }          // whole 32-pixel tiles per sample
+
+extern "C" int nd_pointwise_chain_supported(int cin, int n1, int n2, int n3) { return chain_row<false>(cin, n1, n2, n3, nullptr, nullptr) == 0; }
+
+// what both chain entries take of a layer group: the widths above over whole pixel tiles
+extern "C" int nd_pointwise_chain_takes(int HW, int cin, int n1, int n2, int n3) { return chain_pixels_ok(HW) && nd_pointwise_chain_supported(cin, n1, n2, n3); }
 
 extern "C" int64_t nd_pack_chain_weight_split_floats(int cin, int cout, int first_stage) {
     return (int64_t)nd_round_up(cin, first_stage ? 16 : 32) * nd_round_up(cout, 32) * 3 / 2;      // three bf16 terms per value, counted in floats (the arena's unit)
@@ -507,7 +522,7 @@ static int chain_run(const nd_chain* d, void* stream, bool split) {
     const nd_src& s = d->src;
     ND_REQUIRE(d->n_stages == 2 || d->n_stages == 3, ND_E_BADARG, "nd_pointwise_chain: n_stages=%d (2 or 3)", d->n_stages);
     ND_REQUIRE(s.p0 && d->out, ND_E_BADARG, "nd_pointwise_chain: null tensor pointer");
-    ND_REQUIRE(d->B > 0 && d->HW > 0 && d->HW % 32 == 0, ND_E_SHAPE, "nd_pointwise_chain: HW=%d must be a positive multiple of 32", d->HW);
+    ND_REQUIRE(d->B > 0 && chain_pixels_ok(d->HW), ND_E_SHAPE, "nd_pointwise_chain: HW=%d must be a positive multiple of 32", d->HW);
     ND_REQUIRE(s.c0 > 0 && s.c0 % 4 == 0 && s.c1 % 4 == 0 && (s.c1 == 0) == (s.p1 == nullptr), ND_E_SHAPE,
                "nd_pointwise_chain: source channels %d+%d (multiples of 4; p1 iff c1)", s.c0, s.c1);
     const int cin = s.c0 + s.c1;
@@ -538,47 +553,15 @@ static int chain_run(const nd_chain* d, void* stream, bool split) {
     ND_REQUIRE(tiles < (1L << 31), ND_E_SHAPE, "nd_pointwise_chain: too many pixels");
     a.n_tiles = (int)tiles;
     hipStream_t st = (hipStream_t)stream;
-    const int K0 = nd_round_up(cin, split ? 16 : 8), N1 = nd_round_up(d->st[0].cout, 32), N2 = nd_round_up(d->st[1].cout, 32), N3 = n3 ? nd_round_up(n3, 32) : 0;
-    int rc = ND_E_SHAPE;
+    const int n1 = d->st[0].cout, n2 = d->st[1].cout;
     if (split) {          // the same widths with the first stage's channels in whole 16-channel K steps
-        ND_REQUIRE(s.c1 == 0 || K0 == 16, ND_E_SHAPE, "nd_pointwise_chain_split: two sources only with cin <= 16 (got %d + %d)", s.c0, s.c1);
+        ND_REQUIRE(s.c1 == 0 || cin <= 16, ND_E_SHAPE, "nd_pointwise_chain_split: two sources only with cin <= 16 (got %d + %d)", s.c0, s.c1);
         ND_REQUIRE((long)d->B * d->HW * s.ld0 * 4 < (1L << 32) - 65536 && (long)d->B * d->HW * (s.c1 ? s.ld1 : 0) * 4 < (1L << 32) - 65536 &&
                    (long)d->B * d->HW * d->ldo * 4 < (1L << 32) - 65536, ND_E_SHAPE, "nd_pointwise_chain_split: a tensor of 4 GiB or more");
-#define ND_CHAIN_SPLIT_CASE(k0, n1, n2, n3) \
-        if (K0 == k0 && N1 == n1 && N2 == n2 && N3 == n3) rc = launch_mode<k0, n1, n2, n3, true>(a, st);
-        ND_CHAIN_SPLIT_CASE(16, 32, 32, 0)
-        ND_CHAIN_SPLIT_CASE(16, 32, 32, 32)
-        ND_CHAIN_SPLIT_CASE(32, 32, 32, 0)
-        ND_CHAIN_SPLIT_CASE(32, 32, 32, 32)
-        ND_CHAIN_SPLIT_CASE(32, 64, 32, 32)
-        ND_CHAIN_SPLIT_CASE(16, 64, 64, 0)
-        ND_CHAIN_SPLIT_CASE(48, 64, 64, 0)
-        ND_CHAIN_SPLIT_CASE(48, 96, 64, 64)
-        ND_CHAIN_SPLIT_CASE(64, 64, 64, 0)
-        ND_CHAIN_SPLIT_CASE(64, 64, 32, 0)
-        ND_CHAIN_SPLIT_CASE(48, 64, 32, 0)
-        ND_CHAIN_SPLIT_CASE(64, 128, 64, 64)
-#undef ND_CHAIN_SPLIT_CASE
-        if (rc) return rc;
+        if (int rc = chain_row<true>(cin, n1, n2, n3, &a, st)) return rc;
         return nd_launch_status("nd_pointwise_chain_split_nhwc_f32");
     }
-#define ND_CHAIN_CASE(k0, n1, n2, n3) \
-    if (K0 == k0 && N1 == n1 && N2 == n2 && N3 == n3) rc = launch_mode<k0, n1, n2, n3>(a, st);
-    ND_CHAIN_CASE(8, 32, 32, 0)
-    ND_CHAIN_CASE(16, 32, 32, 0)
-    ND_CHAIN_CASE(16, 32, 32, 32)
-    ND_CHAIN_CASE(32, 32, 32, 0)
-    ND_CHAIN_CASE(32, 32, 32, 32)
-    ND_CHAIN_CASE(32, 64, 32, 32)
-    ND_CHAIN_CASE(8, 64, 64, 0)
-    ND_CHAIN_CASE(48, 64, 64, 0)
-    ND_CHAIN_CASE(48, 96, 64, 64)
-    ND_CHAIN_CASE(64, 64, 64, 0)
-    ND_CHAIN_CASE(64, 64, 32, 0)
-    ND_CHAIN_CASE(48, 64, 32, 0)
-    ND_CHAIN_CASE(64, 128, 64, 64)
-#undef ND_CHAIN_CASE
-    if (rc) return rc;
+    if (int rc = chain_row<false>(cin, n1, n2, n3, &a, st)) return rc;
     return nd_launch_status("nd_pointwise_chain_nhwc_f32");
 }
 
@@ -593,7 +576,7 @@ extern "C" int nd_pointwise_chain_tail_split_nhwc_f32(const nd_chain_tail* dt, v
     const nd_chain* d = &dt->chain;
     const nd_src& s = d->src;
     ND_REQUIRE(d->n_stages == 2 && s.p0 && d->out && dt->mad && dt->r0, ND_E_BADARG, "nd_pointwise_chain_tail: two stages, t, mad, r0 and out");
-    ND_REQUIRE(d->B > 0 && d->HW > 0 && d->HW % 32 == 0, ND_E_SHAPE, "nd_pointwise_chain_tail: HW=%d must be a positive multiple of 32", d->HW);
+    ND_REQUIRE(d->B > 0 && chain_pixels_ok(d->HW), ND_E_SHAPE, "nd_pointwise_chain_tail: HW=%d must be a positive multiple of 32", d->HW);
     ND_REQUIRE(s.c1 == 0 && !s.p1 && s.mode == ND_PRO_NONE && !s.vec && !s.upsample && !s.unshuffle && !s.rowstats, ND_E_BADARG,
                "nd_pointwise_chain_tail: one plain source (the affine + SiLU is this entry point's own prologue)");
     const int cin = s.c0;

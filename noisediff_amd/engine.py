@@ -30,7 +30,7 @@ from typing import Callable, Dict, List, Optional, Sequence, Tuple
 import torch
 
 from . import _lib as L
-from ._host import conv3x3_takes
+from ._host import chain_takes, conv3x3_takes, pointwise_takes
 from .spec import (normalize_stage_attn, stage_attention_param_spec, ATTN_DIM_HEAD, ATTN_HEADS, ISO_DIM, ISO_TABLE_ROWS, POS_DIM, POS_GROUPS, RESNET_GROUPS, SHOT_GROUPS,
                    arch_param_spec, arch_traits, attention_param_spec, stage_dims)
 
@@ -81,8 +81,8 @@ def _few_items(H: int, W: int, cout: int) -> bool:
 
 
 def _wino4_layer(cin: int, cout: int) -> bool:
-    """Layers whose weights are also packed for the F(4x4,3x3) kernel: at least two 16-channel K chunks (conv3x3_wino4.hip)."""
-    return cin > 16 and cin % 4 == 0 and cout % 4 == 0
+    """Layers whose weights are also packed for the F(4x4,3x3) kernel: the widths it takes of a plain one-sample layer (at least two 16-channel K chunks)."""
+    return conv3x3_takes(L.CONV3X3_WINO4, 1, 32, 32, cin, cout, cin, 0, cin, 0)
 
 
 def conv3x3_form(B: int, H: int, W: int, cin: int, cout: int, c0: int, c1: int, ld0: int, ld1: int, mode: int, upsample: bool, packed4: bool, *,
@@ -165,8 +165,8 @@ _CHAIN_SPLIT_LIMIT = (1 << 32) - (1 << 17)    # bytes of one tensor a launch of 
 
 
 def _split_layer(cin: int, cout: int) -> bool:
-    """1x1 / Linear layers whose weights are also packed as three bf16 terms for nd_pointwise_gemm_split_nhwc_f32 (pointwise.hip: pw_split_takes)."""
-    return SPLIT_PW and cin % 32 == 0 and cin >= 64 and cout % 128 == 0
+    """1x1 / Linear layers whose weights are also packed as three bf16 terms for nd_pointwise_gemm_split_nhwc_f32: the widths it takes of a plain layer."""
+    return SPLIT_PW and pointwise_takes(cin, cout, split=True)
 
 
 def _classify(name: str, shape: Sequence[int]) -> str:
@@ -800,8 +800,7 @@ class Plan:
         return out
 
     def _chain_ok(self, HW: int, widths) -> bool:
-        w = list(widths) + [0] * (4 - len(widths))
-        return CHAIN and HW % 32 == 0 and bool(self.e.lib.nd_pointwise_chain_supported(*w))
+        return CHAIN and chain_takes(HW, *widths)
 
     def attn_block(self, name: str, x: torch.Tensor, H: int, W: int) -> torch.Tensor:
         """AttnBlock (Diffusion_arch.py:434-443) with the 1-token CrossAttention folded into cb."""

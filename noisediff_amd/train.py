@@ -39,7 +39,8 @@ from torch.autograd.function import once_differentiable
 from torch import nn
 
 from . import _lib as L
-from ._host import CONV3X3_ENTRY, CONV3X3_PACK, _empty, _need_gpu, _on, _stream, _workspace, conv3x3_kind
+from ._host import (CONV3X3_ENTRY, CONV3X3_PACK, _empty, _need_gpu, _on, _stream, _workspace, conv3x3_kind, conv3x3_trains, conv3x3_wgrad_cat_takes, group_norm_takes,
+                    layer_norm_takes, pointwise_takes, rms_norm_takes, token_sum_takes)
 
 
 def _nhwc(t: torch.Tensor) -> torch.Tensor:
@@ -94,7 +95,7 @@ def _conv3x3_nhwc(x: torch.Tensor, w_oihw: torch.Tensor, bias: Optional[torch.Te
     with _on(x.device):
         out = _empty((B, cout, H, W), x.device, memory_format=torch.channels_last)
         kind = conv3x3_kind(B, H, W, cin, cout, c0, cin - c0, cin)       # ld = c0 + c1 for a concat: stricter than the kernel's widest-source bound
-        if x1 is not None and (kind != "wino4" or c0 % 16 or x1.shape[1] % 16):
+        if x1 is not None and (kind != "wino4" or x1.shape[1] % 16):
             raise L.HipError(f"conv3x3 over two sources needs the F(4x4) kernel and sources of whole 16-channel chunks ({c0} + {x1.shape[1]} channels, {H}x{W})")
         kind = "direct" if kind == "wino" else kind                      # past wino2's limits: the direct kernel
         if kind == "direct" and cin % 8:
@@ -206,12 +207,12 @@ def conv3x3_with_stats(x: torch.Tensor, weight: torch.Tensor, bias: Optional[tor
 
 def cat_sources_ok(x0: torch.Tensor, x1: torch.Tensor, cout: Optional[int] = None) -> bool:
     """Can conv3x3_cat / conv1x1_cat take this pair (else the caller concatenates)?  The F(4x4) kernel's geometry and whole 16-channel chunks per source;
-    ``cout`` (when given): a multiple of 8 (within the kernel's bias table: conv3x3_kind's question)."""
+    ``cout`` (when given): one the layer can train with (conv3x3_trains; within the kernel's bias table: conv3x3_kind's question)."""
     B, c0, H, W = x0.shape
     c1 = x1.shape[1]
-    if cout is not None and cout % 8:
+    if cout is not None and not conv3x3_trains(c0 + c1, cout):
         return False
-    return (x0.is_cuda and x1.is_cuda and x0.dim() == 4 and tuple(x1.shape[2:]) == (H, W) and x1.shape[0] == B and c0 % 16 == 0 and c1 % 16 == 0
+    return (x0.is_cuda and x1.is_cuda and x0.dim() == 4 and tuple(x1.shape[2:]) == (H, W) and x1.shape[0] == B and c1 % 16 == 0
             and conv3x3_kind(B, H, W, c0 + c1, cout or 8, c0, c1, c0 + c1) == "wino4")      # ld = c0 + c1 as in _conv3x3_nhwc; no cout: 8
 
 
@@ -232,7 +233,6 @@ class Conv3x3CatFunction(torch.autograd.Function):
         a, b, weight = ctx.saved_tensors
         if grad_out is None:
             return None, None, None, None, None
-        lib = L.load()
         g = _nhwc(grad_out)
         B, c0, H, W = a.shape
         c1, cout = b.shape[1], weight.shape[0]
@@ -241,7 +241,7 @@ class Conv3x3CatFunction(torch.autograd.Function):
             full = _conv3x3_nhwc(g, weight, None, dgrad=True)            # (B, c0 + c1, H, W) channels_last: the slices are views
             gx0, gx1 = (full[:, :c0] if ctx.needs_input_grad[0] else None), (full[:, c0:] if ctx.needs_input_grad[1] else None)
         want_b = ctx.has_bias and ctx.needs_input_grad[3]
-        if ctx.needs_input_grad[2] and H % 4 == 0 and W % 16 == 0 and c0 % 32 == 0 and c1 % 32 == 0 and cout % 16 == 0 and lib.nd_conv3x3_wgrad_form(-1) != 1:
+        if ctx.needs_input_grad[2] and conv3x3_wgrad_cat_takes(B, H, W, c0, c1, cout):
             with _on(a.device):                                          # the Winograd-domain forms read a cin block from either source: ONE weight gradient
                 grad_w = _empty((cout, c0 + c1, 3, 3), a.device)
                 grad_b = _empty(cout, a.device) if want_b else None
@@ -307,8 +307,8 @@ class GroupNormFunction(torch.autograd.Function):
 
 def group_norm(x: torch.Tensor, groups: int, weight: torch.Tensor, bias: torch.Tensor, eps: float = 1e-5) -> torch.Tensor:
     """Differentiable F.group_norm(x, groups, weight, bias, eps) for 4-D inputs on the HIP library."""
-    if x.dim() != 4 or x.shape[1] % groups or x.shape[1] % 4 or x.shape[1] > 1024 or weight is None or bias is None:
-        raise ValueError(f"group_norm: x {tuple(x.shape)}, groups {groups}: needs a 4-D input, C a multiple of 4 and of groups (<= 1024), affine parameters")
+    if x.dim() != 4 or not group_norm_takes(x.shape[1], groups) or weight is None or bias is None:
+        raise ValueError(f"group_norm: x {tuple(x.shape)}, groups {groups}: needs a 4-D input, channels and groups that nd_groupnorm_train_takes, affine parameters")
     return GroupNormFunction.apply(x, weight, bias, groups, eps)
 
 
@@ -366,8 +366,8 @@ def group_norm_silu(x: torch.Tensor, groups: int, weight: torch.Tensor, bias: to
                     eps: float = 1e-5, res: Optional[torch.Tensor] = None, conv_stats=None) -> torch.Tensor:
     """Differentiable silu(F.group_norm(x, groups, weight, bias, eps) * (scale + 1) + shift) (+ res), scale | shift = the halves of ``scale_shift``
     ((B, 2C) or (B, 2C, 1, 1)), on the HIP library; ``res`` (x's shape): the ResnetBlock's shortcut added in the same pass (Diffusion_arch.py:170)."""
-    if x.dim() != 4 or x.shape[1] % groups or x.shape[1] % 4 or x.shape[1] > 1024 or weight is None or bias is None:
-        raise ValueError(f"group_norm_silu: x {tuple(x.shape)}, groups {groups}: needs a 4-D input, C a multiple of 4 and of groups (<= 1024), affine parameters")
+    if x.dim() != 4 or not group_norm_takes(x.shape[1], groups) or weight is None or bias is None:
+        raise ValueError(f"group_norm_silu: x {tuple(x.shape)}, groups {groups}: needs a 4-D input, channels and groups that nd_groupnorm_train_takes, affine parameters")
     if scale_shift is not None and scale_shift.numel() != x.shape[0] * 2 * x.shape[1]:
         raise ValueError(f"group_norm_silu: scale_shift {tuple(scale_shift.shape)} is not (B, 2C) for x {tuple(x.shape)}")
     if res is not None and res.shape != x.shape:
@@ -402,8 +402,8 @@ class BroadcastAddFunction(torch.autograd.Function):
 
 
 def broadcast_add(tokens: torch.Tensor, vec: torch.Tensor) -> torch.Tensor:
-    """tokens (B, N, C) + vec (B, 1, C) with the token sum of the backward on the HIP library (C a multiple of 4, <= 1024; CUDA tensors)."""
-    if tokens.dim() != 3 or vec.shape != (tokens.shape[0], 1, tokens.shape[2]) or tokens.shape[2] % 4 or tokens.shape[2] > 1024 or not tokens.is_cuda:
+    """tokens (B, N, C) + vec (B, 1, C) with the token sum of the backward on the HIP library (a width that nd_token_sum_takes; CUDA tensors)."""
+    if tokens.dim() != 3 or vec.shape != (tokens.shape[0], 1, tokens.shape[2]) or not token_sum_takes(tokens.shape[2]) or not tokens.is_cuda:
         return tokens + vec
     return BroadcastAddFunction.apply(tokens, vec)
 
@@ -444,13 +444,8 @@ def modulate_silu(n: torch.Tensor, scale_shift: torch.Tensor) -> torch.Tensor:
     return ModulateSiLUFunction.apply(n, scale_shift)
 
 
-def _group_norm_ok(channels: int, groups: int) -> bool:
-    """Channel counts the norm_train.hip kernels take (the C side rejects the rest): C % 4 == 0, C <= 1024, C / groups <= 512."""
-    return channels % 4 == 0 and channels % groups == 0 and channels <= 1024 and channels // groups <= 512
-
-
 def _eligible_norm(m: nn.Module) -> bool:
-    return isinstance(m, nn.GroupNorm) and m.affine and _group_norm_ok(m.num_channels, m.num_groups)
+    return isinstance(m, nn.GroupNorm) and m.affine and group_norm_takes(m.num_channels, m.num_groups)
 
 
 def _hip_norm_forward(self: nn.GroupNorm, x: torch.Tensor) -> torch.Tensor:
@@ -669,7 +664,8 @@ def _pointwise_gemm(x2: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tens
 
 
 def _pw_takes(N: int, cin: int, cout: int) -> bool:
-    return _PW_GEMM and cin % 4 == 0 and cout % 4 == 0 and 0 < N < (1 << 31) and N * max(cin, cout) * 4 < (1 << 40)
+    """The GEMM of a Linear on the library's 1x1 kernel: the knob, widths the entry takes, a token count of 32 bits."""
+    return _PW_GEMM and pointwise_takes(cin, cout) and 0 < N < (1 << 31) and N * max(cin, cout) * 4 < (1 << 40)
 
 
 def _linear_wgrad(x2: torch.Tensor, g2: torch.Tensor, want_b: bool):
@@ -758,8 +754,8 @@ class LinearCatFunction(torch.autograd.Function):
 
 def _cat_tokens(op: str, x0: torch.Tensor, x1: torch.Tensor, weight: torch.Tensor):
     """The argument check of the 1x1 convolutions over cat((x0, x1), 1), and the two sources as contiguous NHWC tokens (views when channels_last)."""
-    if x0.dim() != 4 or tuple(weight.shape[2:]) != (1, 1) or x0.shape[1] + x1.shape[1] != weight.shape[1] or x0.shape[1] % 4 or x1.shape[1] % 4 \
-            or weight.shape[0] % 4 or not (x0.is_cuda and x1.is_cuda):
+    if x0.dim() != 4 or tuple(weight.shape[2:]) != (1, 1) or x0.shape[1] + x1.shape[1] != weight.shape[1] \
+            or not pointwise_takes(weight.shape[1], weight.shape[0], x1.shape[1]) or not (x0.is_cuda and x1.is_cuda):
         raise ValueError(f"{op}: x0 {tuple(x0.shape)} + x1 {tuple(x1.shape)} / weight {tuple(weight.shape)}")
     t0, t1 = x0.permute(0, 2, 3, 1), x1.permute(0, 2, 3, 1)
     return (t0 if t0.is_contiguous() else t0.contiguous()), (t1 if t1.is_contiguous() else t1.contiguous())
@@ -767,7 +763,7 @@ def _cat_tokens(op: str, x0: torch.Tensor, x1: torch.Tensor, weight: torch.Tenso
 
 def conv1x1_cat(x0: torch.Tensor, x1: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Differentiable F.conv2d(torch.cat((x0, x1), 1), weight, bias) for 1x1 kernels that never builds the concatenation (channels_last in and out; both
-    channel counts multiples of 4)."""
+    channel counts nd_pointwise_gemm_takes)."""
     t0, t1 = _cat_tokens("conv1x1_cat", x0, x1, weight)
     return LinearCatFunction.apply(t0, t1, weight.flatten(1), bias).permute(0, 3, 1, 2)
 
@@ -828,14 +824,11 @@ def conv1x1_shortcut_cat(x0: torch.Tensor, x1: torch.Tensor, weight: torch.Tenso
     return a0.permute(0, 3, 1, 2), a1.permute(0, 3, 1, 2), r.permute(0, 3, 1, 2)
 
 
-def _linear_ok(cin: int, cout: int) -> bool:
-    return cin % 4 == 0 and cout % 4 == 0
-
-
 def linear(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor] = None, res: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """Differentiable F.linear(x, weight, bias) (+ res, added in the GEMM's epilogue) with the weight / bias gradient on the HIP library (channel counts multiples of 4)."""
-    if weight.dim() != 2 or x.shape[-1] != weight.shape[1] or not _linear_ok(weight.shape[1], weight.shape[0]):
-        raise ValueError(f"linear: x {tuple(x.shape)} / weight {tuple(weight.shape)}: needs a 2-D weight with channel counts that are multiples of 4")
+    """Differentiable F.linear(x, weight, bias) (+ res, added in the GEMM's epilogue) with the weight / bias gradient on the HIP library (widths that nd_pointwise_gemm_takes;
+    nd_linear_wgrad_f32 takes the same)."""
+    if weight.dim() != 2 or x.shape[-1] != weight.shape[1] or not pointwise_takes(weight.shape[1], weight.shape[0]):
+        raise ValueError(f"linear: x {tuple(x.shape)} / weight {tuple(weight.shape)}: needs a 2-D weight with channel counts the library's 1x1 kernels take (nd_pointwise_gemm_takes)")
     if res is None:
         return LinearFunction.apply(x, weight, bias)
     if tuple(res.shape) != tuple(x.shape[:-1]) + (weight.shape[0],):
@@ -915,19 +908,15 @@ def conv7x7_c4(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tenso
 
 def _eligible_linear(m: nn.Module) -> bool:
     if isinstance(m, nn.Linear):
-        return _linear_ok(m.in_features, m.out_features)
+        return pointwise_takes(m.in_features, m.out_features)
     return (isinstance(m, nn.Conv2d) and m.kernel_size == (1, 1) and m.stride == (1, 1) and m.padding == (0, 0) and m.groups == 1
-            and _linear_ok(m.in_channels, m.out_channels))
+            and pointwise_takes(m.in_channels, m.out_channels))
 
 
 def _hip_linear_forward(self, x: torch.Tensor) -> torch.Tensor:
     if isinstance(self, nn.Linear):
         return linear(x, self.weight, self.bias)
     return conv1x1(x, self.weight, self.bias)
-
-
-def _layer_norm_ok(C_: int) -> bool:
-    return C_ % 4 == 0 and 16 <= C_ <= 1024          # (r5: any multiple of 4 -- the d = 48 network's 48 / 96 / 192 / 384 included)
 
 
 class LayerNormFunction(torch.autograd.Function):
@@ -966,9 +955,10 @@ class LayerNormFunction(torch.autograd.Function):
 
 
 def layer_norm(x: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor, eps: float = 1e-5) -> torch.Tensor:
-    """Differentiable F.layer_norm(x, (C,), weight, bias, eps) over the last dimension on the HIP library (C = 64, 128 or a multiple of 256 <= 1024)."""
-    if weight is None or bias is None or not _layer_norm_ok(x.shape[-1]) or weight.shape != (x.shape[-1],):
-        raise ValueError(f"layer_norm: x {tuple(x.shape)}: needs affine parameters and C = 64, 128 or a multiple of 256 up to 1024")
+    """Differentiable F.layer_norm(x, (C,), weight, bias, eps) over the last dimension on the HIP library (a width that nd_layernorm_train_takes: the d = 48
+    network's 48 / 96 / 192 / 384 included)."""
+    if weight is None or bias is None or not layer_norm_takes(x.shape[-1]) or weight.shape != (x.shape[-1],):
+        raise ValueError(f"layer_norm: x {tuple(x.shape)}: needs affine parameters and a width that nd_layernorm_train_takes")
     return LayerNormFunction.apply(x, weight, bias, eps)
 
 
@@ -1062,10 +1052,6 @@ def linear_attention_core(qkv: torch.Tensor, heads: int = 4) -> torch.Tensor:
     return LinearAttentionCoreFunction.apply(qkv, heads)
 
 
-def _rms_norm_ok(C_: int) -> bool:
-    return C_ % 4 == 0 and 0 < C_ <= 1024
-
-
 class RMSNormFunction(torch.autograd.Function):
     """RMSNorm (Diffusion_arch.py:84-90): F.normalize(x, dim=1) * g * sqrt(C) (+ res, added in the forward kernel) on nd_rmsnorm(_add)_nhwc_f32 and
     nd_rmsnorm_backward_f32; the residual's gradient is the output's."""
@@ -1104,10 +1090,10 @@ class RMSNormFunction(torch.autograd.Function):
 
 
 def rms_norm(x: torch.Tensor, g: torch.Tensor, res: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """Differentiable RMSNorm over the channels of a 4-D tensor on the HIP library: ``g`` (1, C, 1, 1) as the reference stores it (C % 4 == 0, C <= 1024);
+    """Differentiable RMSNorm over the channels of a 4-D tensor on the HIP library: ``g`` (1, C, 1, 1) as the reference stores it (a width that nd_rmsnorm_train_takes);
     ``res`` (x's shape) is added in the forward kernel."""
-    if x.dim() != 4 or not _rms_norm_ok(x.shape[1]) or g.numel() != x.shape[1]:
-        raise ValueError(f"rms_norm: x {tuple(x.shape)} / g {tuple(g.shape)}: needs a 4-D input, C a multiple of 4 up to 1024 and C gains")
+    if x.dim() != 4 or not rms_norm_takes(x.shape[1]) or g.numel() != x.shape[1]:
+        raise ValueError(f"rms_norm: x {tuple(x.shape)} / g {tuple(g.shape)}: needs a 4-D input, a width that nd_rmsnorm_train_takes and C gains")
     if res is not None and res.shape != x.shape:
         raise ValueError(f"rms_norm: res {tuple(res.shape)} does not match x {tuple(x.shape)}")
     return RMSNormFunction.apply(x, g, res)
@@ -1115,7 +1101,7 @@ def rms_norm(x: torch.Tensor, g: torch.Tensor, res: Optional[torch.Tensor] = Non
 
 def _eligible_layer_norm(m: nn.Module) -> bool:
     return (isinstance(m, nn.LayerNorm) and len(m.normalized_shape) == 1 and m.elementwise_affine and m.bias is not None
-            and _layer_norm_ok(m.normalized_shape[0]))
+            and layer_norm_takes(m.normalized_shape[0]))
 
 
 def _hip_layer_norm_forward(self: nn.LayerNorm, x: torch.Tensor) -> torch.Tensor:
@@ -1144,7 +1130,7 @@ def _hip_block_forward(self, x: torch.Tensor, scale_shift=None) -> torch.Tensor:
 
 def _eligible(m: nn.Module) -> bool:
     return (isinstance(m, nn.Conv2d) and m.kernel_size == (3, 3) and m.stride == (1, 1) and m.padding == (1, 1) and m.dilation == (1, 1)
-            and m.groups == 1 and m.padding_mode == "zeros" and m.in_channels % 8 == 0 and m.out_channels % 8 == 0)
+            and m.groups == 1 and m.padding_mode == "zeros" and conv3x3_trains(m.in_channels, m.out_channels))
 
 
 def _hip_conv_forward(self: nn.Conv2d, x: torch.Tensor) -> torch.Tensor:

@@ -22,6 +22,7 @@ import torch.nn.functional as F
 from torch import nn
 
 from . import synth, train
+from ._host import conv3x3_trains, group_norm_takes, layer_norm_takes, pointwise_takes, rms_norm_takes
 from .spec import noisediff_param_spec
 
 P = Dict[str, torch.Tensor]
@@ -76,14 +77,19 @@ class _Ops:
             FALLBACKS[(name, op)] = why
             _log.warning("%s: %s stays on PyTorch (%s)", name, op, why)
 
+    def _conv_on_library(self, x: torch.Tensor, w: torch.Tensor, padding: int, k: int) -> bool:
+        """Does the library's differentiable k x k convolution (3: train.conv3x3, 1: train.conv1x1) run this layer?  The same questions ``train`` asks."""
+        if not (self.hip and x.is_cuda and tuple(w.shape[2:]) == (k, k) and padding == k // 2):
+            return False
+        return conv3x3_trains(w.shape[1], w.shape[0]) if k == 3 else pointwise_takes(w.shape[1], w.shape[0])
+
     def conv(self, name: str, x, padding: int = 0, res: Optional[torch.Tensor] = None) -> torch.Tensor:
         """``x``: a tensor, or a pair (x0, x1) standing for torch.cat((x0, x1), 1) -- the up path's skip concatenations, which the library's 3x3 and
         1x1 convolutions read as two sources (train.conv3x3_cat / conv1x1_cat) instead of a concatenated copy.  ``res``: conv(x) + res, the addition in the
         epilogue of the library's 1x1 kernel where that runs."""
         w, b = self.p[name + ".weight"], self.p.get(name + ".bias")
         if res is not None:
-            if (self.hip and not isinstance(x, tuple) and x.is_cuda and w.shape[2:] == (1, 1) and padding == 0 and w.shape[0] % 4 == 0 and w.shape[1] % 4 == 0
-                    and res.shape[1] == w.shape[0]):
+            if not isinstance(x, tuple) and self._conv_on_library(x, w, padding, 1) and res.shape[1] == w.shape[0]:
                 return train.conv1x1(x, w, b, res=res)
             return self.conv(name, x, padding) + res
         if isinstance(x, tuple):
@@ -93,45 +99,45 @@ class _Ops:
                 if w.shape[2:] == (1, 1) and padding == 0:
                     return train.conv1x1_cat(x[0], x[1], w, b)
             x = torch.cat(x, dim=1)
-        if self.hip and x.is_cuda and w.shape[2:] == (3, 3) and padding == 1 and w.shape[0] % 8 == 0 and w.shape[1] % 8 == 0:
+        if self._conv_on_library(x, w, padding, 3):
             return train.conv3x3(x, w, b)
-        if self.hip and x.is_cuda and w.shape[2:] == (1, 1) and padding == 0 and w.shape[0] % 4 == 0 and w.shape[1] % 4 == 0:
+        if self._conv_on_library(x, w, padding, 1):
             return train.conv1x1(x, w, b)
         if self.hip and x.is_cuda and tuple(w.shape[1:]) == (4, 7, 7) and padding == 3 and w.shape[0] % 4 == 0:
             return train.conv7x7_c4(x, w, b)                                    # the stem (init_conv / cond_init_conv)
-        if self.hip and x.is_cuda and w.shape[2:] == (1, 1) and padding == 0 and w.shape[0] % 4 == 0 and w.shape[1] < 4:
+        if self.hip and x.is_cuda and w.shape[2:] == (1, 1) and padding == 0 and w.shape[1] < 4 and pointwise_takes(4, w.shape[0]):
             # pos_enc.weights (2 -> 8 channels, Diffusion_arch.py:328): as a 4-channel 1x1 convolution with two zero input channels -- the zero weight columns
             # receive gradients that the slice drops
             pad = 4 - w.shape[1]
             return train.conv1x1(F.pad(x, (0, 0, 0, 0, 0, pad)), F.pad(w, (0, 0, 0, 0, 0, pad)), b)
         if x.is_cuda:
-            self._left_library(name, f"conv{w.shape[2]}x{w.shape[3]}", f"{w.shape[1]} -> {w.shape[0]} channels: the library's differentiable convolutions are 3x3 (channels % 8), 1x1 (cout % 4) and the 7x7 stem of a 4-channel image")
+            self._left_library(name, f"conv{w.shape[2]}x{w.shape[3]}", f"{w.shape[1]} -> {w.shape[0]} channels: the library's differentiable convolutions are 3x3 (widths nd_conv3x3_takes of the direct kernel, both ways), 1x1 (widths nd_pointwise_gemm_takes) and the 7x7 stem of a 4-channel image")
         return F.conv2d(x, w, b, padding=padding)
 
     def linear(self, name: str, x: torch.Tensor, res: Optional[torch.Tensor] = None) -> torch.Tensor:
         """``res``: linear(x) + res, the addition in the GEMM's epilogue on the library."""
         w, b = self.p[name + ".weight"], self.p.get(name + ".bias")
-        if self.hip and x.is_cuda and w.shape[0] % 4 == 0 and w.shape[1] % 4 == 0:
+        if self.hip and x.is_cuda and pointwise_takes(w.shape[1], w.shape[0]):
             return train.linear(x, w, b, res)
         if x.is_cuda:
-            self._left_library(name, "linear", f"{w.shape[1]} -> {w.shape[0]}: channel counts must be multiples of 4")
+            self._left_library(name, "linear", f"{w.shape[1]} -> {w.shape[0]}: nd_pointwise_gemm_takes refuses the widths")
         y = F.linear(x, w, b)
         return y if res is None else y + res
 
     def group_norm(self, name: str, x: torch.Tensor, groups: int) -> torch.Tensor:
         w, b = self.p[name + ".weight"], self.p[name + ".bias"]
         if self.hip and x.is_cuda:
-            if train._group_norm_ok(x.shape[1], groups):                     # wider nets (dim > 128: C > 1024) stay on PyTorch's norm
+            if group_norm_takes(x.shape[1], groups):                         # wider nets (dim > 128: C > 1024) stay on PyTorch's norm
                 return train.group_norm(x, groups, w, b, 1e-5)
-            self._left_library(name, "group_norm", f"C = {x.shape[1]}, {groups} groups: outside the library's norm (C <= 1024, C % 4 == 0)")
+            self._left_library(name, "group_norm", f"C = {x.shape[1]}, {groups} groups: nd_groupnorm_train_takes refuses them")
         return F.group_norm(x, groups, w, b, eps=1e-5)
 
     def layer_norm(self, name: str, x: torch.Tensor) -> torch.Tensor:
         w, b = self.p[name + ".weight"], self.p[name + ".bias"]
         if self.hip and x.is_cuda:
-            if train._layer_norm_ok(x.shape[-1]):
+            if layer_norm_takes(x.shape[-1]):
                 return train.layer_norm(x, w, b, 1e-5)
-            self._left_library(name, "layer_norm", f"C = {x.shape[-1]}: the library's LayerNorm takes C = 64, 128 or a multiple of 256")
+            self._left_library(name, "layer_norm", f"C = {x.shape[-1]}: nd_layernorm_train_takes refuses the width")
         return F.layer_norm(x, x.shape[-1:], w, b, eps=1e-5)
 
     # ---- composite layers ------------------------------------------------------------------------------------------
@@ -140,13 +146,13 @@ class _Ops:
         along dim 1: (B, 2C, 1, 1) from the time embedding or (B, 2C, H, W) per-pixel maps."""
         w = self.p[name + ".proj.weight"]
         pair = x if isinstance(x, tuple) else None                             # (x0, x1) = torch.cat((x0, x1), 1), read as two sources where the kernels can
-        if pair is not None and not (self.hip and train.cat_sources_ok(*pair, w.shape[0]) and train._group_norm_ok(w.shape[0], groups)
+        if pair is not None and not (self.hip and train.cat_sources_ok(*pair, w.shape[0]) and group_norm_takes(w.shape[0], groups)
                                      and (ss is None or ss.numel() == pair[0].shape[0] * 2 * w.shape[0])):
             x, pair = torch.cat(pair, dim=1), None
         x0 = pair[0] if pair is not None else x
-        fused = (self.hip and x0.is_cuda and train._group_norm_ok(w.shape[0], groups)
+        fused = (self.hip and x0.is_cuda and group_norm_takes(w.shape[0], groups)
                  and (ss is None or ss.numel() == x0.shape[0] * 2 * w.shape[0]))   # norm, per-sample modulation, SiLU (and the block's shortcut) as one operator
-        if fused and w.shape[0] % 8 == 0 and w.shape[1] % 8 == 0:
+        if fused and conv3x3_trains(w.shape[1], w.shape[0]):
             # ... fed by the convolution's statistics epilogue, as in the sampling engine: no pass of the norm's own over the conv output for its moments
             if pair is not None:
                 x, cs = train.conv3x3_cat(pair[0], pair[1], w, self.p.get(name + ".proj.bias"), with_stats=True)
@@ -232,9 +238,9 @@ class _Ops:
         """RMSNorm (:84-90): F.normalize over the channels * g * sqrt(C) (+ res: in the library's forward kernel)."""
         g = self.p[name + ".g"]
         if self.hip and x.is_cuda:
-            if train._rms_norm_ok(x.shape[1]):
+            if rms_norm_takes(x.shape[1]):
                 return train.rms_norm(x, g, res)
-            self._left_library(name, "rms_norm", f"C = {x.shape[1]}: outside the library's RMSNorm (C <= 1024, C % 4 == 0)")
+            self._left_library(name, "rms_norm", f"C = {x.shape[1]}: nd_rmsnorm_train_takes refuses the width")
         y = F.normalize(x, dim=1) * g * (x.shape[1] ** 0.5)
         return y if res is None else y + res
 

@@ -348,7 +348,7 @@ def test_pointwise_split_matches_torch_and_the_fp32_kernel(ctx, case):
         if case == "qkv_nobias":
             bias, b64 = None, None
         ref = F.linear(x64, w64, b64)
-    d = L.Pointwise()
+    d = L.Pointwise(B=B, HW=HW, W=int(HW ** 0.5), ldo=cout)             # the question is about a whole shape: it includes the fp32 entry's own
     d.src, d.cin, d.cout = s, cin, cout
     assert ctx.lib.nd_pointwise_gemm_split_takes(C.byref(d)) == 1
     o32 = hu.pointwise(ctx, s, wp, bias, B, HW, int(HW ** 0.5), cin, cout, **kw)
@@ -359,9 +359,9 @@ def test_pointwise_split_matches_torch_and_the_fp32_kernel(ctx, case):
     again = hu.pointwise(ctx, s, ws, bias, B, HW, int(HW ** 0.5), cin, cout, entry="nd_pointwise_gemm_split_nhwc_f32", **kw)
     assert torch.equal(osp, again)                      # bitwise repeatable
     # shapes outside the kernel's set are refused by the split entry, not approximated
-    d2 = L.Pointwise()
+    d2 = L.Pointwise(B=B, HW=HW, W=int(HW ** 0.5), ldo=64)
     d2.src, d2.cin, d2.cout = s, cin, 64
-    assert ctx.lib.nd_pointwise_gemm_split_takes(C.byref(d2)) == 0
+    assert ctx.lib.nd_pointwise_gemm_split_takes(C.byref(d2)) == 0 and ctx.lib.nd_pointwise_gemm_takes(C.byref(d2)) == 1
 
 
 def test_pointwise_prologues(ctx):

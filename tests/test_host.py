@@ -516,6 +516,113 @@ def test_a_question_is_not_a_failure():
     assert lib.nd_conv3x3_takes(L.CONV3X3_WINO4, None, 1) == 0 and lib.nd_last_error() == said
 
 
+def _pw(cin=64, cout=64, c1=0, c0=None, ld0=None, ld1=None, ldo=None, split=False, rowstats=False, **kw):
+    """nd_pointwise_gemm_takes / _split_takes on a one-sample descriptor of 32 pixels (rows of 8); ``kw``: further fields of the descriptor or of its source."""
+    d = L.Pointwise(B=1, HW=32, W=8, cin=cin, cout=cout, ldo=cout if ldo is None else ldo)
+    c0 = cin - c1 if c0 is None else c0
+    d.src.c0, d.src.c1, d.src.ld0, d.src.ld1 = c0, c1, c0 if ld0 is None else ld0, c1 if ld1 is None else ld1
+    d.src.rowstats = 16 if rowstats else None                            # given or not is all a question reads of a pointer
+    for k, v in kw.items():
+        setattr(d.src if hasattr(d.src, k) else d, k, v)
+    return bool((L.load().nd_pointwise_gemm_split_takes if split else L.load().nd_pointwise_gemm_takes)(C.byref(d)))
+
+
+def test_norm_questions_answer_on_both_sides_of_each_limit():
+    lib = L.load()
+    gn = lambda c, g: bool(lib.nd_groupnorm_train_takes(c, g))
+    assert gn(64, 8) and gn(1024, 2) and not gn(1024, 1) and not gn(1028, 4) and not gn(60, 8) and not gn(6, 2) and not gn(0, 1) and not gn(64, 0)
+    ln = lambda c: bool(lib.nd_layernorm_train_takes(c))
+    assert ln(16) and not ln(12) and ln(1024) and not ln(1028) and not ln(18) and ln(48)
+    for q in (lib.nd_rmsnorm_train_takes, lib.nd_token_sum_takes):
+        assert q(4) and q(1024) and not q(1028) and not q(6) and not q(0) and not q(-4)
+
+
+def test_pointwise_questions_answer_on_both_sides_of_each_limit():
+    for split in (False, True):                                          # the common shape part: both entries
+        w = dict(split=split, cout=128)
+        assert _pw(**w) and not _pw(HW=0, **w) and not _pw(cin=62, **w) and not _pw(c0=60, **w)
+        assert _pw(c1=32, **w) and not _pw(c0=32, c1=28, **w) and not _pw(c0=30, c1=34, **w)
+        assert _pw(ld0=68, **w) and not _pw(ld0=60, **w) and not _pw(ld0=66, **w) and _pw(c1=32, ld1=36, **w) and not _pw(c1=32, ld1=28, **w) and not _pw(c1=32, ld1=34, **w)
+        assert _pw(ldo=132, **w) and not _pw(ldo=124, **w) and not _pw(ldo=130, **w) and not _pw(upsample=1, **w)
+        assert _pw(act=L.ACT_SILU, **w) and not _pw(act=3, **w) and not _pw(act=-1, **w)
+        assert _pw(mode=L.PRO_LEAKY, **w) and _pw(mode=L.PRO_AFFINE_SILU, **w) and not _pw(mode=L.PRO_AFFINE_SILU, c1=32, **w) and not _pw(mode=L.PRO_AFFINE_MAP_SILU, **w)
+        assert _pw(cin=1024, mode=L.PRO_LAYERNORM, rowstats=True, **w) and not _pw(cin=1028 if not split else 1056, mode=L.PRO_LAYERNORM, rowstats=True, **w)
+        assert _pw(cin=128, mode=L.PRO_LAYERNORM, rowstats=True, **w) and not _pw(cin=128, mode=L.PRO_LAYERNORM, **w) and not _pw(mode=L.PRO_LAYERNORM, rowstats=True, c1=32, **w)
+    # the fp32 entry alone: any width in fours, the LayerNorm prologue with its own statistics up to 64 channels, both shuffles
+    assert _pw(cin=24, cout=20) and _pw(cin=4, cout=4) and _pw(mode=L.PRO_LAYERNORM) and not _pw(cin=68, mode=L.PRO_LAYERNORM)
+    assert _pw(unshuffle=1, ld0=16) and not _pw(unshuffle=1, ld0=12) and not _pw(cin=24, unshuffle=1) and not _pw(unshuffle=1, W=5) and not _pw(unshuffle=1, mode=L.PRO_SILU)
+    shuf = dict(shuffle_c=16, shuffle_h=8, shuffle_w=16, ldo=16)
+    assert _pw(**shuf) and not _pw(**dict(shuf, shuffle_c=12)) and not _pw(**dict(shuf, ldo=12)) and not _pw(**dict(shuf, shuffle_h=0)) and not _pw(**dict(shuf, W=5))
+    # the split kernel's own conditions
+    s = lambda **kw: _pw(split=True, **dict(dict(cout=128), **kw))
+    assert s(cin=64) and not s(cin=32) and s(cin=96) and not s(cin=80) and s(cout=256) and not s(cout=64) and not s(cout=192)
+    assert s(cin=96, c1=32) and s(cin=96, c1=64) and not s(cin=96, c1=48) and not s(cin=96, c1=16)
+    assert not s(unshuffle=1, ld0=16) and not s(shuffle_c=32, shuffle_h=8, shuffle_w=16, ldo=32) and _pw(cout=128, shuffle_c=32, shuffle_h=8, shuffle_w=16, ldo=32)
+    assert not s(mode=L.PRO_LAYERNORM) and s(mode=L.PRO_LAYERNORM, rowstats=True)
+    assert L.load().nd_pointwise_gemm_takes(None) == 0 and L.load().nd_pointwise_gemm_split_takes(None) == 0
+
+
+def test_chain_question_answers_for_the_pixel_tiles_and_the_width_table():
+    lib = L.load()
+    assert lib.nd_pointwise_chain_takes(32, 64, 128, 64, 64) and lib.nd_pointwise_chain_takes(64, 64, 128, 64, 64) and lib.nd_pointwise_chain_takes(32, 4, 32, 32, 0)
+    assert not lib.nd_pointwise_chain_takes(48, 64, 128, 64, 64) and not lib.nd_pointwise_chain_takes(0, 64, 128, 64, 64) and not lib.nd_pointwise_chain_takes(-32, 64, 128, 64, 64)
+    assert not lib.nd_pointwise_chain_takes(32, 64, 128, 128, 64) and not lib.nd_pointwise_chain_takes(32, 64, 64, 64, 64)
+    assert lib.nd_pointwise_chain_supported(64, 128, 64, 64) and not lib.nd_pointwise_chain_supported(64, 128, 128, 64)
+
+
+def test_wgrad_questions_answer_under_every_pin_and_on_both_sides_of_each_limit():
+    lib = L.load()
+    was = lib.nd_conv3x3_wgrad_form(-1)
+    try:
+        plans = {}
+        for pin in (0, 1, 2, 3):
+            lib.nd_conv3x3_wgrad_form(pin)
+            plans[pin] = [lib.nd_conv3x3_wgrad_plan(*shape) for shape in ((2, 16, 32, 64, 64), (1, 9, 11, 32, 64), (2, 16, 32, 48, 64), (79, 64, 64, 64, 64), (78, 64, 64, 64, 64))]
+        # Winograd shape with whole 32 / 64 blocks; nine taps only; cin % 32 != 0: four waves only; 79 * 16 * 4 * 2 * 2 = 20224 >= 20000 > 19968 block items: eight waves by the shape
+        assert plans == {0: [2, 1, 2, 3, 2], 1: [1, 1, 1, 1, 1], 2: [2, 1, 2, 2, 2], 3: [3, 1, 2, 3, 3]}
+        lib.nd_conv3x3_wgrad_form(0)
+        assert lib.nd_conv3x3_wgrad_plan(2, 16, 32, 62, 64) == 1 and lib.nd_conv3x3_wgrad_plan(0, 16, 32, 64, 64) == 1
+        cat = lambda B=2, H=16, W=32, c0=32, c1=32, cout=64, ldx0=None, ldx1=None, ldy=None: bool(lib.nd_conv3x3_wgrad_cat_takes(
+            B, H, W, c0, c1, cout, c0 if ldx0 is None else ldx0, c1 if ldx1 is None else ldx1, cout if ldy is None else ldy))
+        assert cat() and not cat(c0=16) and not cat(c1=48) and not cat(c1=0) and cat(W=16) and not cat(W=12) and cat(H=4) and not cat(H=6)
+        assert cat(cout=16) and not cat(cout=8) and not cat(cout=20) and cat(ldx0=36) and not cat(ldx0=28) and not cat(ldx0=34) and not cat(ldx1=28) and not cat(ldx1=34)
+        assert not cat(ldy=60) and not cat(ldy=66) and not cat(B=0)
+        # within a sample every tensor stays below 1 GiB (H W ld 4 < 2^30: 65536 pixels of 4092 / 4096 floats), and there are fewer than 2^30 pixels; nothing is allocated
+        big = dict(B=1, H=256, W=256)
+        for ld in ("ldx0", "ldx1", "ldy"):
+            assert cat(**big, **{ld: 4092}) and not cat(**big, **{ld: 4096})
+        assert cat(B=16383, H=256, W=256) and not cat(B=16384, H=256, W=256)
+        for pin, takes in ((1, False), (2, True), (3, True)):
+            lib.nd_conv3x3_wgrad_form(pin)
+            assert cat() == takes
+    finally:
+        lib.nd_conv3x3_wgrad_form(was)
+
+
+def test_the_new_questions_are_not_failures_either():
+    """Every question of the 1x1, chain, norm and weight-gradient families answering 0 leaves nd_last_error as the last refusal wrote it."""
+    lib = L.load()
+    assert lib.nd_conv3x3_wino_nhwc_f32(None, None) == -1               # a host-only refusal: returns before any HIP call
+    said = lib.nd_last_error()
+    assert not _pw(cin=62) and not _pw(ldo=60) and not _pw(cin=32, split=True) and not _pw(cin=128, mode=L.PRO_LAYERNORM, split=True)
+    assert not lib.nd_groupnorm_train_takes(1024, 1) and not lib.nd_layernorm_train_takes(12) and not lib.nd_rmsnorm_train_takes(6) and not lib.nd_token_sum_takes(1028)
+    assert not lib.nd_pointwise_chain_takes(48, 64, 128, 64, 64) and not lib.nd_pointwise_chain_takes(32, 64, 64, 64, 64)
+    assert lib.nd_conv3x3_wgrad_plan(1, 9, 11, 32, 64) == 1 and not lib.nd_conv3x3_wgrad_cat_takes(2, 16, 32, 16, 32, 64, 16, 32, 64)
+    assert not lib.nd_conv3x3_wgrad_cat_takes(1, 256, 256, 32, 32, 64, 32, 4096, 64)
+    assert lib.nd_last_error() == said
+
+
+def test_engine_layer_rules_equal_their_literal_rules_on_a_grid():
+    """engine._split_layer / _wino4_layer ask the library; the literal rules they replaced are the specification (cout in steps of 12: a few seconds)."""
+    from noisediff_amd import engine
+    for cin in range(4, 2049, 4):
+        for cout in range(4, 2049, 12):
+            assert engine._split_layer(cin, cout) == bool(engine.SPLIT_PW and cin % 32 == 0 and cin >= 64 and cout % 128 == 0), (cin, cout)
+            assert engine._wino4_layer(cin, cout) == (cin > 16 and cin % 4 == 0 and cout % 4 == 0), (cin, cout)
+    assert engine._wino4_layer(64, 2048) and not engine._wino4_layer(64, 2052)     # the one difference: no F(4x4) packing past the kernel's bias table
+    assert not engine._wino4_layer(16, 64) and not engine._wino4_layer(18, 64) and not engine._wino4_layer(64, 62) and not engine._split_layer(64, 0)
+
+
 def test_conv3x3_kind_answers_a_repeated_shape_from_its_cache():
     from noisediff_amd._host import conv3x3_kind
     shape = (3, 48, 80, 64, 64, 64, 0, 64)

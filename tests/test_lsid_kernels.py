@@ -168,16 +168,19 @@ def wgrad_form():
     lib.nd_conv3x3_wgrad_form(was)
 
 
-def _effective_form(B, H, W, cin, cout, pin):
-    """The form a pin runs (the library's rule, include/noisediff_hip.h): a Winograd form only where it takes the shape, eight waves only for
-    cout % 64 == 0, and the product's choice (pin 0) by the size of the problem."""
-    if pin == 1 or H % 4 or W % 16 or cin % 16 or cout % 16:
-        return 1
-    if pin == 2 or cout % 64 or cin % 32:
-        return 2
-    if pin == 3:
-        return 3
-    return 3 if B * (H // 4) * (W // 16) * (cin // 32) * (cout // 32) >= 20000 else 2
+def _under_pin(pin, question, *shape):
+    """The library's answer to one of its weight-gradient questions (nd_conv3x3_wgrad_plan / nd_conv3x3_wgrad_cat_takes) under a pin of the form; the
+    pin in force before is put back."""
+    lib = L.load()
+    was = lib.nd_conv3x3_wgrad_form(pin)
+    try:
+        return int(getattr(lib, question)(*shape))
+    finally:
+        lib.nd_conv3x3_wgrad_form(was)
+
+
+def _plan(B, H, W, cin, cout, pin):
+    return _under_pin(pin, "nd_conv3x3_wgrad_plan", B, H, W, cin, cout)
 
 
 def _lsid_wgrad_layers():
@@ -213,7 +216,7 @@ def _check_wgrad_leaky(B, H, W, cin, cout, tag, wgrad_form, x_lo=-1.5, x_hi=1.0,
     for form in (0,) + FORMS:
         wgrad_form(form)
         wsz[form] = int(lib.nd_conv3x3_wgrad_workspace_floats(B, H, W, cin, cout))
-    product = _effective_form(B, H, W, cin, cout, 0)
+    product = _plan(B, H, W, cin, cout, 0)
     assert wsz[0] == wsz[product], (tag, wsz)                           # the product runs the form the rule names
     ref = db64 = None
     for form in FORMS:
@@ -222,7 +225,7 @@ def _check_wgrad_leaky(B, H, W, cin, cout, tag, wgrad_form, x_lo=-1.5, x_hi=1.0,
         got = _twice(lambda: _wgrad("nd_conv3x3_wgrad_leaky_nhwc_f32", x, ldx, dy, B, H, W, cin, cout, ws))
         twin = _twice(lambda: _wgrad("nd_conv3x3_wgrad_nhwc_f32", xa, cin, dy, B, H, W, cin, cout, ws))
         assert torch.equal(got[0], twin[0]) and torch.equal(got[1], twin[1]), (tag, form)
-        if _effective_form(B, H, W, cin, cout, form) == form:       # (a pin that does not take the shape ran another form: checked there)
+        if _plan(B, H, W, cin, cout, form) == form:       # (a pin that does not take the shape ran another form: checked there)
             if ref is None:
                 ref = torch.nn.grad.conv2d_weight(F.leaky_relu(_nchw64(x), SLOPE), (cout, cin, 3, 3), _nchw64(dy), padding=1).numpy()
                 db64 = _nchw64(dy).sum(dim=(0, 2, 3)).numpy()
@@ -244,16 +247,16 @@ def test_wgrad_leaky_reads_a_channel_slice_and_an_all_negative_input(wgrad_form)
 
 
 def test_the_lsid_wgrad_table_reaches_every_form():
-    """By the library's rule (_effective_form, a copy of ww_takes / ww_plan in conv3x3_wgrad.hip), the product picks the nine-tap form (1) or the
+    """By the library's own answer (nd_conv3x3_wgrad_plan), the product picks the nine-tap form (1) or the
     four-wave Winograd-domain form (2) on LSID's layers -- never the eight-wave form (3), whose threshold no LSID layer here reaches.  Form 3 runs on
     this table only where the tests pin it (cout % 64 == 0: 64x64 stages 2 and 3).  The library's own evidence is the workspace it asks for: the
     Winograd-domain layout is larger than the nine-tap one on the 64x64 stages 1 to 3, so form 0 there is shown to be a Winograd form.  The
     workspace cannot tell form 2 from form 3 (the same size on these shapes); _check_wgrad_leaky asserts form 0's size equals the named form's."""
-    product = {_effective_form(B, H, W, cin, cout, 0) for B, H, W, cin, cout, _ in WGRAD_CASES}
-    pinned = {_effective_form(B, H, W, cin, cout, f) for B, H, W, cin, cout, _ in WGRAD_CASES for f in FORMS}
+    product = {_plan(B, H, W, cin, cout, 0) for B, H, W, cin, cout, _ in WGRAD_CASES}
+    pinned = {_plan(B, H, W, cin, cout, f) for B, H, W, cin, cout, _ in WGRAD_CASES for f in FORMS}
     assert product == {1, 2} and 3 not in product                    # form 3: reached by pinning only
     assert pinned == {1, 2, 3}
-    assert {tag for B, H, W, cin, cout, tag in WGRAD_CASES if _effective_form(B, H, W, cin, cout, 3) == 3} == {
+    assert {tag for B, H, W, cin, cout, tag in WGRAD_CASES if _plan(B, H, W, cin, cout, 3) == 3} == {
         "64x64.conv2_2", "64x64.conv2_1", "64x64.conv3_2", "64x64.conv3_1"}
     lib = L.load()
     was = lib.nd_conv3x3_wgrad_form(-1)
@@ -266,7 +269,7 @@ def test_the_lsid_wgrad_table_reaches_every_form():
                 sizes.append(int(lib.nd_conv3x3_wgrad_workspace_floats(B, H, W, cin, cout)))
             if sizes[0] != sizes[1]:
                 shown.add(tag)
-                assert _effective_form(B, H, W, cin, cout, 0) != 1, tag
+                assert _plan(B, H, W, cin, cout, 0) != 1, tag
     finally:
         lib.nd_conv3x3_wgrad_form(was)
     assert shown >= {"64x64.conv1_2", "64x64.conv2_1", "64x64.conv2_2", "64x64.conv3_1", "64x64.conv3_2"}
@@ -286,8 +289,8 @@ def _cat_cases():
     return cases
 
 
-def _ww_cat(B, H, W, c0, c1, cout, pin):
-    return c0 % 32 == 0 and c1 % 32 == 0 and _effective_form(B, H, W, c0 + c1, cout, pin) != 1
+def _cat_takes(B, H, W, c0, c1, cout, pin, ldx0=None):
+    return bool(_under_pin(pin, "nd_conv3x3_wgrad_cat_takes", B, H, W, c0, c1, cout, c0 if ldx0 is None else ldx0, c1, cout))
 
 
 @pytest.mark.parametrize("form", [0, 1, 3])
@@ -313,7 +316,7 @@ def test_wgrad_cat_leaky_second_activates_the_second_source_only(case, form, wgr
         return dw, db
 
     dw, db = _twice(lambda: run("nd_conv3x3_wgrad_cat_leaky_second_nhwc_f32", x1))
-    if _ww_cat(B, H, W, c0, c1, cout, form):
+    if _cat_takes(B, H, W, c0, c1, cout, form, ldx0=c0 + 16):
         tw, tb = _twice(lambda: run("nd_conv3x3_wgrad_cat_nhwc_f32", x1a))
         assert torch.equal(dw, tw) and torch.equal(db, tb)
     else:                                                               # nine taps per source, whatever the pin asks for the single-source entry
@@ -333,8 +336,8 @@ def test_wgrad_cat_leaky_second_activates_the_second_source_only(case, form, wgr
 
 def test_the_cat_table_takes_both_branches():
     cases = _cat_cases()
-    assert any(_ww_cat(B, H, W, c0, c1, co, 0) for B, H, W, c0, c1, co, _ in cases)
-    assert any(not _ww_cat(B, H, W, c0, c1, co, 0) for B, H, W, c0, c1, co, _ in cases)
+    assert any(_cat_takes(B, H, W, c0, c1, co, 0) for B, H, W, c0, c1, co, _ in cases)
+    assert any(not _cat_takes(B, H, W, c0, c1, co, 0) for B, H, W, c0, c1, co, _ in cases)
 
 
 # ====================================================================================================== 4. conv10's weight gradient

@@ -147,7 +147,7 @@ GEMM = {
     "n_cin1024": row("narrow8", (0, 0), 1, 37, 1024, 8, ep="b", why="the whole 32 KB LDS weight image (`wl[256 * 8 * 4]`)"),
     "n_trip": row("narrow4", (0, 0), 1, lambda n: 64 * 8 * n + 37, 8, 4, ep="b0", why="grid = 8 CUs blocks: the first 37-pixel block of a second grid-stride trip"),
 }
-# ---- the split entry: pointwise_split_kernel (pw_split_takes: cin % 32 == 0, cin >= 64, cout % 128 == 0)
+# ---- the split entry: pointwise_split_kernel (pw_split_shape: cin % 32 == 0, cin >= 64, cout % 128 == 0)
 SPLIT = {
     "s_cin64": row("split", None, 2, 130, 64, 128, ep="b", why="two chunks; HW = 130: a second 128-pixel tile of 2 rows"),
     "s_cin96_cat": row("split", None, 2, 130, 96, 128, c0=32, pro="silu", ep="b0", why="three chunks (`cbn` re-stage, `min(.., last_ks)`), concat at 32"),
@@ -251,6 +251,7 @@ def test_gemm_bodies(ctx, name):
     B, HW = resolve(r)
     inp, r64, r32 = gemm_case(name, B, HW)
     d, out, keep = gemm_desc(ctx, r, inp, B, HW)
+    assert ctx.lib.nd_pointwise_gemm_takes(C.byref(d)) == 1
     run_twice(ctx, lambda: ctx.lib.nd_pointwise_gemm_nhwc_f32(C.byref(d), ctx.stream), out, (B, HW, r["cout"]), r64, r32, keep, f"{r['body']} {name}")
 
 
@@ -384,6 +385,7 @@ def test_chain_every_instantiated_width(ctx, name, form):
     B, HW = 2, 64
     widths, _ = CHAINS[name]
     assert ctx.lib.nd_pointwise_chain_supported(widths[0], widths[1], widths[2], widths[3] if len(widths) == 4 else 0)
+    assert ctx.lib.nd_pointwise_chain_takes(HW, widths[0], widths[1], widths[2], widths[3] if len(widths) == 4 else 0)
     inp, r64 = chain_inputs(name, B, HW)
     r32 = R.chain(inp, R.F32, ENTRY[form][2])
     dt, out, keep = chain_desc(ctx, form, name, inp, B, HW)
@@ -454,7 +456,9 @@ def _set(path, value):
     return f
 
 
-# name -> (base row, split entry, descriptor mutation, fragment of the message)
+# name -> (base row, split entry, descriptor mutation, fragment of the message).  Rows of OPERANDS are refused for an operand that is given (its stride): the
+# entry's pointer part; every other row is refused by the shape part, which the question of the entry answers too.
+OPERANDS = {"ldr0_below_cout", "ldr1_not_a_multiple_of_4", "ldt_below_cout"}
 REFUSALS = {
     "ln_cin_above_1024": ("ln1028", False, None, "C <= 1024"),
     "ln_wide_without_rowstats": ("g_cin80_ln", False, _set("src.rowstats", None), "needs src.rowstats"),
@@ -486,11 +490,12 @@ def test_gemm_refusals(ctx, name):
     if callable(mutate):
         mutate(d)
     fn = ctx.lib.nd_pointwise_gemm_split_nhwc_f32 if split else ctx.lib.nd_pointwise_gemm_nhwc_f32
+    takes = ctx.lib.nd_pointwise_gemm_split_takes if split else ctx.lib.nd_pointwise_gemm_takes
     rc, msg = finish(ctx, fn(C.byref(d), ctx.stream), name)
     assert rc < 0 and why in msg, f"{name}: expected a refusal with '{why}', got rc {rc} '{msg}'"
+    assert msg.startswith("nd_pointwise_gemm_split: " if "split kernel" in why else "nd_pointwise: "), msg
     assert torch.isnan(out.host()).all(), f"{name}: a refused call wrote to the output"
-    if split:
-        assert ctx.lib.nd_pointwise_gemm_split_takes(C.byref(d)) == 0
+    assert takes(C.byref(d)) == (1 if name in OPERANDS else 0), f"{name}: the question and the entry disagree"
 
 
 CHAIN_REFUSALS = {
@@ -515,6 +520,19 @@ def test_chain_refusals(ctx, name):
     rc, msg = finish(ctx, chain_call(ctx, form, dt)(), name)
     assert rc < 0 and why in msg, f"{name}: expected a refusal with '{why}', got rc {rc} '{msg}'"
     assert torch.isnan(out.host()).all(), f"{name}: a refused call wrote to the output"
+    if form != "tail" and ("multiple of 32" in why or "not instantiated" in why):      # what nd_pointwise_chain_takes answers for: pixel tiles and widths
+        ch = dt.chain
+        assert ctx.lib.nd_pointwise_chain_takes(ch.HW, ch.src.c0 + ch.src.c1, ch.st[0].cout, ch.st[1].cout, ch.st[2].cout if ch.n_stages == 3 else 0) == 0
+
+
+def test_the_library_instantiates_no_chain_the_list_lacks(ctx):
+    """CHAINS is this file's own list of the instantiated widths; the library's table (one X-macro in pwchain.hip) has no further row on a grid around it."""
+    up = lambda v, m: -(-v // m) * m
+    listed = {(up(w[0], 8), up(w[1], 32), up(w[2], 32), up(w[3], 32) if len(w) == 4 else 0) for w, _ in CHAINS.values()}
+    assert len(listed) == len(CHAINS) == 13
+    grid = [(k0, n1, n2, n3) for k0 in range(8, 89, 8) for n1 in range(32, 193, 32) for n2 in range(32, 193, 32) for n3 in range(0, 193, 32)]
+    assert {g for g in grid if ctx.lib.nd_pointwise_chain_supported(*g)} == listed
+    assert {g for g in grid if ctx.lib.nd_pointwise_chain_takes(64, *g)} == listed and not any(ctx.lib.nd_pointwise_chain_takes(48, *g) for g in listed)
 
 
 # ================================================================================================================ packers

@@ -579,3 +579,57 @@ def test_block_with_the_convs_statistics_at_the_step_shapes_matches_float64(k):
     for got, r, name in zip([dx, wa.grad, ba.grad, ga.grad, bea.grad, sa.grad, ra.grad, y.grad], [t.grad for t in td] + [yd.grad],
                             ("dx", "dw", "db", "dgamma", "dbeta", "dss", "dres", "dconv_out")):
         assert rel_err(got.cpu().numpy(), r.numpy()) < 2e-4, (k, name)
+
+
+# ---------------------------------------------------------------------------------------------------------------- the questions and their entries
+
+def test_the_norm_and_weight_gradient_questions_agree_with_their_entries():
+    """nd_groupnorm_train_takes, nd_layernorm_train_takes, nd_rmsnorm_train_takes, nd_token_sum_takes and nd_conv3x3_wgrad_cat_takes against what their entries
+    do, just inside and just outside each limit (one sample of 32 pixels; every pointer valid and aligned, so a refusal is a refusal of the shape).  An entry
+    decides on the host before any launch: a shape its question refuses starts no kernel.  The answers are literals, not computed from the code."""
+    lib, st = L.load(), _st()
+    HW, CMAX = 32, 1028
+    buf = lambda n: torch.zeros(n, device=DEV)
+    x, y, g, dx = U("q.x", (HW * CMAX,)).to(DEV), buf(HW * CMAX), U("q.g", (HW * CMAX,)).to(DEV), buf(HW * CMAX)
+    gamma, beta, dgam, dbet = U("q.gamma", (CMAX,)).to(DEV), U("q.beta", (CMAX,)).to(DEV), buf(CMAX), buf(CMAX)
+    stats, mad = buf(2 * CMAX), buf(3 * CMAX)
+    ws = buf(int(max(lib.nd_groupnorm_silu_train_workspace_floats(1, HW, CMAX), lib.nd_layernorm_train_workspace_floats(HW, CMAX),
+                     lib.nd_rmsnorm_backward_workspace_floats(HW, CMAX), lib.nd_token_sum_workspace_floats(1, HW, CMAX))))
+    p = lambda t: t.data_ptr()
+
+    def agree(takes, want, entry, prefix, call):
+        rc = call()
+        msg = lib.nd_last_error().decode() if rc else ""
+        assert rc <= 0, f"{entry}: HIP error {rc}: {msg}"
+        assert bool(takes) == want == (rc == 0), f"{entry}: the question says {takes}, the entry returned {rc} '{msg}', expected {want}"
+        assert rc == 0 or msg.startswith(prefix + ":"), msg
+
+    for C_, G, want in ((64, 8, True), (1024, 2, True), (1024, 1, False), (1028, 4, False), (60, 8, False), (6, 2, False)):
+        takes = lib.nd_groupnorm_train_takes(C_, G)
+        agree(takes, want, "nd_groupnorm_train_forward_f32", "nd_groupnorm_train_forward",
+              lambda: lib.nd_groupnorm_train_forward_f32(p(x), C_, p(gamma), p(beta), p(y), C_, p(stats), p(ws), 1, HW, C_, G, 1e-5, st))
+        agree(takes, want, "nd_groupnorm_train_backward_f32", "nd_groupnorm_train_backward",
+              lambda: lib.nd_groupnorm_train_backward_f32(p(g), C_, p(x), C_, p(gamma), p(stats), p(dx), C_, p(dgam), p(dbet), p(ws), 1, HW, C_, G, st))
+        agree(takes, want, "nd_groupnorm_silu_train_forward_f32", "nd_groupnorm_silu_train_forward",
+              lambda: lib.nd_groupnorm_silu_train_forward_f32(p(x), C_, p(gamma), p(beta), None, None, 0, p(y), C_, p(stats), p(mad), p(ws), 1, HW, C_, G, 1e-5, st))
+        agree(takes, want, "nd_groupnorm_silu_train_backward_f32", "nd_groupnorm_silu_train_backward",
+              lambda: lib.nd_groupnorm_silu_train_backward_f32(p(g), C_, p(x), C_, p(gamma), p(beta), None, p(stats), p(mad), p(dx), C_, p(dgam), p(dbet), None, p(ws),
+                                                               1, HW, C_, G, st))
+    for C_, want in ((16, True), (12, False), (1024, True), (1028, False), (18, False)):
+        takes = lib.nd_layernorm_train_takes(C_)
+        agree(takes, want, "nd_layernorm_train_forward_f32", "nd_layernorm_train_forward",
+              lambda: lib.nd_layernorm_train_forward_f32(p(x), C_, p(gamma), p(beta), p(y), C_, p(stats), HW, C_, 1e-5, st))
+        agree(takes, want, "nd_layernorm_train_backward_f32", "nd_layernorm_train_backward",
+              lambda: lib.nd_layernorm_train_backward_f32(p(g), C_, p(x), C_, p(gamma), p(stats), p(dx), C_, p(dgam), p(dbet), p(ws), HW, C_, st))
+    for C_, want in ((4, True), (1024, True), (1028, False), (6, False), (0, False)):
+        agree(lib.nd_rmsnorm_train_takes(C_), want, "nd_rmsnorm_backward_f32", "nd_rmsnorm_backward",
+              lambda: lib.nd_rmsnorm_backward_f32(p(g), C_, p(x), C_, p(gamma), p(dx), C_, p(dgam), p(ws), 1, HW, C_, st))
+        agree(lib.nd_token_sum_takes(C_), want, "nd_token_sum_f32", "nd_token_sum", lambda: lib.nd_token_sum_f32(p(x), C_, p(y), p(ws), 1, HW, C_, st))
+    # the two-source weight gradient: 4 x 16 pixels is one tile group of the Winograd-domain form, 9 x 11 and 6 x 16 are none; sources of whole 32-channel blocks
+    dw, wsw = buf(64 * 64 * 9), buf(int(max(lib.nd_conv3x3_wgrad_workspace_floats(1, 9, 11, 64, 64), lib.nd_conv3x3_wgrad_workspace_floats(1, 4, 16, 64, 64),
+                                         lib.nd_conv3x3_wgrad_workspace_floats(1, 4, 16, 64, 16))))
+    for H, W, c0, c1, cout, want in ((4, 16, 32, 32, 16, True), (4, 16, 32, 32, 64, True), (4, 16, 16, 48, 16, False), (4, 16, 32, 16, 16, False), (9, 11, 32, 32, 16, False),
+                                     (6, 16, 32, 32, 16, False), (4, 16, 32, 32, 8, False)):
+        agree(lib.nd_conv3x3_wgrad_cat_takes(1, H, W, c0, c1, cout, c0, c1, cout), want, "nd_conv3x3_wgrad_cat_nhwc_f32", "nd_conv3x3_wgrad_cat_nhwc_f32",
+              lambda: lib.nd_conv3x3_wgrad_cat_nhwc_f32(p(x), c0, c0, p(g), c1, c1, p(y), cout, p(dw), p(dbet), p(wsw), 1, H, W, cout, st))
+    torch.cuda.synchronize()
