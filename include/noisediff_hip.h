@@ -564,6 +564,38 @@ int nd_raw_to_bayer_u16(const float* img, uint16_t* out, const int32_t* bl, int 
  * A thread takes 4, 2 or 1 packed columns: the widest that w and the given outputs' alignment allow. */
 int nd_raw_diffusion_batch_f32(const uint16_t* frames, int N, int H2, int W2, const nd_raw_sample* table, float black, float white, float* noise,
                                float* noisy, float* clean, float* coord, int B, int h, int w, void* stream);
+/* A packed RAW frame developed to an sRGB picture (develop.hip): what test_denoising.py's postprocess_bayer gets from
+ * rawpy.postprocess(use_camera_wb=True, half_size=True, no_auto_bright=True, output_bps=8, bright=1), LibRaw's develop steps restated; also
+ * half_size=False with the bilinear demosaic and output_bps=16.  NOT checked against LibRaw bit for bit: the yardstick is tests/render_ref.py.
+ * Integer arithmetic except where fp32 is named; every fp32 step is one IEEE operation in the written order, no fused multiply-add.
+ * The source is ONE of src_f32 (fp32 [B][4][H][W], channels as above) and src_u16 (uint16 [B][2H][2W]), the other NULL; H, W: the packed frame.
+ * Per CFA value of channel c:
+ *   from a code x: v = max(x - black[c], 0); from a packed value: x is nd_raw_to_bayer_u16's code first (clip by comparisons, NaN -> 0,
+ *   t = (double)p * (white - black[c]) + black[c], truncated), then the same v;
+ *   s = min(trunc(fl32(v) * scale_mul[c]), 65535), one fp32 multiply, truncation toward zero.
+ * full = 0: window pixel (y, x) = packed pixel (y0 + y, x0 + x) gives one output pixel, R = s0, G = (s1 + s3) >> 1, B = s2; out is [B][h][w][3].
+ * full = 1: every site (r, q) of the window's 2h x 2w mosaic gives one output pixel; out is [B][2h][2w][3].  The site keeps its own colour's s
+ *   (both greens are G); each missing colour is floor(sum / count) over the sites of that colour in the 3 x 3 window around (r, q) that lie inside
+ *   the FRAME (not the window): (a + b) >> 1 at green sites and (a + b + c + d) >> 2 at red and blue sites in the interior, the mean of the 1 to 3
+ *   sites there are on the frame's outermost ring (dcraw's lin_interpolate and border_interpolate(1)).
+ * Colour and tone, for output channel k: o = 0 + R * rgb_cam[3k]; o = o + G * rgb_cam[3k + 1]; o = o + B * rgb_cam[3k + 2] in fp32, each product
+ *   rounded before it is added; u = clip((int)o, 0, 65535), truncation toward zero; the value written is curve[u] >> 8 as uint8 (bps = 8) or
+ *   curve[u] as uint16 (bps = 16), channels interleaved.
+ * params: HOST memory, read during the call; the B images share it.  curve: uint16[65536] in DEVICE memory, 16-byte aligned.  The sources and
+ * out: 4-byte aligned (ND_E_ALIGN).  ND_E_SHAPE, before any launch: a window that leaves the frame, a side above 2^24.  ND_E_BADARG: a null
+ * pointer, both or neither source, a non-positive size, B > 65535, bps not 8 or 16, full not 0 or 1, white outside (0, 65535], a black level
+ * outside [0, white], a scale_mul that is negative or not finite, an rgb_cam entry that is not finite.  Nothing allocates or synchronises. */
+typedef struct nd_develop_params {
+    int32_t black[4];       /* black_level_per_channel                                                                    */
+    int32_t white;          /* the white point of the packed values (16383)                                               */
+    float scale_mul[4];     /* fl32((double)pre[c] * 65535.0 / maximum), pre = the camera multipliers over their smallest */
+    float rgb_cam[9];       /* camera to sRGB, row-major 3 x 3                                                            */
+    int32_t x0, y0;         /* window origin in packed pixels                                                             */
+    int32_t bps;            /* 8 or 16                                                                                    */
+    int32_t full;           /* 0: half size; 1: full resolution, bilinear                                                 */
+} nd_develop_params;
+int nd_raw_develop(const float* src_f32, const uint16_t* src_u16, int B, int H, int W, const nd_develop_params* params, const uint16_t* curve,
+                   void* out, int h, int w, void* stream);
 /* (cout, cin) row-major (Linear / 1x1 conv weight) -> [cinP/4][coutP][4]; `unshuffle_c` > 0
  * permutes K from (c p1 p2) to (p1 p2 c) for a pixel-unshuffled input with c = unshuffle_c. */
 int64_t nd_pack_pointwise_weight_floats(int cin, int cout);

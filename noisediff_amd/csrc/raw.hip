@@ -23,6 +23,7 @@
 #pragma clang fp contract(off)
 
 #include "philox_poisson.h"
+#include "raw_codes.h"
 
 namespace {
 
@@ -31,31 +32,6 @@ constexpr uint32_t RW_NORMAL_BLOCK = 32u;           // the Philox block of the n
 static_assert(RW_NORMAL_BLOCK == PO_MAX_ATTEMPTS / 2, "the normal draw takes the first block the Poisson draw cannot reach");
 
 
-// 2 V codes from p (4-byte aligned at least) as V words: the even Bayer column in the low half, the odd one in the high half
-template <int V>
-__device__ __forceinline__ void rw_load_pairs(const uint16_t* p, uint32_t (&r)[V]) {
-    static_assert(V == 1 || V == 2 || V == 4, "one, two or four packed columns per thread");
-    const uintptr_t a = (uintptr_t)p;
-    if constexpr (V == 4) {
-        if ((a & 15u) == 0) {
-            const uint4 t = *reinterpret_cast<const uint4*>(p);
-            r[0] = t.x;  r[1] = t.y;  r[2] = t.z;  r[3] = t.w;
-            return;
-        }
-    }
-    if constexpr (V >= 2) {
-        if ((a & 7u) == 0) {
-#pragma unroll
-            for (int i = 0; i < V; i += 2) {
-                const uint2 t = *reinterpret_cast<const uint2*>(p + 2 * i);
-                r[i] = t.x;  r[i + 1] = t.y;
-            }
-            return;
-        }
-    }
-#pragma unroll
-    for (int i = 0; i < V; ++i) r[i] = *reinterpret_cast<const uint32_t*>(p + 2 * i);
-}
 template <int V>
 __device__ __forceinline__ void rw_store_pairs(uint16_t* p, const uint32_t (&r)[V]) {      // p is 4 V-byte aligned: checked on the host
     if constexpr (V == 4) *reinterpret_cast<uint4*>(p) = uint4{r[0], r[1], r[2], r[3]};
@@ -281,13 +257,6 @@ struct BayerArgs {
     int bl[4];
     int white, h, w;
 };
-
-__device__ __forceinline__ uint32_t rw_to_code(float x, int bl, int white) {
-    if (!(x == x)) return 0u;
-    const float p = x < 0.0f ? 0.0f : (x > 1.0f ? 1.0f : x);
-    const double t = (double)p * (double)(white - bl) + (double)bl;
-    return (uint32_t)t;
-}
 
 // Thread i of block row blockIdx.y = image b takes packed columns V (i mod (w / V)) .. + V - 1 of packed row i / (w / V): 2 x 2V codes.
 template <int V>
