@@ -65,7 +65,9 @@ def test_wgrad_is_bitwise_repeatable_and_matches_a_float64_sum(shape, form, wgra
     """nd_conv3x3_wgrad_nhwc_f32 in each of its forms -- nine taps (any shape), the Winograd-domain F(4x4) kernel on four waves (H % 4 == 0, W % 16 == 0,
     channel counts % 16 == 0 -- d = 48's 48 / 96 / 80 / 112: half-empty last blocks --; down to a single tile group per workgroup, 1 / 2 / 3 groups: the three exits of its pipeline) and on eight waves
     (cout % 64 == 0 as well) -- against a float64 weight gradient; bitwise repeatable, bias gradient, argument checks.  A form that does not take the
-    shape leaves it to the next one, as the product does; the product's own choice (by the shape) is one of them."""
+    shape leaves it to the next one, as the product does; the product's own choice (by the shape) is one of them.  These shapes are layers of the networks; the
+    edge shapes of every form (second trips of the tile and reduce loops, interior tiles next to border tiles, every finisher, uneven group shares, guarded buffers)
+    and a bound derived from each form's own fp32 reference are in tests/test_wgrad_float64.py."""
     lib = L.load()
     wgrad_form(form)
     B, H, W, cin, cout = shape
