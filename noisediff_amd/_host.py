@@ -6,7 +6,7 @@ from __future__ import annotations
 
 import ctypes as C
 import functools
-from typing import Optional
+from typing import Callable, NamedTuple, Optional
 
 import torch
 
@@ -57,8 +57,7 @@ def conv3x3_takes(kernel: int, B: int, H: int, W: int, cin: int, cout: int, c0: 
                   map_blocked: bool = False, ldo: Optional[int] = None, splits: int = 1) -> bool:
     """Does the conv3x3 kernel ``kernel`` (L.CONV3X3_*) take a layer of these sizes?  The library's answer (nd_conv3x3_takes: the kernel's own shape checks, the
     only place its limits are written); ``splits`` > 1: its split-K entry.  Host code: needs the built library and no GPU."""
-    d = L.Conv3x3(B=B, H=H, W=W, cin=cin, cout=cout, ldo=cout if ldo is None else ldo)
-    d.src.c0, d.src.c1, d.src.ld0, d.src.ld1, d.src.mode, d.src.upsample, d.src.map_blocked = c0, c1, ld0, ld1, mode, int(upsample), int(map_blocked)
+    d = L.conv3x3(L.src(None, None, mode, c0, ld0, 0, c1, ld1, upsample=int(upsample), map_blocked=int(map_blocked)), None, None, None, B, H, W, cin, cout, ldo)
     return bool(L.load().nd_conv3x3_takes(kernel, C.byref(d), splits))
 
 
@@ -108,8 +107,7 @@ def conv3x3_wgrad_cat_takes(B: int, H: int, W: int, c0: int, c1: int, cout: int)
 def pointwise_takes(cin: int, cout: int, c1: int = 0, split: bool = False) -> bool:
     """Does nd_pointwise_gemm_nhwc_f32 (``split``: nd_pointwise_gemm_split_nhwc_f32) take a plain dense 1x1 / Linear layer of these widths, the last ``c1`` input
     channels from a second source?  One pixel: no limit of either entry depends on the pixel count."""
-    d = L.Pointwise(B=1, HW=1, W=1, cin=cin, cout=cout, ldo=cout)
-    d.src.c0, d.src.c1, d.src.ld0, d.src.ld1 = cin - c1, c1, cin - c1, c1
+    d = L.pointwise(L.src(None, None, L.PRO_NONE, cin - c1, cin - c1, 0, c1, c1), None, None, None, 1, 1, 1, cin, cout)
     return bool((L.load().nd_pointwise_gemm_split_takes if split else L.load().nd_pointwise_gemm_takes)(C.byref(d)))
 
 
@@ -128,7 +126,26 @@ def conv3x3_kind(B: int, H: int, W: int, cin: int, cout: int, c0: int, c1: int, 
     return "wino" if wino else "direct"
 
 
-CONV3X3_PACK = {"wino4": "nd_pack_conv3x3_wino4_weight", "wino2": "nd_pack_conv3x3_wino_weight", "wino": "nd_pack_conv3x3_wino_weight",
-                "direct": "nd_pack_conv3x3_weight"}
-CONV3X3_ENTRY = {"wino4": "nd_conv3x3_wino4_nhwc_f32", "wino2": "nd_conv3x3_wino2_nhwc_f32", "wino": "nd_conv3x3_wino_nhwc_f32",
-                 "direct": "nd_conv3x3_nhwc_f32"}
+class Conv3x3Kernel(NamedTuple):
+    """What the host knows of one conv3x3 kernel; CONV3X3 is keyed by conv3x3_kind's answer, which is engine.conv3x3_form's but for its "" (direct)."""
+    kernel: int                  # L.CONV3X3_*: the kernel nd_conv3x3_takes is asked about
+    entry: str
+    splitk: Optional[str]        # its split-K entry
+    pack: str                    # the weight packing; + "_floats": its size, + "_dgrad": the data gradient's, from the forward weight
+    slot: str                    # the suffix of the sampling engine's arena slot of that packing
+    tiling: Optional[int]        # the id bench.py reads from an op's meta; None: the library's nd_conv3x3_tiling_id of the shape
+    stat_slots: Callable         # (lib, B, H, W, cout) -> slots per sample of the statistics epilogue
+
+
+_direct_slots = lambda lib, B, H, W, cout: lib.nd_conv3x3_stat_slots(H, W, cout, B)
+_wino_slots = lambda lib, B, H, W, cout: lib.nd_conv3x3_wino_stat_slots(H, W)
+_wino4_slots = lambda lib, B, H, W, cout: lib.nd_conv3x3_wino4_stat_slots(H, W)
+CONV3X3 = {
+    "direct": Conv3x3Kernel(L.CONV3X3_DIRECT, "nd_conv3x3_nhwc_f32", None, "nd_pack_conv3x3_weight", ".weight", None, _direct_slots),
+    "wino": Conv3x3Kernel(L.CONV3X3_WINO, "nd_conv3x3_wino_nhwc_f32", None, "nd_pack_conv3x3_wino_weight", ".weight.wino", 9001, _wino_slots),
+    "wino2": Conv3x3Kernel(L.CONV3X3_WINO2, "nd_conv3x3_wino2_nhwc_f32", None, "nd_pack_conv3x3_wino_weight", ".weight.wino", 9002, _wino_slots),
+    "wino4": Conv3x3Kernel(L.CONV3X3_WINO4, "nd_conv3x3_wino4_nhwc_f32", "nd_conv3x3_wino4_splitk_nhwc_f32", "nd_pack_conv3x3_wino4_weight", ".weight.wino4", 9004,
+                           _wino4_slots),
+    "wino4_16": Conv3x3Kernel(L.CONV3X3_WINO4_16, "nd_conv3x3_wino4_16_nhwc_f32", "nd_conv3x3_wino4_16_splitk_nhwc_f32", "nd_pack_conv3x3_wino4_weight", ".weight.wino4",
+                              9016, _wino4_slots),
+}

@@ -345,5 +345,66 @@ def call(name: str, *args):
 
 
 def ptr(t) -> Optional[int]:
-    """Device pointer of a torch tensor (None -> NULL)."""
-    return None if t is None else t.data_ptr()
+    """Device address of an operand: None (NULL), an integer address, or anything with data_ptr() (a torch tensor)."""
+    return t if t is None or isinstance(t, int) else t.data_ptr()
+
+
+# ---- launch descriptors, each filled in ONE place.  Operands are what ptr() takes; a width that is not given is the operand's last dimension.  The structs hold raw
+# addresses only, so every builder hangs the operands it was given on the struct (``_refs``; a struct built from a source carries that source's along): whoever holds
+# a descriptor holds its operands.  Positional parameters and plain assignments, no keyword dictionaries: a training step builds several hundred of these.
+def src(t, t2=None, mode: int = PRO_NONE, c: Optional[int] = None, ld: Optional[int] = None, offset: int = 0, c1: Optional[int] = None, ld1: Optional[int] = None,
+        mad=None, map=None, vec=None, gamma=None, beta=None, rowstats=None, upsample: int = 0, unshuffle: int = 0, map_blocked: int = 0) -> Src:
+    """An nd_src: ``c`` channels of ``t`` at a pixel stride of ``ld`` from element ``offset`` on, then (``t2``) ``c1`` channels of a second source at ``ld1``."""
+    s = Src()
+    s.p0 = ptr(t) + 4 * offset if offset else ptr(t)
+    s.c0, s.ld0, s.mode = t.shape[-1] if c is None else c, t.shape[-1] if ld is None else ld, mode
+    if t2 is not None:
+        s.p1, s.c1, s.ld1 = ptr(t2), t2.shape[-1] if c1 is None else c1, t2.shape[-1] if ld1 is None else ld1
+    elif c1 or ld1:                      # widths without addresses: a question to nd_*_takes
+        s.c1, s.ld1 = c1 or 0, ld1 or 0
+    if upsample or unshuffle or map_blocked:         # (a new struct is all zeros: the common plain source sets nothing more)
+        s.upsample, s.unshuffle, s.map_blocked = upsample, unshuffle, map_blocked
+    if not (mad is None and map is None and vec is None and gamma is None and beta is None and rowstats is None):
+        s.mad, s.map, s.vec, s.gamma, s.beta, s.rowstats = ptr(mad), ptr(map), ptr(vec), ptr(gamma), ptr(beta), ptr(rowstats)
+    s._refs = (t, t2, mad, map, vec, gamma, beta, rowstats)
+    return s
+
+
+def src_rows(s: Src, b0: int, pixels: int, map_width: int = 0) -> Src:
+    """A copy of ``s`` that starts at sample ``b0``: every per-sample operand it has (p0, p1, mad, map, vec) moved by its own stride.  ``pixels``: the source's
+    pixels per sample (a quarter of the output's behind ``upsample``); ``map_width``: the map's floats per pixel, 2 (c0 + c1) stored, fewer where the kernel forms it."""
+    r = Src.from_buffer_copy(s)
+    r._refs = getattr(s, "_refs", ())
+    for name, step in (("p0", pixels * s.ld0), ("p1", pixels * s.ld1), ("mad", 3 * (s.c0 + s.c1)), ("map", pixels * map_width), ("vec", s.c0 + s.c1)) if b0 else ():
+        if getattr(s, name):
+            setattr(r, name, getattr(s, name) + 4 * b0 * step)
+    return r
+
+
+def conv3x3(s: Src, weight, bias, out, B: int, H: int, W: int, cin: int, cout: int, ldo: Optional[int] = None, stats=None, slot_count=None) -> Conv3x3:
+    """An nd_conv3x3 over the source ``s``; ``stats`` with ``slot_count``: the statistics epilogue's two outputs."""
+    d = Conv3x3()
+    d.src, d.weight, d.bias, d.out = s, ptr(weight), ptr(bias), ptr(out)
+    if stats is not None:
+        d.stats, d.slot_count = ptr(stats), ptr(slot_count)
+    d.B, d.H, d.W, d.cin, d.cout, d.ldo = B, H, W, cin, cout, cout if ldo is None else ldo
+    d._refs = (getattr(s, "_refs", ()), weight, bias, out, stats, slot_count)
+    return d
+
+
+def pointwise(s: Src, weight, bias, out, B: int, HW: int, W: int, cin: int, cout: int, ldo: Optional[int] = None, act: int = ACT_NONE, res0=None, res1=None, vec=None,
+              gn_t=None, gn_mad=None, shuffle=None, ldr0: Optional[int] = None, ldr1: Optional[int] = None, ldt: Optional[int] = None) -> Pointwise:
+    """An nd_pointwise over the source ``s``; ``gn_t`` with ``gn_mad``: silu(GroupNorm(gn_t)) added in the epilogue; ``shuffle`` = (c, h, w): the pixel-shuffled store."""
+    d = Pointwise()
+    d.src, d.weight, d.bias, d.out, d.vec = s, ptr(weight), ptr(bias), ptr(out), ptr(vec)
+    d.B, d.HW, d.W, d.cin, d.cout, d.ldo, d.act = B, HW, W, cin, cout, cout if ldo is None else ldo, act
+    if res0 is not None:
+        d.res0, d.ldr0 = ptr(res0), res0.shape[-1] if ldr0 is None else ldr0
+    if res1 is not None:
+        d.res1, d.ldr1 = ptr(res1), res1.shape[-1] if ldr1 is None else ldr1
+    if gn_t is not None:
+        d.gn_t, d.ldt, d.gn_mad = ptr(gn_t), gn_t.shape[-1] if ldt is None else ldt, ptr(gn_mad)
+    if shuffle is not None:
+        d.shuffle_c, d.shuffle_h, d.shuffle_w = shuffle
+    d._refs = (getattr(s, "_refs", ()), weight, bias, out, res0, res1, vec, gn_t, gn_mad)
+    return d

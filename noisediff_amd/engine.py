@@ -30,7 +30,7 @@ from typing import Callable, Dict, List, Optional, Sequence, Tuple
 import torch
 
 from . import _lib as L
-from ._host import chain_takes, conv3x3_takes, pointwise_takes
+from ._host import CONV3X3, chain_takes, conv3x3_takes, pointwise_takes
 from .spec import (normalize_stage_attn, stage_attention_param_spec, ATTN_DIM_HEAD, ATTN_HEADS, ISO_DIM, ISO_TABLE_ROWS, POS_DIM, POS_GROUPS, RESNET_GROUPS, SHOT_GROUPS,
                    arch_param_spec, arch_traits, attention_param_spec, stage_dims)
 
@@ -134,13 +134,13 @@ def conv3x3_form(B: int, H: int, W: int, cin: int, cout: int, c0: int, c1: int, 
     if rows and form == "wino4_16" and k_16split:     # few items per sample: K ranges by the SAMPLE's geometry (the batch never enters: a sample's bits stay batch-invariant)
         splits = int(L.load().nd_conv3x3_wino4_16_splitk_plan(H, W, cin, cout))
     if splits > 1:                                   # the partial sums of a launch stay below 2 GiB: smaller pieces, never another kernel
-        rows = piece(_FORM_KERNEL[form], splits)
+        rows = piece(CONV3X3[form].kernel, splits)
     if rows:
         return form, splits, rows
     # both F(2x2) kernels share weights, statistics slots and descriptor; wino2 (one resident wave per SIMD, all 16 position accumulators in registers) is the
     # default, wino covers what it does not take, the direct kernel what neither does
     for form in ("wino2", "wino") if k_wino2 else ("wino",):
-        rows = piece(_FORM_KERNEL[form], mode=stored)
+        rows = piece(CONV3X3[form].kernel, mode=stored)
         if rows:
             return form, 1, rows
     return "", 1, B
@@ -149,7 +149,6 @@ def conv3x3_form(B: int, H: int, W: int, cin: int, cout: int, c0: int, c1: int, 
 # Policy, not a kernel's limit (the F(4x4) entries take outputs up to 4 GiB): one launch writes less than 2 GiB.  The rule this function replaced held every
 # piece to the split-K partial-sum bound at ONE range too; kept, so that no layer's launches change.
 _LAUNCH_OUT_BYTES = 2 * 1024 ** 3
-_FORM_KERNEL = {"": L.CONV3X3_DIRECT, "wino": L.CONV3X3_WINO, "wino2": L.CONV3X3_WINO2, "wino4": L.CONV3X3_WINO4, "wino4_16": L.CONV3X3_WINO4_16}
 _MAP_PRODUCERS = ("pos_block1.mlp.1.weight", "pos_block2.mlp.1.weight")
 
 
@@ -604,16 +603,6 @@ class Plan:
         self._keep.append(args)
         self._ops.append((fn, args, name, meta))
 
-    def _src(self, t: torch.Tensor, t2: Optional[torch.Tensor] = None, mode=L.PRO_NONE, **kw) -> L.Src:
-        s = L.Src()
-        s.p0, s.c0, s.ld0 = t.data_ptr(), t.shape[-1], t.shape[-1]
-        if t2 is not None:
-            s.p1, s.c1, s.ld1 = t2.data_ptr(), t2.shape[-1], t2.shape[-1]
-        s.mode = mode
-        for k, v in kw.items():
-            setattr(s, k, v.data_ptr() if isinstance(v, torch.Tensor) else v)
-        return s
-
     def conv3(self, name: str, src: L.Src, cin: int, cout: int, H: int, W: int, stats: bool):
         """nn.Conv2d(cin, cout, 3, padding=1); returns (out, stats, slot_count, slots)."""
         e = self.e
@@ -621,7 +610,7 @@ class Plan:
         up = 1 if src.upsample else 0
         # the kernel form, the K ranges of its split-K entry and the rows per launch (the whole batch at the bench sizes)
         form, splits, rows = conv3x3_form(self.B, H, W, cin, cout, src.c0, src.c1, src.ld0, src.ld1, src.mode, bool(src.upsample), (name + ".weight.wino4") in e.slots)
-        wino, wino2, wino4 = form != "", form == "wino2", form.startswith("wino4")
+        k, wino, wino4 = CONV3X3[form or "direct"], form != "", form.startswith("wino4")
         if src.mode == L.PRO_AFFINE_GENMAP_SILU and form != "wino4":
             raise L.HipError(f"{name}: maps formed in the kernel need conv3x3_wino4's 16 x 32-region form (Plan.posgen decides by the same rule)")
         if wino and not wino4 and (name + ".weight.wino4") in e.slots and src.mode in (L.PRO_NONE, L.PRO_AFFINE_SILU, L.PRO_AFFINE_MAP_SILU) and not _few_items(H, W, cout):
@@ -629,40 +618,26 @@ class Plan:
         st = sc = None
         slots = 0
         if stats:     # per-(slot, channel) {sum, M2} partials for nd_groupnorm_finalize_f32: F(4x4) one slot per 16 x 16 tile, F(2x2) two
-            slots = (e.lib.nd_conv3x3_wino4_stat_slots(H, W) if wino4 else e.lib.nd_conv3x3_wino_stat_slots(H, W) if wino
-                     else e.lib.nd_conv3x3_stat_slots(H, W, cout, self.B))
+            slots = k.stat_slots(e.lib, self.B, H, W, cout)
             st = self._alloc(self.B, slots, cout, 2)
             sc = self._alloc(slots)
         if src.map_blocked and not wino4:
             raise L.HipError(f"{name}: the scale / shift map was produced in the blocked layout but the layer does not run on conv3x3_wino4")
         # ONE packing of the weight is read (and marked for the weight broadcast): F(4x4), F(2x2) or the direct form
-        weight = e.p(name + (".weight.wino4" if wino4 else ".weight.wino" if wino else ".weight"))
-        entry = f"nd_conv3x3_{form}_nhwc_f32" if form else "nd_conv3x3_nhwc_f32"
-        tiling = (9016 if form == "wino4_16" else 9004) if wino4 else 9002 if wino2 else 9001 if wino else e.lib.nd_conv3x3_tiling_id(self.B, H, W, cout)
+        weight = e.p(name + k.slot)
+        tiling = e.lib.nd_conv3x3_tiling_id(self.B, H, W, cout) if k.tiling is None else k.tiling
         ws = self._alloc(splits * rows * H * W * cout) if splits > 1 else None
-        sh, sw, ctot = H >> up, W >> up, src.c0 + src.c1
+        map_width = POS_DIM if src.mode == L.PRO_AFFINE_GENMAP_SILU else 2 * (src.c0 + src.c1)
         for b0 in range(0, self.B, rows):                # one launch per piece of `rows` samples (one piece at the bench sizes)
             nb = min(rows, self.B - b0)
-            d = L.Conv3x3()
-            s = L.Src.from_buffer_copy(src)
-            if b0:                                       # the piece's rows of every per-sample operand
-                s.p0 = src.p0 + 4 * b0 * sh * sw * src.ld0
-                if src.p1:
-                    s.p1 = src.p1 + 4 * b0 * sh * sw * src.ld1
-                if src.mad:
-                    s.mad = src.mad + 4 * b0 * 3 * ctot
-                if src.map:
-                    s.map = src.map + 4 * b0 * H * W * (POS_DIM if src.mode == L.PRO_AFFINE_GENMAP_SILU else 2 * ctot)
-            d.src, d.weight, d.bias, d.out = s, weight, e.p(name + ".bias"), out.data_ptr() + 4 * b0 * H * W * cout
-            d.B, d.H, d.W, d.cin, d.cout, d.ldo = nb, H, W, cin, cout, cout
-            if stats:
-                d.stats, d.slot_count = st.data_ptr() + 4 * b0 * slots * cout * 2, sc.data_ptr()
+            d = L.conv3x3(L.src_rows(src, b0, (H >> up) * (W >> up), map_width), weight, e.p(name + ".bias"), out.data_ptr() + 4 * b0 * H * W * cout, nb, H, W, cin, cout,
+                          stats=st.data_ptr() + 4 * b0 * slots * cout * 2 if stats else None, slot_count=sc if stats else None)
             meta = {"layer": name, "B": nb, "H": H, "W": W, "cin": cin, "cout": cout, "mode": int(src.mode), "tiling": tiling}
             if splits > 1:
                 meta["splits"] = splits
-                self._add(f"nd_conv3x3_{form}_splitk_nhwc_f32", C.byref(d), ws.data_ptr(), splits, e.stream, meta=meta)
+                self._add(k.splitk, C.byref(d), ws.data_ptr(), splits, e.stream, meta=meta)
             else:
-                self._add(entry, C.byref(d), e.stream, meta=meta)
+                self._add(k.entry, C.byref(d), e.stream, meta=meta)
             self._keep.append(d)
         if ws is not None:
             self._release(ws)
@@ -674,21 +649,11 @@ class Plan:
         e = self.e
         if out is None:
             out = self._alloc(self.B, HW, cout)
-        d = L.Pointwise()
-        d.src, d.out = src, out.data_ptr()
-        d.bias = e.p(name + ".bias" + variant) if bias else None
-        d.B, d.HW, d.W, d.cin, d.cout, d.ldo, d.act = self.B, HW, W, cin, cout, cout, act
+        d = L.pointwise(src, None, e.p(name + ".bias" + variant) if bias else None, out, self.B, HW, W, cin, cout, act=act, res0=res0, res1=res1, vec=vec,
+                        gn_t=gn_t, gn_mad=gn_mad)
         # wide layers: the split-product kernel on the bf16 matrix cores (a function of the layer's shape alone, never of the batch)
         split = not variant and (name + ".weight.split") in e.slots and bool(e.lib.nd_pointwise_gemm_split_takes(C.byref(d)))
         d.weight = e.p(name + (".weight.split" if split else ".weight" + variant))
-        if res0 is not None:
-            d.res0, d.ldr0 = res0.data_ptr(), res0.shape[-1]
-        if res1 is not None:
-            d.res1, d.ldr1 = res1.data_ptr(), res1.shape[-1]
-        if vec is not None:
-            d.vec = vec.data_ptr()
-        if gn_t is not None:
-            d.gn_t, d.ldt, d.gn_mad = gn_t.data_ptr(), gn_t.shape[-1], gn_mad.data_ptr()
         self._add("nd_pointwise_gemm_split_nhwc_f32" if split else "nd_pointwise_gemm_nhwc_f32", C.byref(d), e.stream,
                   meta={"layer": name, "B": self.B, "HW": HW, "cin": cin, "cout": cout, "split": int(split)})
         self._keep.append(d)
@@ -713,7 +678,7 @@ class Plan:
         (c2, mad2) -- the block's output is silu((c2 - M) A + D) + its shortcut, formed by the caller's fused consumer."""
         cin = x.shape[-1] + (skip.shape[-1] if skip is not None else 0)
         HW = H * W
-        c1, st1, sc1, n1 = self.conv3(name + ".block1.proj", self._src(x, skip), cin, cout, H, W, stats=True)
+        c1, st1, sc1, n1 = self.conv3(name + ".block1.proj", L.src(x, skip), cin, cout, H, W, stats=True)
         ss_off = None if posmap is not None else self.e.tproj_off.get(name)     # blocks built with time_emb_dim=None have no mlp
         mad1 = self.gn_finalize(st1, sc1, n1, name + ".block1.norm", cout, groups, ss_off)
         a1 = None
@@ -724,14 +689,14 @@ class Plan:
             self._add("nd_affine_silu_add_f32", c1.data_ptr(), cout, mad1.data_ptr(), None, cout, None, cout, a1.data_ptr(), cout,
                       self.B, HW, cout, self.e.stream,
                       meta={"layer": name + ".block1.act", "stream_bytes": 4.0 * self.B * HW * cout * 2})
-            src2 = self._src(a1)
+            src2 = L.src(a1)
         else:
             if posmap is not None and self.posgen:           # scale | shift formed in the kernel from silu(pos_emb) and this block's mlp[1]
-                src2 = self._src(c1, None, L.PRO_AFFINE_GENMAP_SILU, mad=mad1, map=self.pos_e, gamma=self.e.p(name + ".mlp.1.weight.gen"),
+                src2 = L.src(c1, None, L.PRO_AFFINE_GENMAP_SILU, mad=mad1, map=self.pos_e, gamma=self.e.p(name + ".mlp.1.weight.gen"),
                                  beta=self.e.p(name + ".mlp.1.bias"))
             else:
                 mode = L.PRO_AFFINE_MAP_SILU if posmap is not None else L.PRO_AFFINE_SILU
-                src2 = self._src(c1, None, mode, mad=mad1, **({"map": posmap, "map_blocked": int(self.posmap_blocked)} if posmap is not None else {}))
+                src2 = L.src(c1, None, mode, mad=mad1, **({"map": posmap, "map_blocked": int(self.posmap_blocked)} if posmap is not None else {}))
         c2, st2, sc2, n2 = self.conv3(name + ".block2.proj", src2, cout, cout, H, W, stats=True)
         if a1 is not None:
             self._release(a1)
@@ -741,7 +706,7 @@ class Plan:
             return c2, mad2
         if cin != cout:       # h + res_conv(x): the 1x1 GEMM adds silu(GN(c2)) in its epilogue   :170
             assert extra_res is None
-            out = self.pw(name + ".res_conv", self._src(x, skip), cin, cout, HW, W, gn_t=c2, gn_mad=mad2)
+            out = self.pw(name + ".res_conv", L.src(x, skip), cin, cout, HW, W, gn_t=c2, gn_mad=mad2)
         else:
             assert skip is None
             out = self._alloc(self.B, HW, cout)
@@ -772,14 +737,7 @@ class Plan:
         for b0 in range(0, self.B, rows):
             nb = min(rows, self.B - b0)
             d = L.Chain()
-            sp = L.Src.from_buffer_copy(src)
-            if b0:
-                sp.p0 = src.p0 + 4 * b0 * HW * src.ld0
-                if src.p1:
-                    sp.p1 = src.p1 + 4 * b0 * HW * src.ld1
-                if src.vec:
-                    sp.vec = src.vec + 4 * b0 * (src.c0 + src.c1)
-            d.src, d.out, d.n_stages, d.B, d.HW, d.ldo = sp, out.data_ptr() + 4 * b0 * HW * ldo, len(stages), nb, HW, ldo
+            d.src, d.out, d.n_stages, d.B, d.HW, d.ldo = L.src_rows(src, b0, HW), out.data_ptr() + 4 * b0 * HW * ldo, len(stages), nb, HW, ldo
             for i, (layer, cin, cout, act, res) in enumerate(stages):
                 d.st[i].weight, d.st[i].bias = e.p(layer + (".weight.chain_s" if split else ".weight.chain")), e.p(layer + ".bias")
                 d.st[i].cin, d.st[i].cout, d.st[i].act, d.st[i].res = cin, cout, act, res
@@ -807,7 +765,7 @@ class Plan:
         Cc, HW = x.shape[-1], H * W
         cb = self.cb[name]
         if self._chain_ok(HW, (Cc, 2 * Cc, Cc, Cc)):
-            ln = self._src(x, None, L.PRO_LAYERNORM, vec=cb, gamma=self.e.p(name + ".norm2.weight"), beta=self.e.p(name + ".norm2.bias"))
+            ln = L.src(x, None, L.PRO_LAYERNORM, vec=cb, gamma=self.e.p(name + ".norm2.weight"), beta=self.e.p(name + ".norm2.bias"))
             y = self.chain(name + ".ff+proj_out", ln,
                            [(name + ".ff.net.0.0", Cc, 2 * Cc, L.ACT_GELU, L.CHAIN_RES_NONE),
                             (name + ".ff.net.2", 2 * Cc, Cc, L.ACT_NONE, L.CHAIN_RES_INPUT),
@@ -819,10 +777,10 @@ class Plan:
             rs = self._alloc(self.B, HW, 2)
             self._add("nd_layernorm_stats_f32", x.data_ptr(), Cc, cb.data_ptr(), rs.data_ptr(), self.B, HW, Cc, 1e-5, self.e.stream)
             kw["rowstats"] = rs
-        ln = self._src(x, None, L.PRO_LAYERNORM, vec=cb, gamma=self.e.p(name + ".norm2.weight"), beta=self.e.p(name + ".norm2.bias"), **kw)
+        ln = L.src(x, None, L.PRO_LAYERNORM, vec=cb, gamma=self.e.p(name + ".norm2.weight"), beta=self.e.p(name + ".norm2.bias"), **kw)
         h1 = self.pw(name + ".ff.net.0.0", ln, Cc, 2 * Cc, HW, W, act=L.ACT_GELU)
-        x2 = self.pw(name + ".ff.net.2", self._src(h1), 2 * Cc, Cc, HW, W, res0=x, vec=cb)
-        y = self.pw(name + ".proj_out", self._src(x2), Cc, Cc, HW, W, res0=x)
+        x2 = self.pw(name + ".ff.net.2", L.src(h1), 2 * Cc, Cc, HW, W, res0=x, vec=cb)
+        y = self.pw(name + ".proj_out", L.src(x2), Cc, Cc, HW, W, res0=x)
         self._release(h1, x2)
         if rs is not None:
             self._release(rs)
@@ -834,7 +792,7 @@ class Plan:
                                        (name + ".fc2", hid, cout, L.ACT_NONE, L.CHAIN_RES_NONE)], H * W)
             return o.view(self.B, H, W, cout)
         h = self.pw(name + ".fc1", src, cin, hid, H * W, W, act=L.ACT_GELU)
-        o = self.pw(name + ".fc2", self._src(h), hid, cout, H * W, W, res0=res0)
+        o = self.pw(name + ".fc2", L.src(h), hid, cout, H * W, W, res0=res0)
         self._release(h)
         return o.view(self.B, H, W, cout)
 
@@ -846,13 +804,13 @@ class Plan:
             pe = self._alloc(B, H, W, 3 * POS_DIM)
             self._add("nd_pos_enc_f32", self.position.data_ptr(), e.p("pos_enc.weights.weight"), e.p("pos_enc.weights.bias"),
                       pe.data_ptr(), B, H, W, POS_DIM, st)
-            h = self.pw("pos_mlp.fc1", self._src(pe), 3 * POS_DIM, 2 * POS_DIM, H * W, W, act=L.ACT_GELU)
-            self.pw("pos_mlp.fc2", self._src(h), 2 * POS_DIM, POS_DIM, H * W, W, out=self.pos_emb)
+            h = self.pw("pos_mlp.fc1", L.src(pe), 3 * POS_DIM, 2 * POS_DIM, H * W, W, act=L.ACT_GELU)
+            self.pw("pos_mlp.fc2", L.src(h), 2 * POS_DIM, POS_DIM, H * W, W, out=self.pos_emb)
             if self.posgen:                                  # the maps are formed by their consumers: only the activation is shared work
                 self._add("nd_affine_silu_add_f32", self.pos_emb.data_ptr(), POS_DIM, self.pos_e_mad.data_ptr(), None, POS_DIM, None, POS_DIM,
                           self.pos_e.data_ptr(), POS_DIM, B, H * W, POS_DIM, st, meta={"layer": "pos_emb.silu", "stream_bytes": 8.0 * B * H * W * POS_DIM})
             for blk, dst in (() if self.posgen else (("pos_block1", self.posmap1), ("pos_block2", self.posmap2))):
-                self.pw(blk + ".mlp.1", self._src(self.pos_emb, None, L.PRO_SILU), POS_DIM, 2 * e.dim, H * W, W, out=dst,
+                self.pw(blk + ".mlp.1", L.src(self.pos_emb, None, L.PRO_SILU), POS_DIM, 2 * e.dim, H * W, W, out=dst,
                         variant=".blk16" if self.posmap_blocked else "")
             self._release(pe, h)
         if tr.iso_attn:
@@ -900,21 +858,21 @@ class Plan:
         shot_noise = None
         if tr.shot_branch:
             # ---- shot-noise branch, full resolution (:598-604)
-            r_shot = self.mlp("shot_mlp1", self._src(self.clean, self.x), 2 * e.inp_dim, d, d, H, W)
+            r_shot = self.mlp("shot_mlp1", L.src(self.clean, self.x), 2 * e.inp_dim, d, d, H, W)
             s = self.attn_block("shot_attn", r_shot, H, W)
-            s2 = self.mlp("shot_mlp2", self._src(s), d, d, d, H, W)
+            s2 = self.mlp("shot_mlp2", L.src(s), d, d, d, H, W)
             if (SHOT_TAIL and not self.debug and SPLIT_CHAIN and self._chain_ok(H * W, (d, d, e.inp_dim)) and e.lib.nd_pointwise_chain_tail_takes(d, d, e.inp_dim, 0)
                     and all(n + ".weight.chain_s" in e.slots for n in ("shot_mlp3.fc1", "shot_mlp3.fc2"))):
                 # shot_mlp3(shot_time(s2) + r): the block's tail is the chain's prologue -- no s3
                 c2, mad2 = self.resnet("shot_time", s2, None, d, H, W, SHOT_GROUPS, tail=False)
-                shot_noise = self.chain("shot_time.tail+shot_mlp3", self._src(c2), [("shot_mlp3.fc1", d, d, L.ACT_GELU, L.CHAIN_RES_NONE),
+                shot_noise = self.chain("shot_time.tail+shot_mlp3", L.src(c2), [("shot_mlp3.fc1", d, d, L.ACT_GELU, L.CHAIN_RES_NONE),
                                                                                    ("shot_mlp3.fc2", d, e.inp_dim, L.ACT_NONE, L.CHAIN_RES_NONE)], H * W,
                                         tail=(mad2, s2, r_shot)).view(B, H, W, e.inp_dim)
                 self._release(r_shot, s, s2, c2, mad2)
                 s3 = None
             else:
                 s3 = self.resnet("shot_time", s2, None, d, H, W, SHOT_GROUPS, extra_res=r_shot)   # shot_time(...) + r
-                shot_noise = self._tap("shot_noise", self.mlp("shot_mlp3", self._src(s3), d, d, e.inp_dim, H, W))
+                shot_noise = self._tap("shot_noise", self.mlp("shot_mlp3", L.src(s3), d, d, e.inp_dim, H, W))
             if s3 is not None:
                 for nm, tt in (("shot_mlp1", r_shot), ("shot_attn", s), ("shot_mlp2", s2), ("shot_time", s3)):
                     self._tap(nm, tt)
@@ -927,7 +885,7 @@ class Plan:
         self._tap("init_conv", x0)
         xin = x0
         if tr.cond_branch:          # x = cond_concat_conv(cat[init_conv(x), clean_emb])   others_arch.py:495-498
-            xin, *_ = self.conv3("cond_concat_conv", self._src(x0, self.clean_emb), 2 * d, d, H, W, stats=False)
+            xin, *_ = self.conv3("cond_concat_conv", L.src(x0, self.clean_emb), 2 * d, d, H, W, stats=False)
             self._tap("cond_concat", xin)
         pm1, pm2 = ((self.pos_e, self.pos_e) if self.posgen else (self.posmap1, self.posmap2)) if tr.position else (None, None)   # else plain ResnetBlocks without time
         x = self._tap("pos_block1", self.resnet("pos_block1", xin, None, d, H, W, POS_GROUPS, posmap=pm1))
@@ -947,10 +905,10 @@ class Plan:
             xa = self.attn_block(p + ".2", x2, h, w) if tr.iso_attn else x2
             self._tap(p + ".0", x1); self._tap(p + ".1", x2); self._tap(p + ".2", xa)
             if i == 3:
-                x, *_ = self.conv3(f"{p}.{rs}", self._src(xa), cin, cout, h, w, stats=False)
+                x, *_ = self.conv3(f"{p}.{rs}", L.src(xa), cin, cout, h, w, stats=False)
             else:
                 h, w = h // 2, w // 2
-                x = self.pw(f"{p}.{rs}.1", self._src(xa, None, L.PRO_NONE, unshuffle=1, c0=4 * cin, ld0=cin), 4 * cin, cout,
+                x = self.pw(f"{p}.{rs}.1", L.src(xa, None, L.PRO_NONE, 4 * cin, cin, unshuffle=1), 4 * cin, cout,
                             h * w, w).view(B, h, w, cout)
             if xa is not x2:
                 self._release(xa)
@@ -976,10 +934,10 @@ class Plan:
             if xa is not x2:
                 self._release(x2)
             if i == 3:
-                x, *_ = self.conv3(f"{p}.{rs}", self._src(xa), cout, cin, h, w, stats=False)
+                x, *_ = self.conv3(f"{p}.{rs}", L.src(xa), cout, cin, h, w, stats=False)
             else:
                 h, w = h * 2, w * 2
-                x, *_ = self.conv3(f"{p}.{rs}.1", self._src(xa, None, L.PRO_NONE, upsample=1), cout, cin, h, w, stats=False)
+                x, *_ = self.conv3(f"{p}.{rs}.1", L.src(xa, None, L.PRO_NONE, upsample=1), cout, cin, h, w, stats=False)
             self._release(xa)
             self._tap(p + ".0", x1); self._tap(p + ".1", x2); self._tap(p + ".2", xa); self._tap(f"up{i}", x)
         xp = self._tap("pos_block2", self.resnet("pos_block2", x, None, d, H, W, POS_GROUPS, posmap=pm2))
@@ -1003,7 +961,7 @@ class Plan:
         xf = self._tap("final_res_block", self.resnet("final_res_block", xp, x0, d, H, W, G))
         self._release(xp, x0)
         # NoiseDiffNet: shot + read (:644); the ablation nets return final_conv(x) alone
-        self.pw("final_conv", self._src(xf), d, e.inp_dim, H * W, W, res0=shot_noise, out=self.model_out)
+        self.pw("final_conv", L.src(xf), d, e.inp_dim, H * W, W, res0=shot_noise, out=self.model_out)
         self._release(xf)
         if shot_noise is not None:
             self._release(shot_noise)
@@ -1014,10 +972,10 @@ class Plan:
         hid = ATTN_HEADS * ATTN_DIM_HEAD
         xn = self._alloc(B, N, Cc)
         self._add("nd_rmsnorm_nhwc_f32", x.data_ptr(), Cc, e.p(prefix + ".norm.g"), xn.data_ptr(), Cc, B, N, Cc, e.stream)
-        qkv = self.pw(prefix + ".to_qkv", self._src(xn), Cc, 3 * hid, N, w, bias=False)
+        qkv = self.pw(prefix + ".to_qkv", L.src(xn), Cc, 3 * hid, N, w, bias=False)
         att = self._alloc(B, N, hid)
         self._add("nd_attention_mfma_f32", qkv.data_ptr(), 3 * hid, att.data_ptr(), hid, B, N, ATTN_HEADS, ATTN_DIM_HEAD, e.stream)
-        y = self.pw(prefix + ".to_out", self._src(att), hid, Cc, N, w, res0=x)
+        y = self.pw(prefix + ".to_out", L.src(att), hid, Cc, N, w, res0=x)
         self._release(xn, qkv, att, x)
         return y.view(B, h, w, Cc)
 
@@ -1031,11 +989,11 @@ class Plan:
         hid = ATTN_HEADS * ATTN_DIM_HEAD
         xn = self._alloc(B, N, Cc)
         self._add("nd_rmsnorm_nhwc_f32", x.data_ptr(), Cc, e.p(prefix + ".norm.g"), xn.data_ptr(), Cc, B, N, Cc, e.stream)
-        qkv = self.pw(prefix + ".to_qkv", self._src(xn), Cc, 3 * hid, N, w, bias=False)
+        qkv = self.pw(prefix + ".to_qkv", L.src(xn), Cc, 3 * hid, N, w, bias=False)
         att = self._alloc(B, N, hid)
         ws = self._alloc(int(e.lib.nd_linear_attention_workspace_floats(B, N, ATTN_HEADS)))
         self._add("nd_linear_attention_f32", qkv.data_ptr(), 3 * hid, att.data_ptr(), hid, ws.data_ptr(), B, N, ATTN_HEADS, ATTN_DIM_HEAD, e.stream)
-        o = self.pw(prefix + ".to_out.0", self._src(att), hid, Cc, N, w)
+        o = self.pw(prefix + ".to_out.0", L.src(att), hid, Cc, N, w)
         y = self._alloc(B, N, Cc)
         self._add("nd_rmsnorm_add_nhwc_f32", o.data_ptr(), Cc, e.p(prefix + ".to_out.1.g"), x.data_ptr(), Cc, y.data_ptr(), Cc, B, N, Cc, e.stream)
         self._release(xn, qkv, att, ws, o, x)

@@ -23,7 +23,7 @@ from torch import nn
 from . import _lib as L
 from .net import _attach, _init
 from .spec import LSID_STAGES, lsid_param_spec
-from ._host import CONV3X3_ENTRY, CONV3X3_PACK, _stream, conv3x3_kind
+from ._host import CONV3X3, _stream, conv3x3_kind
 
 WINO4 = os.environ.get("ND_WINO4", "1") != "0"           # A-B knob: 0 = never the F(4x4,3x3) kernel
 
@@ -104,37 +104,18 @@ class _Launcher:
     def conv3x3(self, w_oihw: torch.Tensor, bias: Optional[torch.Tensor], src: L.Src, B: int, h: int, w: int, cin: int, cout: int,
                 dgrad: bool = False) -> torch.Tensor:
         """One 3x3 convolution (``dgrad``: the data gradient of the layer whose forward weight is ``w_oihw``; cin / cout are the operator's)."""
-        kind = conv3x3_kind(B, h, w, cin, cout, src.c0, src.c1, max(src.ld0, src.ld1), self.wino4)
-        pack = CONV3X3_PACK[kind]
-        wp = self.empty(int(getattr(self.lib, pack + "_floats")(cin, cout)))
-        self.pack(pack + ("_dgrad" if dgrad else ""), w_oihw.data_ptr(), wp.data_ptr(), cin, cout)
+        k = CONV3X3[conv3x3_kind(B, h, w, cin, cout, src.c0, src.c1, max(src.ld0, src.ld1), self.wino4)]
+        wp = self.empty(int(getattr(self.lib, k.pack + "_floats")(cin, cout)))
+        self.pack(k.pack + ("_dgrad" if dgrad else ""), w_oihw.data_ptr(), wp.data_ptr(), cin, cout)
         out = self.empty(B, h, w, cout)
-        d = L.Conv3x3()
-        d.src, d.weight, d.out = src, wp.data_ptr(), out.data_ptr()
-        d.bias = bias.data_ptr() if bias is not None else None
-        d.B, d.H, d.W, d.cin, d.cout, d.ldo = B, h, w, cin, cout, cout
+        d = L.conv3x3(src, wp, bias, out, B, h, w, cin, cout)
         self.keep.append(d)
-        self.launch(CONV3X3_ENTRY[kind], C.byref(d))
+        self.launch(k.entry, C.byref(d))
         return out
-
-    @staticmethod
-    def src(t: torch.Tensor, c: Optional[int] = None, ld: Optional[int] = None, t2: Optional[torch.Tensor] = None, mode: int = L.PRO_NONE,
-            offset: int = 0) -> L.Src:
-        s = L.Src()
-        s.p0, s.c0, s.ld0 = t.data_ptr() + 4 * offset, c or t.shape[-1], ld or t.shape[-1]
-        if t2 is not None:
-            s.p1, s.c1, s.ld1 = t2.data_ptr(), t2.shape[-1], t2.shape[-1]
-        s.mode = mode
-        return s
 
     def pointwise(self, src: L.Src, wp: torch.Tensor, bias: Optional[torch.Tensor], out: torch.Tensor, B: int, HW: int, W: int, cin: int, cout: int,
                   ldo: int, shuffle: Optional[Tuple[int, int, int]] = None, crop_src: Optional[Tuple[int, int]] = None) -> None:
-        d = L.Pointwise()
-        d.src, d.weight, d.out = src, wp.data_ptr(), out.data_ptr()
-        d.bias = bias.data_ptr() if bias is not None else None
-        d.B, d.HW, d.W, d.cin, d.cout, d.ldo = B, HW, W, cin, cout, ldo
-        if shuffle is not None:
-            d.shuffle_c, d.shuffle_h, d.shuffle_w = shuffle
+        d = L.pointwise(src, wp, bias, out, B, HW, W, cin, cout, ldo, shuffle=shuffle)
         self.keep.append(d)
         if crop_src is not None:
             self.launch("nd_pointwise_gemm_unshuffle_crop_nhwc_f32", C.byref(d), crop_src[0], crop_src[1])
@@ -176,8 +157,8 @@ def lsid_forward_hip(P: Dict[str, torch.Tensor], x: torch.Tensor, saved: Dict[st
     for i, c in enumerate(LSID_STAGES, start=1):
         h, w = sizes[i - 1]
         wi1 = w11 if i == 1 else P[f"conv{i}_1.weight"]
-        a = run.conv3x3(wi1, P[f"conv{i}_1.bias"], run.src(cur, mode=mode), B, h, w, cin, c)
-        z = run.conv3x3(P[f"conv{i}_2.weight"], P[f"conv{i}_2.bias"], run.src(a, mode=L.PRO_LEAKY), B, h, w, c, c)   # raw; consumers apply LeakyReLU
+        a = run.conv3x3(wi1, P[f"conv{i}_1.bias"], L.src(cur, mode=mode), B, h, w, cin, c)
+        z = run.conv3x3(P[f"conv{i}_2.weight"], P[f"conv{i}_2.bias"], L.src(a, mode=L.PRO_LEAKY), B, h, w, c, c)   # raw; consumers apply LeakyReLU
         saved[f"a{i}"], saved[f"z{i}"] = a, z
         cur, mode, cin = z, L.PRO_LEAKY, c
         if i < 5:
@@ -193,14 +174,14 @@ def lsid_forward_hip(P: Dict[str, torch.Tensor], x: torch.Tensor, saved: Dict[st
         wt = P[f"up{j}.weight"]                              # ConvTranspose2d(2, s=2) + crop to the skip's size (:135): (cin, c, 2, 2) -> rows (p1 p2 c'), columns cin
         m = wt.permute(2, 3, 1, 0).reshape(4 * c, cin).contiguous()
         up = run.empty(B, sh, sw, c)
-        run.pointwise(run.src(cur, mode=L.PRO_LEAKY), run.pack_pw(m, cin, 4 * c), None, up, B, hp * wp_, wp_, cin, 4 * c, c, shuffle=(c, sh, sw))
-        a = run.conv3x3(P[f"conv{j}_1.weight"], P[f"conv{j}_1.bias"], run.src(up, t2=saved[f"z{i}"], mode=L.PRO_LEAKY_SECOND), B, sh, sw, 2 * c, c)
-        z = run.conv3x3(P[f"conv{j}_2.weight"], P[f"conv{j}_2.bias"], run.src(a, mode=L.PRO_LEAKY), B, sh, sw, c, c)
+        run.pointwise(L.src(cur, mode=L.PRO_LEAKY), run.pack_pw(m, cin, 4 * c), None, up, B, hp * wp_, wp_, cin, 4 * c, c, shuffle=(c, sh, sw))
+        a = run.conv3x3(P[f"conv{j}_1.weight"], P[f"conv{j}_1.bias"], L.src(up, saved[f"z{i}"], L.PRO_LEAKY_SECOND), B, sh, sw, 2 * c, c)
+        z = run.conv3x3(P[f"conv{j}_2.weight"], P[f"conv{j}_2.bias"], L.src(a, mode=L.PRO_LEAKY), B, sh, sw, c, c)
         saved[f"u{j}"], saved[f"a{j}"], saved[f"z{j}"] = up, a, z
         cur, cin = z, c
     y = run.empty(B, H, W, 4)
     w10 = P["conv10.weight"].reshape(4, cin).contiguous()
-    run.pointwise(run.src(cur, mode=L.PRO_LEAKY), run.pack_pw(w10, cin, 4), P["conv10.bias"], y, B, H * W, W, cin, 4, 4)
+    run.pointwise(L.src(cur, mode=L.PRO_LEAKY), run.pack_pw(w10, cin, 4), P["conv10.bias"], y, B, H * W, W, cin, 4, 4)
     return y if head_nhwc else head_to_nchw(run, y)
 
 

@@ -78,8 +78,7 @@ def convt2x2_dgrad(run: _Launcher, w: torch.Tensor, d_up: torch.Tensor, ld_up: i
     over the zero-filled pixel unshuffle of ``d_up`` -- its first c channels, pixel stride ``ld_up``."""
     cin, c = w.shape[0], w.shape[1]
     t = run.empty(B, h, w_, cin)
-    src = run.src(d_up, c=4 * c, ld=ld_up)
-    src.unshuffle = 1
+    src = L.src(d_up, c=4 * c, ld=ld_up, unshuffle=1)
     run.pointwise(src, run.pack_pw(w.reshape(cin, 4 * c).contiguous(), 4 * c, cin, unshuffle_c=c), None, t, B, h * w_, w_, 4 * c, cin, cin,
                   crop_src=(up_h, up_w))
     return t
@@ -122,7 +121,7 @@ def _lsid_hip_backward_from_head(P: Dict[str, torch.Tensor], saved: Dict[str, to
            ws(lib.nd_linear_wgrad_workspace_floats(N, c, 4)).data_ptr(), N, c, 4, run.st)
     G["conv10.weight"], G["conv10.bias"] = gw.reshape(4, c, 1, 1), gb
     t = run.empty(B, H, W, c)
-    run.pointwise(run.src(dy), run.pack_pw_t(P["conv10.weight"].reshape(4, c).contiguous(), 4, c), None, t, B, H * W, W, 4, c, c)
+    run.pointwise(L.src(dy), run.pack_pw_t(P["conv10.weight"].reshape(4, c).contiguous(), 4, c), None, t, B, H * W, W, 4, c, c)
     dz = run.join(saved["z9"], t, t, c, None)
     # ---- up path, last stage first
     dcat: Dict[int, torch.Tensor] = {}
@@ -134,13 +133,13 @@ def _lsid_hip_backward_from_head(P: Dict[str, torch.Tensor], saved: Dict[str, to
         hp, wp_ = sizes[i]
         a = saved[f"a{j}"]
         wgrad3(f"conv{j}_2", a, dz, c, c, True)
-        t = run.conv3x3(P[f"conv{j}_2.weight"], None, run.src(dz), B, h, w, c, c, dgrad=True)
+        t = run.conv3x3(P[f"conv{j}_2.weight"], None, L.src(dz), B, h, w, c, c, dgrad=True)
         da = run.join(a, t, t, c, None)
         gw, gb = run.empty(c, 2 * c, 3, 3), run.empty(c)
         L.call("nd_conv3x3_wgrad_cat_leaky_second_nhwc_f32", saved[f"u{j}"].data_ptr(), c, c, saved[f"z{i}"].data_ptr(), c, c, da.data_ptr(), c,
                gw.data_ptr(), gb.data_ptr(), ws(lib.nd_conv3x3_wgrad_cat_workspace_floats(B, h, w, c, c, c)).data_ptr(), B, h, w, c, run.st)
         G[f"conv{j}_1.weight"], G[f"conv{j}_1.bias"] = gw, gb
-        dc = run.conv3x3(P[f"conv{j}_1.weight"], None, run.src(da), B, h, w, c, 2 * c, dgrad=True)     # [d up | d leaky(skip)]
+        dc = run.conv3x3(P[f"conv{j}_1.weight"], None, L.src(da), B, h, w, c, 2 * c, dgrad=True)     # [d up | d leaky(skip)]
         dcat[i] = dc
         # ConvTranspose2d(cin -> c) on leaky(z_prev) + crop: weight gradient, then the gradient of leaky(z_prev)
         zp = saved[f"z{j - 1}"] if j > 6 else saved["z5"]
@@ -159,12 +158,12 @@ def _lsid_hip_backward_from_head(P: Dict[str, torch.Tensor], saved: Dict[str, to
             dz = run.join(saved[f"z{i}"], run.empty(B, h, w, c), dcat[i], 2 * c, d_pool, direct_offset=c)
         a = saved[f"a{i}"]
         wgrad3(f"conv{i}_2", a, dz, c, c, True)
-        t = run.conv3x3(P[f"conv{i}_2.weight"], None, run.src(dz), B, h, w, c, c, dgrad=True)
+        t = run.conv3x3(P[f"conv{i}_2.weight"], None, L.src(dz), B, h, w, c, c, dgrad=True)
         da = run.join(a, t, t, c, None)
         if i > 1:
             cprev = LSID_STAGES[i - 2]
             wgrad3(f"conv{i}_1", saved[f"p{i - 1}"], da, cprev, cprev, True)
-            d_pool = run.conv3x3(P[f"conv{i}_1.weight"], None, run.src(da), B, h, w, c, cprev, dgrad=True)
+            d_pool = run.conv3x3(P[f"conv{i}_1.weight"], None, L.src(da), B, h, w, c, cprev, dgrad=True)
         else:
             wgrad3("conv1_1", x8, da, 4, 8, False)          # the image itself: no activation, 4 of the 8 staged channels
     return G

@@ -39,7 +39,7 @@ from torch.autograd.function import once_differentiable
 from torch import nn
 
 from . import _lib as L
-from ._host import (CONV3X3_ENTRY, CONV3X3_PACK, _empty, _need_gpu, _on, _stream, _workspace, conv3x3_kind, conv3x3_trains, conv3x3_wgrad_cat_takes, group_norm_takes,
+from ._host import (CONV3X3, _empty, _need_gpu, _on, _stream, _workspace, conv3x3_kind, conv3x3_trains, conv3x3_wgrad_cat_takes, group_norm_takes,
                     layer_norm_takes, pointwise_takes, rms_norm_takes, token_sum_takes)
 
 
@@ -65,7 +65,7 @@ def _pack_pointwise(w_ptr: int, packed_ptr: int, cin: int, cout: int, transposed
 def _pack_conv3x3(kind: str, w_ptr: int, packed_ptr: int, cin: int, cout: int, dgrad: bool, st) -> None:
     """The operand of the ``kind`` kernel (conv3x3_kind) from an OIHW weight; ``dgrad``: the data gradient's, read in place from the FORWARD weight
     (cin / cout are the operator's)."""
-    L.call(CONV3X3_PACK[kind] + ("_dgrad" if dgrad else ""), w_ptr, packed_ptr, cin, cout, st)
+    L.call(CONV3X3[kind].pack + ("_dgrad" if dgrad else ""), w_ptr, packed_ptr, cin, cout, st)
 
 
 def _conv3x3_nhwc(x: torch.Tensor, w_oihw: torch.Tensor, bias: Optional[torch.Tensor], dgrad: bool = False, stats: bool = False,
@@ -100,34 +100,25 @@ def _conv3x3_nhwc(x: torch.Tensor, w_oihw: torch.Tensor, bias: Optional[torch.Te
         kind = "direct" if kind == "wino" else kind                      # past wino2's limits: the direct kernel
         if kind == "direct" and cin % 8:
             raise L.HipError(f"conv3x3 on the HIP library needs cin % 8 == 0 (cin={cin})")
-        wino4 = kind == "wino4"
+        k, wino4 = CONV3X3[kind], kind == "wino4"
         if wino4 and cached:
             wptr = _pack_cache(x.device).get(w_oihw, cin, cout, dgrad, st, kind="w4", base=wbase)
         else:
-            wp = _workspace(CONV3X3_PACK[kind] + "_floats", x.device, cin, cout)
+            wp = _workspace(k.pack + "_floats", x.device, cin, cout)
             _pack_conv3x3(kind, w_oihw.data_ptr(), wp.data_ptr(), cin, cout, dgrad, st)
             wptr = wp.data_ptr()
-        d = L.Conv3x3()
-        d.src.p0, d.src.c0, d.src.ld0, d.src.mode = x.data_ptr(), c0, c0, L.PRO_NONE
-        if x1 is not None:
-            d.src.p1, d.src.c1, d.src.ld1 = x1.data_ptr(), x1.shape[1], x1.shape[1]
-        d.weight, d.out = wptr, out.data_ptr()
-        if bias is not None:
-            b = bias.detach().to(torch.float32).contiguous()
-            d.bias = b.data_ptr()
-        d.B, d.H, d.W, d.cin, d.cout, d.ldo = B, H, W, cin, cout, cout
-        splits = int(lib.nd_conv3x3_wino4_splitk_plan(B, H, W, cin, cout)) if wino4 and _SPLIT_K else 1
+        b = None if bias is None else bias.detach().to(torch.float32).contiguous()
         st_t = sc_t = None
         if stats:                                                 # (the split-K form leaves the same slots from its reduction kernel)
-            slots = int(lib.nd_conv3x3_wino4_stat_slots(H, W) if wino4 else lib.nd_conv3x3_wino_stat_slots(H, W) if kind == "wino2"
-                        else lib.nd_conv3x3_stat_slots(H, W, cout, B))
+            slots = int(k.stat_slots(lib, B, H, W, cout))
             st_t, sc_t = _empty((B, slots, cout, 2), x.device), _empty(slots, x.device)
-            d.stats, d.slot_count = st_t.data_ptr(), sc_t.data_ptr()
+        d = L.conv3x3(L.src(x, x1, L.PRO_NONE, c0, c0, 0, cin - c0, cin - c0), wptr, b, out, B, H, W, cin, cout, None, st_t, sc_t)
+        splits = int(lib.nd_conv3x3_wino4_splitk_plan(B, H, W, cin, cout)) if wino4 and _SPLIT_K else 1
         if splits > 1:      # few (sample, region, cout tile) items for 256 CUs (the deep layers at training batch sizes): cut along cin
             ws = _workspace("nd_conv3x3_wino4_splitk_workspace_floats", x.device, B, H, W, cout, splits)
             L.call("nd_conv3x3_wino4_splitk_nhwc_f32", C.byref(d), ws.data_ptr(), splits, st)
         else:
-            L.call(CONV3X3_ENTRY[kind], C.byref(d), st)
+            L.call(k.entry, C.byref(d), st)
         # wp / b are dropped on return: safe, because the kernels were enqueued on torch's CURRENT stream and the caching
         # allocator reuses a block only for work that is enqueued later on that same stream
     return (out, st_t, sc_t) if stats else out
@@ -648,17 +639,8 @@ def _pointwise_gemm(x2: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tens
             w32 = w.detach().float().contiguous()
             _pack_pointwise(w32.data_ptr(), wp.data_ptr(), cin, cout, transposed, st)
             wptr = wp.data_ptr()
-        d = L.Pointwise()
-        d.src.p0, d.src.c0, d.src.ld0, d.src.mode = x2.data_ptr(), c0, c0, L.PRO_NONE
-        if x2b is not None:
-            d.src.p1, d.src.c1, d.src.ld1 = x2b.data_ptr(), x2b.shape[1], x2b.shape[1]
-        d.weight, d.out = wptr, y.data_ptr()
-        if bias is not None:
-            b32 = bias.detach().float().contiguous()
-            d.bias = b32.data_ptr()
-        if res is not None:
-            d.res0, d.ldr0 = res.data_ptr(), cout
-        d.B, d.HW, d.W, d.cin, d.cout, d.ldo, d.act = 1, N, 1, cin, cout, cout, L.ACT_NONE
+        b32 = None if bias is None else bias.detach().float().contiguous()
+        d = L.pointwise(L.src(x2, x2b, L.PRO_NONE, c0, c0, 0, cin - c0, cin - c0), wptr, b32, y, 1, N, 1, cin, cout, res0=res, ldr0=cout)
         L.call("nd_pointwise_gemm_nhwc_f32", C.byref(d), st)
     return y
 

@@ -4,6 +4,7 @@ import ctypes as C
 import torch
 
 from noisediff_amd import _lib as L
+from noisediff_amd._host import CONV3X3
 
 DEV = torch.device("cuda", 0)
 
@@ -75,17 +76,9 @@ def nchw(t):           # NHWC gpu -> NCHW cpu
 
 
 def src(t, t2=None, mode=L.PRO_NONE, **kw):
-    s = L.Src()
-    s.p0, s.c0, s.ld0 = t.data_ptr(), t.shape[-1], t.shape[-1]
-    if t2 is not None:
-        s.p1, s.c1, s.ld1 = t2.data_ptr(), t2.shape[-1], t2.shape[-1]
-    s.mode = mode
-    for k, v in kw.items():
-        setattr(s, k, v.data_ptr() if isinstance(v, torch.Tensor) else v)
-    # the struct only holds raw pointers: keep the tensors alive (a freed block would be recycled by
+    # the struct only holds raw pointers: the builder keeps the tensors alive on it (a freed block would be recycled by
     # torch's caching allocator for the next allocation, e.g. the NaN-filled output buffer)
-    s._refs = [t, t2] + list(kw.values())
-    return s
+    return L.src(t, t2, mode, **kw)
 
 
 def pack_conv3(ctx, w):
@@ -107,36 +100,24 @@ def pack_pw(ctx, w, unshuffle_c=0):
     return out
 
 
-def conv3x3(ctx, s, wp, bias, B, H, W, cin, cout, stats=False):
+def conv3x3(ctx, s, wp, bias, B, H, W, cin, cout, stats=False, kind="direct"):
     out = full((B, H, W, cout))
-    d = L.Conv3x3()
-    d.src, d.weight, d.bias, d.out = s, wp.data_ptr(), None if bias is None else bias.data_ptr(), out.data_ptr()
-    d.B, d.H, d.W, d.cin, d.cout, d.ldo = B, H, W, cin, cout, cout
+    k = CONV3X3[kind]
     st = sc = None
     slots = 0
     if stats:
-        slots = ctx.lib.nd_conv3x3_stat_slots(H, W, cout, B)
+        slots = k.stat_slots(ctx.lib, B, H, W, cout)
         st = full((B, slots, cout, 2))
         sc = full((slots,))
-        d.stats, d.slot_count = st.data_ptr(), sc.data_ptr()
-    L.call("nd_conv3x3_nhwc_f32", C.byref(d), ctx.stream)
+    d = L.conv3x3(s, wp, bias, out, B, H, W, cin, cout, stats=st, slot_count=sc)
+    L.call(k.entry, C.byref(d), ctx.stream)
     ctx.sync()
     return out, st, sc, slots
 
 
 def pointwise(ctx, s, wp, bias, B, HW, W, cin, cout, act=0, res0=None, res1=None, vec=None, gn_t=None, gn_mad=None, entry="nd_pointwise_gemm_nhwc_f32"):
     out = full((B, HW, cout))
-    d = L.Pointwise()
-    d.src, d.weight, d.bias, d.out = s, wp.data_ptr(), None if bias is None else bias.data_ptr(), out.data_ptr()
-    d.B, d.HW, d.W, d.cin, d.cout, d.ldo, d.act = B, HW, W, cin, cout, cout, act
-    if res0 is not None:
-        d.res0, d.ldr0 = res0.data_ptr(), res0.shape[-1]
-    if res1 is not None:
-        d.res1, d.ldr1 = res1.data_ptr(), res1.shape[-1]
-    if vec is not None:
-        d.vec = vec.data_ptr()
-    if gn_t is not None:
-        d.gn_t, d.ldt, d.gn_mad = gn_t.data_ptr(), gn_t.shape[-1], gn_mad.data_ptr()
+    d = L.pointwise(s, wp, bias, out, B, HW, W, cin, cout, act=act, res0=res0, res1=res1, vec=vec, gn_t=gn_t, gn_mad=gn_mad)
     L.call(entry, C.byref(d), ctx.stream)
     ctx.sync()
     return out

@@ -29,6 +29,7 @@ pytestmark = pytest.mark.gpu
 import conv3x3_ref as R
 from hiputil import GUARD, Guarded, nan_like
 from noisediff_amd import _lib as L
+from noisediff_amd._host import CONV3X3
 
 # name -> (C entry, packer, fp32 reference kind, channels a K chunk holds for a virtual concat's boundary, one statistics slot per 16 x 16 tile, split-K,
 #          slot (rows, columns) of a one-pass pivoted statistics epilogue or None for the two-pass one: conv3x3_ref.slot_stats_pivoted)
@@ -41,8 +42,7 @@ ENTRIES = {
     "wino4_splitk": ("nd_conv3x3_wino4_splitk_nhwc_f32", "nd_pack_conv3x3_wino4_weight", 4, 16, True, True, (16, 16)),
     "wino4_16_splitk": ("nd_conv3x3_wino4_16_splitk_nhwc_f32", "nd_pack_conv3x3_wino4_weight", 4, 16, True, True, (16, 16)),
 }
-KERNELS = {"direct": L.CONV3X3_DIRECT, "wino": L.CONV3X3_WINO, "wino2": L.CONV3X3_WINO2, "wino4": L.CONV3X3_WINO4, "wino4_16": L.CONV3X3_WINO4_16,
-           "wino4_splitk": L.CONV3X3_WINO4, "wino4_16_splitk": L.CONV3X3_WINO4_16}
+KERNELS = {entry: CONV3X3[entry.replace("_splitk", "")].kernel for entry in ENTRIES}      # what nd_conv3x3_takes is asked about: the split-K entries are their kernel's
 MODES = {"none": L.PRO_NONE, "concat": L.PRO_NONE, "upsample": L.PRO_NONE, "affine": L.PRO_AFFINE_SILU, "map": L.PRO_AFFINE_MAP_SILU, "map_blocked": L.PRO_AFFINE_MAP_SILU,
          "genmap": L.PRO_AFFINE_GENMAP_SILU, "leaky": L.PRO_LEAKY, "leaky_second": L.PRO_LEAKY_SECOND}
 STATS_PROLOGUES = ("none", "affine", "map", "map_blocked", "genmap", "concat")      # what the sampler puts in front of a convolution whose output a GroupNorm follows

@@ -114,9 +114,7 @@ def test_conv3x3_winograd_addressing_and_prologues(ctx, entry):
         wp = hu.full((ctx.lib.nd_pack_conv3x3_wino_weight_floats(cin, cout),))
         L.call("nd_pack_conv3x3_wino_weight", wd.data_ptr(), wp.data_ptr(), cin, cout, ctx.stream)
         out, bd = hu.full((B, H, W, cout)), hu.dev(b)
-        d = L.Conv3x3()
-        d.src, d.weight, d.bias, d.out = s, wp.data_ptr(), bd.data_ptr(), out.data_ptr()
-        d.B, d.H, d.W, d.cin, d.cout, d.ldo = B, H, W, cin, cout, cout
+        d = L.conv3x3(s, wp, bd, out, B, H, W, cin, cout)
         L.call(entry, C.byref(d), ctx.stream)
         ctx.sync()
         return hu.nchw(out)
@@ -153,10 +151,7 @@ def test_conv3x3_wino2_is_bitwise_repeatable(ctx):
     runs = []
     for _ in range(5):
         out, st, sc = hu.full((B, H, W, cout)), hu.full((B, slots, cout, 2)), hu.full((slots,))
-        d = L.Conv3x3()
-        d.src = hu.src(xd, None, L.PRO_AFFINE_SILU, mad=mad)
-        d.weight, d.bias, d.out, d.stats, d.slot_count = wp.data_ptr(), bd.data_ptr(), out.data_ptr(), st.data_ptr(), sc.data_ptr()
-        d.B, d.H, d.W, d.cin, d.cout, d.ldo = B, H, W, cin, cout, cout
+        d = L.conv3x3(hu.src(xd, None, L.PRO_AFFINE_SILU, mad=mad), wp, bd, out, B, H, W, cin, cout, stats=st, slot_count=sc)
         L.call("nd_conv3x3_wino2_nhwc_f32", C.byref(d), ctx.stream)
         ctx.sync()
         runs.append((out.cpu(), st.cpu()))
@@ -413,7 +408,7 @@ def test_pointwise_prologues(ctx):
     wd, bd = U("pp.wd", (32, 64, 1, 1), -0.3, 0.3), U("pp.bd", (32,))
     sd = {"d.1.weight": wd, "d.1.bias": bd}
     ref = O.pixel_unshuffle_conv(sd, "d", xc)
-    s = hu.src(hu.nhwc(xc), None, L.PRO_NONE, unshuffle=1, c0=64, ld0=16)
+    s = hu.src(hu.nhwc(xc), None, L.PRO_NONE, unshuffle=1, c=64, ld=16)
     out = hu.pointwise(ctx, s, hu.pack_pw(ctx, wd, unshuffle_c=16), hu.dev(bd), B, (H // 2) * (W // 2), W // 2, 64, 32)
     assert rel_err(out.view(B, H // 2, W // 2, 32).permute(0, 3, 1, 2).cpu(), ref) < TOL
 
@@ -714,15 +709,7 @@ def test_conv3x3_winograd_matches_direct_semantics(ctx, case, entry):
     ctx.sync()
 
     def run(s):
-        out = hu.full((B, H, W, cout))
-        slots = ctx.lib.nd_conv3x3_wino_stat_slots(H, W)
-        st, sc = hu.full((B, slots, cout, 2)), hu.full((slots,))
-        d = L.Conv3x3()
-        d.src, d.weight, d.bias, d.out, d.stats, d.slot_count = s, wp.data_ptr(), bd.data_ptr(), out.data_ptr(), st.data_ptr(), sc.data_ptr()
-        d.B, d.H, d.W, d.cin, d.cout, d.ldo = B, H, W, cin, cout, cout
-        L.call(entry, C.byref(d), ctx.stream)
-        ctx.sync()
-        return out, st, sc, slots
+        return hu.conv3x3(ctx, s, wp, bd, B, H, W, cin, cout, True, "wino2" if entry == "nd_conv3x3_wino2_nhwc_f32" else "wino")
 
     bd = hu.dev(b)
     out, st, sc, slots = run(hu.src(hu.nhwc(x)))
@@ -753,18 +740,10 @@ def test_conv3x3_winograd_matches_direct_semantics(ctx, case, entry):
 
 def _run_wino4(ctx, s, wp, bd, B, H, W, cin, cout, stats=True, entry="nd_conv3x3_wino4_nhwc_f32"):
     import hiputil as hu
-    out = hu.full((B, H, W, cout))
-    d = L.Conv3x3()
-    d.src, d.weight, d.bias, d.out = s, wp.data_ptr(), bd.data_ptr(), out.data_ptr()
-    d.B, d.H, d.W, d.cin, d.cout, d.ldo = B, H, W, cin, cout, cout
-    st = sc = None
-    slots = ctx.lib.nd_conv3x3_wino4_stat_slots(H, W)            # one per 16 x 16 tile (the F(2x2) kernels: two)
-    if stats:
-        st, sc = hu.full((B, slots, cout, 2)), hu.full((slots,))
-        d.stats, d.slot_count = st.data_ptr(), sc.data_ptr()
-    L.call(entry, C.byref(d), ctx.stream)
-    ctx.sync()
-    return out, st, sc, slots
+    from noisediff_amd._host import CONV3X3
+    kind = next(kind for kind, k in CONV3X3.items() if k.entry == entry)
+    out, st, sc, _ = hu.conv3x3(ctx, s, wp, bd, B, H, W, cin, cout, stats, kind)
+    return out, st, sc, CONV3X3[kind].stat_slots(ctx.lib, B, H, W, cout)            # one per 16 x 16 tile (the F(2x2) kernels: two)
 
 
 def _check_gn(ctx, case, ref, st, sc, slots, B, cout, tol):
@@ -942,9 +921,7 @@ def test_conv3x3_wino2_headline_shapes(ctx, case):
 
     def run(s):
         out, st, sc = hu.full((B, H, W, cout)), hu.full((B, slots, cout, 2)), hu.full((slots,))
-        d = L.Conv3x3()
-        d.src, d.weight, d.bias, d.out, d.stats, d.slot_count = s, wp.data_ptr(), bd.data_ptr(), out.data_ptr(), st.data_ptr(), sc.data_ptr()
-        d.B, d.H, d.W, d.cin, d.cout, d.ldo = B, H, W, cin, cout, cout
+        d = L.conv3x3(s, wp, bd, out, B, H, W, cin, cout, stats=st, slot_count=sc)
         L.call("nd_conv3x3_wino2_nhwc_f32", C.byref(d), ctx.stream)
         ctx.sync()
         return out, st, sc
@@ -1078,9 +1055,7 @@ def test_conv3x3_wino4_16_split_k_for_sampling(ctx, case):
     def run(s, nb=B):
         out, st, sc = hu.full((nb, H, W, cout)), hu.full((nb, slots, cout, 2)), hu.full((slots,))
         ws_ = hu.full((ctx.lib.nd_conv3x3_wino4_splitk_workspace_floats(nb, H, W, cout, splits),))
-        d = L.Conv3x3()
-        d.src, d.weight, d.bias, d.out, d.stats, d.slot_count = s, wp.data_ptr(), bd.data_ptr(), out.data_ptr(), st.data_ptr(), sc.data_ptr()
-        d.B, d.H, d.W, d.cin, d.cout, d.ldo = nb, H, W, cin, cout, cout
+        d = L.conv3x3(s, wp, bd, out, nb, H, W, cin, cout, stats=st, slot_count=sc)
         L.call(entry, C.byref(d), ws_.data_ptr(), splits, ctx.stream)
         ctx.sync()
         return out, st, sc

@@ -633,8 +633,116 @@ def test_conv3x3_kind_answers_a_repeated_shape_from_its_cache():
     assert (after.hits, after.misses) == (before.hits + 1, before.misses)
 
 
-_FORM_KERNEL = {"": L.CONV3X3_DIRECT, "wino": L.CONV3X3_WINO, "wino2": L.CONV3X3_WINO2, "wino4": L.CONV3X3_WINO4, "wino4_16": L.CONV3X3_WINO4_16}
-_KIND_KERNEL = dict(_FORM_KERNEL, direct=L.CONV3X3_DIRECT)
+class _Operand:
+    """A stand-in for a device tensor on the CPU: an address and a shape."""
+
+    def __init__(self, address, *shape):
+        self.address, self.shape = address, shape
+
+    def data_ptr(self):
+        return self.address
+
+
+_T, _T2 = _Operand(0x10000, 2, 8, 8, 24), _Operand(0x20000, 2, 8, 8, 40)
+_EXTRA = {name: _Operand(0x30000 + 0x1000 * i, 7) for i, name in enumerate(("mad", "map", "vec", "gamma", "beta", "rowstats"))}
+
+
+def test_source_builder_fills_what_a_hand_filled_nd_src_holds():
+    """L.src against L.Src filled field by field here: one and two sources, the c / ld / offset overrides, every extra operand alone and together, the three
+    addressing flags; tensors, integer addresses and None alike; the operands hang on the struct."""
+    assert bytes(L.src(_T)) == bytes(L.Src(p0=0x10000, c0=24, ld0=24))
+    assert bytes(L.src(0x10000, c=24, ld=24)) == bytes(L.Src(p0=0x10000, c0=24, ld0=24))
+    assert bytes(L.src(_T, _T2, L.PRO_LEAKY_SECOND)) == bytes(L.Src(p0=0x10000, c0=24, ld0=24, p1=0x20000, c1=40, ld1=40, mode=L.PRO_LEAKY_SECOND))
+    assert bytes(L.src(_T, 0x20000, c1=16, ld1=48)) == bytes(L.Src(p0=0x10000, c0=24, ld0=24, p1=0x20000, c1=16, ld1=48))
+    assert bytes(L.src(_T, c=16, ld=32, offset=5)) == bytes(L.Src(p0=0x10000 + 4 * 5, c0=16, ld0=32))
+    assert bytes(L.src(_T, c=16)) == bytes(L.Src(p0=0x10000, c0=16, ld0=24)) and bytes(L.src(_T, ld=32)) == bytes(L.Src(p0=0x10000, c0=24, ld0=32))
+    assert bytes(L.src(None, None, L.PRO_SILU, 8, 12, 0, 4, 6)) == bytes(L.Src(c0=8, ld0=12, c1=4, ld1=6, mode=L.PRO_SILU))       # a question: widths, no address
+    for name, op in _EXTRA.items():
+        want = bytes(L.Src(p0=0x10000, c0=24, ld0=24, mode=L.PRO_AFFINE_SILU, **{name: op.address}))
+        assert bytes(L.src(_T, None, L.PRO_AFFINE_SILU, **{name: op})) == want and bytes(L.src(_T, None, L.PRO_AFFINE_SILU, **{name: op.address})) == want, name
+    for flag in ("upsample", "unshuffle", "map_blocked"):
+        assert bytes(L.src(_T, **{flag: 1})) == bytes(L.Src(p0=0x10000, c0=24, ld0=24, **{flag: 1})), flag
+    s = L.src(_T, _T2, L.PRO_AFFINE_MAP_SILU, upsample=1, unshuffle=1, map_blocked=1, **_EXTRA)
+    assert bytes(s) == bytes(L.Src(p0=0x10000, c0=24, ld0=24, p1=0x20000, c1=40, ld1=40, mode=L.PRO_AFFINE_MAP_SILU, upsample=1, unshuffle=1, map_blocked=1,
+                                   **{name: op.address for name, op in _EXTRA.items()}))
+    assert {id(r) for r in s._refs} >= {id(_T), id(_T2)} | {id(op) for op in _EXTRA.values()}
+
+
+def test_conv3x3_builder_fills_what_a_hand_filled_nd_conv3x3_holds():
+    """L.conv3x3: with and without bias, with and without statistics, ldo != cout; the source's operands carried over."""
+    s, w, b, out, st, sc = L.src(_T, mad=_EXTRA["mad"]), _Operand(0x40000, 9), _Operand(0x41000, 32), _Operand(0x42000, 2, 8, 8, 32), _Operand(0x43000, 2, 4, 32, 2), 0x44000
+    plain = dict(src=s, weight=0x40000, out=0x42000, B=2, H=8, W=8, cin=24, cout=32)
+    assert bytes(L.conv3x3(s, w, None, out, 2, 8, 8, 24, 32)) == bytes(L.Conv3x3(ldo=32, **plain))
+    assert bytes(L.conv3x3(s, 0x40000, b, 0x42000, 2, 8, 8, 24, 32)) == bytes(L.Conv3x3(bias=0x41000, ldo=32, **plain))
+    assert bytes(L.conv3x3(s, w, b, out, 2, 8, 8, 24, 32, 48)) == bytes(L.Conv3x3(bias=0x41000, ldo=48, **plain))
+    d = L.conv3x3(s, w, b, out, 2, 8, 8, 24, 32, stats=st, slot_count=sc)
+    assert bytes(d) == bytes(L.Conv3x3(bias=0x41000, ldo=32, stats=0x43000, slot_count=0x44000, **plain))
+    assert d._refs[0] is s._refs and {id(r) for r in d._refs} >= {id(w), id(b), id(out), id(st)}
+
+
+def test_pointwise_builder_fills_what_a_hand_filled_nd_pointwise_holds():
+    """L.pointwise: each of res0, res1, vec, gn_t + gn_mad, act, shuffle and ldo != cout alone, then all of them."""
+    s, w, b, out = L.src(_T, _T2), _Operand(0x40000, 9), _Operand(0x41000, 32), _Operand(0x42000, 2, 64, 32)
+    r0, r1, vec, gn_t, gn_mad = _Operand(0x50000, 2, 64, 32), _Operand(0x51000, 2, 64, 36), _Operand(0x52000, 2, 32), _Operand(0x53000, 2, 64, 44), _Operand(0x54000, 2, 3, 32)
+    plain = dict(src=s, weight=0x40000, bias=0x41000, out=0x42000, B=2, HW=64, W=8, cin=64, cout=32)
+    build = lambda *a, **kw: bytes(L.pointwise(s, w, b, out, 2, 64, 8, 64, 32, *a, **kw))
+    assert build() == bytes(L.Pointwise(ldo=32, **plain)) and build(40) == bytes(L.Pointwise(ldo=40, **plain))
+    assert bytes(L.pointwise(s, 0x40000, None, 0x42000, 2, 64, 8, 64, 32)) == bytes(L.Pointwise(ldo=32, **dict(plain, bias=None)))
+    assert build(act=L.ACT_GELU) == bytes(L.Pointwise(ldo=32, act=L.ACT_GELU, **plain))
+    assert build(res0=r0) == bytes(L.Pointwise(ldo=32, res0=0x50000, ldr0=32, **plain)) and build(res0=0x50000, ldr0=48) == bytes(L.Pointwise(ldo=32, res0=0x50000, ldr0=48, **plain))
+    assert build(res1=r1) == bytes(L.Pointwise(ldo=32, res1=0x51000, ldr1=36, **plain))
+    assert build(vec=vec) == bytes(L.Pointwise(ldo=32, vec=0x52000, **plain))
+    assert build(gn_t=gn_t, gn_mad=gn_mad) == bytes(L.Pointwise(ldo=32, gn_t=0x53000, ldt=44, gn_mad=0x54000, **plain))
+    assert build(shuffle=(8, 15, 17)) == bytes(L.Pointwise(ldo=32, shuffle_c=8, shuffle_h=15, shuffle_w=17, **plain))
+    d = L.pointwise(s, w, b, out, 2, 64, 8, 64, 32, 40, L.ACT_SILU, r0, r1, vec, gn_t, gn_mad, (8, 15, 17))
+    assert bytes(d) == bytes(L.Pointwise(ldo=40, act=L.ACT_SILU, res0=0x50000, ldr0=32, res1=0x51000, ldr1=36, vec=0x52000, gn_t=0x53000, ldt=44, gn_mad=0x54000,
+                                         shuffle_c=8, shuffle_h=15, shuffle_w=17, **plain))
+    assert d._refs[0] is s._refs and {id(r) for r in d._refs} >= {id(x) for x in (w, b, out, r0, r1, vec, gn_t, gn_mad)}
+
+
+def test_rows_from_a_sample_move_every_per_sample_operand_by_its_own_stride():
+    """L.src_rows: sample 0 is the source itself; sample 3 behind an upsampled source, a stored map and a map formed in the kernel, each against the
+    offsets written out here (4 bytes per float); gamma / beta / rowstats and every integer stay."""
+    from noisediff_amd.spec import POS_DIM
+    H, W, b0 = 16, 32, 3
+    two = L.src(_T, _T2, L.PRO_AFFINE_SILU, mad=_EXTRA["mad"], vec=_EXTRA["vec"], gamma=_EXTRA["gamma"])
+    r = L.src_rows(two, 0, H * W, 128)
+    assert bytes(r) == bytes(two) and r is not two and r._refs is two._refs
+    up = L.src(_T, upsample=1, mad=_EXTRA["mad"])                          # source pixels: a quarter of the output's
+    assert bytes(L.src_rows(up, b0, (H // 2) * (W // 2))) == bytes(L.Src(p0=0x10000 + 4 * b0 * (H // 2) * (W // 2) * 24, c0=24, ld0=24, upsample=1,
+                                                                         mad=_EXTRA["mad"].address + 4 * b0 * 3 * 24))
+    c0, c1 = 24, 40
+    stored = L.src(_T, _T2, L.PRO_AFFINE_MAP_SILU, ld=28, mad=_EXTRA["mad"], map=_EXTRA["map"], map_blocked=1, beta=_EXTRA["beta"])
+    assert bytes(L.src_rows(stored, b0, H * W, 2 * (c0 + c1))) == bytes(L.Src(
+        p0=0x10000 + 4 * b0 * H * W * 28, c0=c0, ld0=28, p1=0x20000 + 4 * b0 * H * W * c1, c1=c1, ld1=c1, mode=L.PRO_AFFINE_MAP_SILU, map_blocked=1,
+        mad=_EXTRA["mad"].address + 4 * b0 * 3 * (c0 + c1), map=_EXTRA["map"].address + 4 * b0 * H * W * 2 * (c0 + c1), beta=_EXTRA["beta"].address))
+    formed = L.src(_T, None, L.PRO_AFFINE_GENMAP_SILU, mad=_EXTRA["mad"], map=_EXTRA["map"], gamma=_EXTRA["gamma"], beta=_EXTRA["beta"])
+    assert bytes(L.src_rows(formed, b0, H * W, POS_DIM)) == bytes(L.Src(
+        p0=0x10000 + 4 * b0 * H * W * c0, c0=c0, ld0=c0, mode=L.PRO_AFFINE_GENMAP_SILU, mad=_EXTRA["mad"].address + 4 * b0 * 3 * c0,
+        map=_EXTRA["map"].address + 4 * b0 * H * W * POS_DIM, gamma=_EXTRA["gamma"].address, beta=_EXTRA["beta"].address))
+    ln = L.src(_T, None, L.PRO_LAYERNORM, vec=_EXTRA["vec"], rowstats=_EXTRA["rowstats"])      # a chain's source: the per-sample vector moves, no mad / map to move
+    assert bytes(L.src_rows(ln, b0, H * W)) == bytes(L.Src(p0=0x10000 + 4 * b0 * H * W * c0, c0=c0, ld0=c0, mode=L.PRO_LAYERNORM, vec=_EXTRA["vec"].address + 4 * b0 * c0,
+                                                           rowstats=_EXTRA["rowstats"].address))
+
+
+def test_the_conv3x3_table_names_what_the_library_exports():
+    """_host.CONV3X3: one record per kernel; its entries are the library's, its enum value the header's, its tiling id the literal Plan.conv3 held (the direct
+    kernel's came from nd_conv3x3_tiling_id, and does: None), its arena slot and its statistics slots what Plan.conv3 chose."""
+    from noisediff_amd._host import CONV3X3
+    header = open(os.path.join(REPO, "include", "noisediff_hip.h")).read()
+    enum = {name.lower(): int(value) for name, value in re.findall(r"ND_CONV3X3_(\w+) = (\d+)", re.search(r"enum nd_conv3x3_kernel \{([^}]*)\}", header).group(1))}
+    tiling = {"direct": None, "wino": 9001, "wino2": 9002, "wino4": 9004, "wino4_16": 9016}
+    slot = {"direct": ".weight", "wino": ".weight.wino", "wino2": ".weight.wino", "wino4": ".weight.wino4", "wino4_16": ".weight.wino4"}
+    assert set(CONV3X3) == set(enum) == set(tiling) and len(enum) == 5
+    lib = L.load()
+    B, H, W, cout = 3, 48, 80, 64
+    for name, k in CONV3X3.items():
+        assert k.kernel == enum[name] == getattr(L, "CONV3X3_" + name.upper()) and k.tiling == tiling[name] and k.slot == slot[name], name
+        assert k.entry == ("nd_conv3x3_nhwc_f32" if name == "direct" else f"nd_conv3x3_{name}_nhwc_f32") and k.entry in L.SIGNATURES, name
+        assert k.splitk == (f"nd_conv3x3_{name}_splitk_nhwc_f32" if name.startswith("wino4") else None) and (k.splitk is None or k.splitk in L.SIGNATURES), name
+        assert all(k.pack + suffix in L.SIGNATURES for suffix in ("", "_floats", "_dgrad")), name
+        want = lib.nd_conv3x3_stat_slots(H, W, cout, B) if name == "direct" else lib.nd_conv3x3_wino4_stat_slots(H, W) if name.startswith("wino4") else lib.nd_conv3x3_wino_stat_slots(H, W)
+        assert k.stat_slots(lib, B, H, W, cout) == want > 0, name
 
 
 def conv3x3_selection_differences():
@@ -643,7 +751,7 @@ def conv3x3_selection_differences():
     (never more launches) where the form and the split count are the recorded ones."""
     import json
     from noisediff_amd import engine, train
-    from noisediff_amd._host import conv3x3_kind, conv3x3_takes
+    from noisediff_amd._host import CONV3X3, conv3x3_kind, conv3x3_takes
     table = json.load(open(os.path.join(REPO, "tests", "golden", "conv3x3_selection.json")))
     out = []
     for *row, form, splits, rows in table["form"]:                      # a row: the inputs, then what was decided
@@ -655,13 +763,13 @@ def conv3x3_selection_differences():
             new = ["raise", 0, 0]
         same = new == old or (new[:2] == old[:2] and not old[0].startswith("wino4") and old[0] != "raise" and new[2] >= old[2] and -(-B // new[2]) <= -(-B // old[2]))
         if not same:
-            refused = old[0] == "raise" or not conv3x3_takes(_FORM_KERNEL[old[0]], old[2], H, W, cin, cout, c0, c1, ld0, ld1, mode, bool(up), splits=old[1])
+            refused = old[0] == "raise" or not conv3x3_takes(CONV3X3[old[0] or "direct"].kernel, old[2], H, W, cin, cout, c0, c1, ld0, ld1, mode, bool(up), splits=old[1])
             out.append(("form", row, old, new, refused))
     for *row, old in table["kind"]:
         B, H, W, cin, cout, c0, c1, ld, w4 = row
         new = conv3x3_kind(B, H, W, cin, cout, c0, c1, ld, wino4=bool(w4))
         if new != old:
-            out.append(("kind", row, old, new, not conv3x3_takes(_KIND_KERNEL[old], B, H, W, cin, cout, c0, c1, ld, ld if c1 else 0)))
+            out.append(("kind", row, old, new, not conv3x3_takes(CONV3X3[old].kernel, B, H, W, cin, cout, c0, c1, ld, ld if c1 else 0)))
     for *row, old in table["cat"]:
         B, c0, c1, H, W, cout = row
         new = bool(train.cat_sources_ok(_cuda_like(B, c0, H, W), _cuda_like(B, c1, H, W), cout))

@@ -1093,7 +1093,7 @@ def test_pointwise_unshuffle_crop_against_float64(ctx, size):
         wt = U(f"uc.w.{j}", (cin, c, 2, 2)) * (4 * c) ** -0.5
         dcat = U(f"uc.d.{j}.{size}", (B, up_h, up_w, 2 * c), -2, 2)
         dd = hu.dev(dcat)
-        s = hu.src(dd, c0=4 * c, ld0=2 * c, unshuffle=1)
+        s = hu.src(dd, c=4 * c, ld=2 * c, unshuffle=1)
         wp = hu.pack_pw(ctx, wt.reshape(cin, 4 * c).contiguous(), unshuffle_c=c)
         out = hu.full((B * h * w_ + 2, cin + 4))
         d = L.Pointwise()
@@ -1181,7 +1181,7 @@ def test_bad_arguments_return_their_error_code_without_a_launch(ctx):
     # the cropped unshuffle: descriptor by pointer
     wp = hu.pack_pw(ctx, U("bad.w", (8, 16)), unshuffle_c=4)
     d = L.Pointwise()
-    d.src, d.weight, d.out = hu.src(a, c0=16, ld0=4, unshuffle=1), wp.data_ptr(), po
+    d.src, d.weight, d.out = hu.src(a, c=16, ld=4, unshuffle=1), wp.data_ptr(), po
     d.B, d.HW, d.W, d.cin, d.cout, d.ldo = 1, 4, 2, 16, 8, 8
     fn = lib.nd_pointwise_gemm_unshuffle_crop_nhwc_f32
     assert fn(C.byref(d), 3, 4, st) == 0, L.load().nd_last_error()
