@@ -626,6 +626,26 @@ int nd_pointwise_gemm_split_takes(const nd_pointwise* d);
 int64_t nd_pack_pointwise_weight_split_floats(int cin, int cout);
 int nd_pack_pointwise_weight_split(const float* w, float* packed, int cin, int cout, void* stream);
 
+/* Downsample = pixel-unshuffle + 1x1 (Diffusion_arch.py:80-81) on the streaming kernels: the same descriptor as nd_pointwise_gemm_nhwc_f32 with
+ * src.unshuffle = 1 (the source is the (2 H, 2 W) image with c0 / 4 channels at a pixel stride of ld0; HW, W: the OUTPUT's), staged as the plain source with a
+ * doubled pixel and row stride plus one constant per 32-channel chunk.  cout % 128 == 0: the split-product kernel, `weight` an
+ * nd_pack_pointwise_weight_split_unshuffle packing (unshuffle_c = cin / 4; nd_pack_pointwise_weight_split_floats floats); otherwise the pipelined fp32 kernel,
+ * `weight` an nd_pack_pointwise_weight packing with unshuffle_c = cin / 4.  Takes (nd_pointwise_downsample_takes: 1 / 0, no HIP call, nd_last_error untouched; it
+ * reads the sizes, widths, strides and modes and WHETHER res0 / res1 / gn_t / vec are given): one source, (c0 / 4) % 32 == 0, cout % 64 == 0, no prologue, no
+ * residual operands, no output shuffle; anything else: ND_E_SHAPE. */
+int nd_pointwise_downsample_nhwc_f32(const nd_pointwise* d, void* stream);
+int nd_pointwise_downsample_takes(const nd_pointwise* d);
+int nd_pack_pointwise_weight_split_unshuffle(const float* w, float* packed, int cin, int cout, int unshuffle_c, void* stream);
+
+/* The tail of a wide AttnBlock (Diffusion_arch.py:434-443), ff.net.2 then proj_out with only additions between them, as ONE linear map over [h1; x]:
+ *   y = Wp (W2 h1 + b2 + x + cb) + bp + x = [Wp W2 | Wp + I] [h1; x] + (Wp b2 + bp) + Wp cb.
+ * nd_pack_attn_tail_fold writes w_out (C, 3 C) row-major = [Wp W2 | Wp + I] and b_out [C] = Wp b2 + bp from W2 (C, 2 C) and Wp (C, C) in torch layout, every
+ * C-term sum in fp64 on the device and rounded once to fp32 (b2 / bp may be NULL: zeros); nd_pack_attn_tail_fold_floats(C) = 3 C C, the floats of w_out.
+ * The GEMM is nd_pointwise_gemm_split_nhwc_f32 on nd_pack_pointwise_weight_split(w_out, cin = 3 C, cout = C) with the sources (h1, x) and
+ * vec = Wp cb + b_out per sample (proj_out itself over the rows of cb, with b_out as its bias). */
+int64_t nd_pack_attn_tail_fold_floats(int C);
+int nd_pack_attn_tail_fold(const float* w2, const float* b2, const float* wp, const float* bp, float* w_out, float* b_out, int C, void* stream);
+
 /* Two 1x1 layers with nothing between them but an addition, the second one narrow (cout 4 or 8), as ONE streaming dot product -- the end of the
  * U-Net, final_conv(res_conv(cat(xp, x0)) + silu(GN(c2))) + shot (Diffusion_arch.py:156,170,554,644):
  *   out[p] = W [p0[p]; p1[p]; silu((t[p] - M[b]) * A[b] + D[b])] + bias [+ res0[p]],    W = [Wf Wr | Wf],  bias = Wf br + bf

@@ -180,6 +180,11 @@ SIGNATURES = {
     "nd_pointwise_narrow_fold_takes": (i32, [i32, i32, i32, i32]),
     "nd_pack_narrow_fold_floats": (i64, [i32, i32]),
     "nd_pack_narrow_fold": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, i32, vp]),
+    "nd_pointwise_downsample_nhwc_f32": (i32, [C.POINTER(Pointwise), vp]),
+    "nd_pointwise_downsample_takes": (i32, [C.POINTER(Pointwise)]),
+    "nd_pack_pointwise_weight_split_unshuffle": (i32, [vp, vp, i32, i32, i32, vp]),
+    "nd_pack_attn_tail_fold_floats": (i64, [i32]),
+    "nd_pack_attn_tail_fold": (i32, [vp, vp, vp, vp, vp, vp, i32, vp]),
     "nd_pack_pointwise_weight_floats": (i64, [i32, i32]),
     "nd_pack_pointwise_weight": (i32, [vp, vp, i32, i32, i32, vp]),
     "nd_pack_pointwise_weight_t": (i32, [vp, vp, i32, i32, vp]),
@@ -297,7 +302,7 @@ SIGNATURES = {
 
 _UNCHECKED = {"nd_conv3x3_takes", "nd_pointwise_gemm_takes", "nd_pointwise_gemm_split_takes", "nd_pointwise_chain_supported", "nd_pointwise_chain_takes",
               "nd_groupnorm_train_takes", "nd_layernorm_train_takes", "nd_rmsnorm_train_takes", "nd_token_sum_takes", "nd_conv3x3_wgrad_plan", "nd_conv3x3_wgrad_cat_takes",
-              "nd_pointwise_chain_tail_takes", "nd_pointwise_narrow_fold_takes", "nd_pack_narrow_fold_floats", "nd_version", "nd_last_error", "nd_stream_device", "nd_conv3x3_wgrad_form", "nd_adam_chunk_elements", "nd_ema_chunk_elements", "nd_conv7x7_c4_wgrad_workspace_floats", "nd_conv3x3_stat_slots", "nd_conv3x3_tiling_id", "nd_pack_conv3x3_weight_floats",
+              "nd_pointwise_chain_tail_takes", "nd_pointwise_narrow_fold_takes", "nd_pack_narrow_fold_floats", "nd_pointwise_downsample_takes", "nd_pack_attn_tail_fold_floats", "nd_version", "nd_last_error", "nd_stream_device", "nd_conv3x3_wgrad_form", "nd_adam_chunk_elements", "nd_ema_chunk_elements", "nd_conv7x7_c4_wgrad_workspace_floats", "nd_conv3x3_stat_slots", "nd_conv3x3_tiling_id", "nd_pack_conv3x3_weight_floats",
               "nd_pack_pointwise_weight_floats", "nd_linear_attention_workspace_floats", "nd_conv3x3_wino_stat_slots", "nd_conv3x3_wino4_stat_slots",
               "nd_pack_conv3x3_wino_weight_floats", "nd_pack_conv3x3_wino4_weight_floats", "nd_conv3x3_wino4_splitk_plan", "nd_conv3x3_wino4_16_splitk_plan", "nd_conv3x3_wino4_splitk_workspace_floats", "nd_token_sum_workspace_floats", "nd_cond_step_lds_bytes", "nd_conv3x3_wgrad_workspace_floats",
               "nd_groupnorm_train_workspace_floats", "nd_linear_wgrad_workspace_floats",

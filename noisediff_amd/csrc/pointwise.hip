@@ -190,10 +190,24 @@ __device__ __forceinline__ void pw_epilogue(const PwArgs& a, f32x16 (&acc)[MB][N
 // matrix work instead of relying on a second resident workgroup to fill the gap; one barrier per chunk.
 constexpr int PKC = 32, PLDA = PKC + 4;
 
+// ---- pixel-unshuffled staging of the pipelined and the split kernel (their UNS instances: nd_pointwise_downsample_nhwc_f32).  The source is the (2 H, 2 W)
+// image with c0 / 4 channels, the layer's K order (p1 p2 c): a 32-channel chunk lies inside ONE sub-pixel (host: (c0 / 4) % 32 == 0), so the source of output pixel
+// (y, x) for chunk cb is pixel (2 y + p1, 2 x + p2), channels cb mod (c0 / 4) ... -- the plain staging with a row base formed once per tile (uns_row) plus one
+// constant per chunk (uns_chunk), in floats.
+__device__ __forceinline__ size_t uns_row(const nd_pointwise& d, int b, int p) {
+    const int y = p / d.W, x = p - y * d.W;
+    return (((size_t)b * (d.HW / d.W) * 2 + 2 * y) * (2 * d.W) + 2 * x) * d.src.ld0;
+}
+__device__ __forceinline__ int uns_chunk(const nd_pointwise& d, int cb) {
+    const int Cs = d.src.c0 >> 2;
+    const int sub = (cb >= Cs) + (cb >= 2 * Cs) + (cb >= 3 * Cs);          // the chunk's sub-pixel p1 p2 (no division: once per chunk, next to the MFMAs)
+    return ((sub >> 1) * 2 * d.W + (sub & 1)) * d.src.ld0 + (cb - sub * Cs);
+}
+
 #ifndef PW_PIPE_OCC
 #define PW_PIPE_OCC 3        // waves per SIMD the 64-pixel tiles are compiled for (168 registers; 2 -> 3: -0.2 % per step same-box, 4 spills)
 #endif
-template <int MB, int NB, int MODE>
+template <int MB, int NB, int MODE, bool UNS = false>
 __global__ __launch_bounds__(256, (MB == 1 ? PW_PIPE_OCC : 2)) void pointwise_pipe_kernel(const PwArgs a) {
     constexpr int BM = 2 * MB * 32, BN = 2 * NB * 32;
     constexpr int SIT = BM / 32;                              // staging passes: BM rows x 8 channel quads / 256 threads
@@ -238,6 +252,7 @@ __global__ __launch_bounds__(256, (MB == 1 ? PW_PIPE_OCC : 2)) void pointwise_pi
         const size_t pix = (size_t)b * HW + min(p0 + prow + it * 32, HW - 1);
         pixoff0[it] = pix * s.ld0;
         pixoff1[it] = pix * s.ld1;
+        if constexpr (UNS) pixoff0[it] = uns_row(a.d, b, min(p0 + prow + it * 32, HW - 1));
         rmean[it] = 0.0f; rrstd[it] = 1.0f;
         if (MODE == ND_PRO_LAYERNORM) {                       // host: rowstats present (rows wider than one chunk)
             rmean[it] = s.rowstats[2 * pix];
@@ -256,11 +271,17 @@ __global__ __launch_bounds__(256, (MB == 1 ? PW_PIPE_OCC : 2)) void pointwise_pi
                 bq[S][g][nb] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(
                     wrsrc, wvoff, __builtin_amdgcn_readfirstlane((((cb >> 2) + 2 * g) * a.coutP + nb * 32) * 16), 0));
         const int c = cb + quad * 4;                          // < Cin: cin % 32 == 0
-        const bool sec = c >= s.c0;
-        const float* base = sec ? s.p1 : s.p0;
-        const int cc = sec ? c - s.c0 : c;
+        if constexpr (UNS) {
+            const float* base = s.p0 + (uns_chunk(a.d, cb) + quad * 4);
 #pragma unroll
-        for (int it = 0; it < SIT; ++it) raw[S][it] = nd_ld4(base + (sec ? pixoff1[it] : pixoff0[it]) + cc);
+            for (int it = 0; it < SIT; ++it) raw[S][it] = nd_ld4(base + pixoff0[it]);
+        } else {
+            const bool sec = c >= s.c0;
+            const float* base = sec ? s.p1 : s.p0;
+            const int cc = sec ? c - s.c0 : c;
+#pragma unroll
+            for (int it = 0; it < SIT; ++it) raw[S][it] = nd_ld4(base + (sec ? pixoff1[it] : pixoff0[it]) + cc);
+        }
         if (MODE == ND_PRO_LAYERNORM) {
             const f32x4 zero = {0, 0, 0, 0};
             pA[S] = nd_ld4(s.gamma + c); pB[S] = nd_ld4(s.beta + c);
@@ -518,7 +539,7 @@ constexpr int SROW = SKC * 2 + 16;                           // bytes per row of
 constexpr int SPLANE = 128 * SROW, SABUF = 3 * SPLANE;       // one term plane, one chunk buffer (30 KB)
 constexpr int SPLIT_LDS = 2 * SABUF > 128 * 132 * 4 ? 2 * SABUF : 128 * 132 * 4;
 
-template <int MODE>
+template <int MODE, bool UNS = false>
 __global__ __launch_bounds__(256, 2) void pointwise_split_kernel(const PwArgs a) {
     constexpr int MB = 2, NB = 2, BM = 128, BN = 128;
     extern __shared__ __attribute__((aligned(16))) float Ab[];  // two chunk buffers during the K loop, the output tile in the epilogue
@@ -562,6 +583,7 @@ __global__ __launch_bounds__(256, 2) void pointwise_split_kernel(const PwArgs a)
         const size_t pix = (size_t)b * HW + min(p0 + prow + it * 64, HW - 1);
         pixoff0[it] = pix * s.ld0;
         pixoff1[it] = pix * s.ld1;
+        if constexpr (UNS) pixoff0[it] = uns_row(a.d, b, min(p0 + prow + it * 64, HW - 1));
         rmean[it] = 0.0f; rrstd[it] = 1.0f;
         if (MODE == ND_PRO_LAYERNORM) {                       // host: rowstats present
             rmean[it] = s.rowstats[2 * pix];
@@ -582,14 +604,23 @@ __global__ __launch_bounds__(256, 2) void pointwise_split_kernel(const PwArgs a)
     };
     auto stage_load = [&](int cb) {
         const int c = cb + seg * 8;                            // < Cin: cin % 32 == 0
-        const bool sec = c >= s.c0;                            // a chunk never straddles the sources (host check)
-        const float* base = sec ? s.p1 : s.p0;
-        const int cc = sec ? c - s.c0 : c;
+        if constexpr (UNS) {
+            const float* base = s.p0 + (uns_chunk(a.d, cb) + seg * 8);
 #pragma unroll
-        for (int it = 0; it < 2; ++it) {
-            const float* p = base + (sec ? pixoff1[it] : pixoff0[it]) + cc;
-            raw[it][0] = nd_ld4(p);
-            raw[it][1] = nd_ld4(p + 4);
+            for (int it = 0; it < 2; ++it) {
+                raw[it][0] = nd_ld4(base + pixoff0[it]);
+                raw[it][1] = nd_ld4(base + pixoff0[it] + 4);
+            }
+        } else {
+            const bool sec = c >= s.c0;                        // a chunk never straddles the sources (host check)
+            const float* base = sec ? s.p1 : s.p0;
+            const int cc = sec ? c - s.c0 : c;
+#pragma unroll
+            for (int it = 0; it < 2; ++it) {
+                const float* p = base + (sec ? pixoff1[it] : pixoff0[it]) + cc;
+                raw[it][0] = nd_ld4(p);
+                raw[it][1] = nd_ld4(p + 4);
+            }
         }
         if (MODE == ND_PRO_LAYERNORM) {
             const f32x4 zero = {0, 0, 0, 0};
@@ -1036,6 +1067,33 @@ __global__ void pack_narrow_fold_kernel(const float* __restrict__ wf, const floa
     }
 }
 
+// The wide AttnBlock's tail folded (nd_pack_attn_tail_fold): ff.net.2 and proj_out have only additions between them,
+//   y = Wp (W2 h1 + b2 + x + cb) + bp + x = [Wp W2 | Wp + I] [h1; x] + (Wp b2 + bp) + Wp cb,
+// so w_out (C, 3 C) row-major holds Wp W2 in its first 2 C columns and Wp + I in the last C, b_out = Wp b2 + bp: every C-term sum (and the + 1 of the diagonal)
+// in fp64, rounded ONCE to fp32.  W2 (C, 2 C) and Wp (C, C) in torch layout.  The per-sample Wp cb stays with the caller (it changes with the condition).
+__global__ void pack_attn_tail_fold_kernel(const float* __restrict__ w2, const float* __restrict__ b2, const float* __restrict__ wp, const float* __restrict__ bp,
+                                           float* __restrict__ w_out, float* __restrict__ b_out, int Cc) {
+    const size_t total = (size_t)Cc * 3 * Cc;
+    for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < total + Cc; i += (size_t)gridDim.x * blockDim.x) {
+        if (i >= total) {
+            const int n = (int)(i - total);
+            double s = 0.0;
+            for (int j = 0; j < Cc; ++j) s += (double)wp[(size_t)n * Cc + j] * (double)(b2 ? b2[j] : 0.0f);
+            b_out[n] = (float)(s + (double)(bp ? bp[n] : 0.0f));
+            continue;
+        }
+        const int n = (int)(i / (3 * Cc)), k = (int)(i - (size_t)n * 3 * Cc);
+        double s;
+        if (k < 2 * Cc) {
+            s = 0.0;
+            for (int j = 0; j < Cc; ++j) s += (double)wp[(size_t)n * Cc + j] * (double)w2[(size_t)j * 2 * Cc + k];
+        } else {
+            s = (double)wp[(size_t)n * Cc + (k - 2 * Cc)] + (k - 2 * Cc == n ? 1.0 : 0.0);
+        }
+        w_out[i] = (float)s;
+    }
+}
+
 // (cout, cin) -> [cinP/4][coutP][4], optional K permutation for pixel-unshuffled inputs
 // transposed: `w` is (cin, cout) row-major -- the forward weight of the Linear whose DATA gradient dx = dy @ W this packing serves
 __global__ void pack_pointwise_kernel(const float* __restrict__ w, float* __restrict__ out,
@@ -1122,20 +1180,39 @@ void launch(const PwArgs& a, hipStream_t st) {
 }
 
 // (cout, cin) row-major -> three bf16 terms in [K step][term][32-cout tile][lane 64][8]: slot i of lane l = W[32 tile + (l & 31)][16 ks + 8 (l >> 5) + i]
-__global__ void pack_pointwise_split_kernel(const float* __restrict__ w, unsigned short* __restrict__ out, int cin, int cout, int cinP, int coutP) {
+// unshuffle_c > 0: the K permutation for pixel-unshuffled inputs, as pack_pointwise_kernel applies it
+__global__ void pack_pointwise_split_kernel(const float* __restrict__ w, unsigned short* __restrict__ out, int cin, int cout, int cinP, int coutP, int unshuffle_c) {
     const size_t total = (size_t)cinP * coutP;
     const int n32 = coutP / 32;
     for (size_t idx = blockIdx.x * (size_t)blockDim.x + threadIdx.x; idx < total; idx += (size_t)gridDim.x * blockDim.x) {
         const int i = (int)(idx & 7), l = (int)((idx >> 3) & 63);
         const size_t rest = idx >> 9;
         const int tile = (int)(rest % n32), ks = (int)(rest / n32);
-        const int n = 32 * tile + (l & 31), k = 16 * ks + 8 * (l >> 5) + i;
-        const float v = (n < cout && k < cin) ? w[(size_t)n * cin + k] : 0.0f;
+        const int n = 32 * tile + (l & 31), kp = 16 * ks + 8 * (l >> 5) + i;
+        int k = kp;
+        if (unshuffle_c > 0) {   // packed order (p1 p2 c)  <-  torch order (c p1 p2)
+            const int sub = kp / unshuffle_c, c = kp - sub * unshuffle_c;
+            k = c * 4 + sub;
+        }
+        const float v = (n < cout && kp < cin) ? w[(size_t)n * cin + k] : 0.0f;
         const bf16_terms t = nd_split3_bf16(v);
         unsigned short* o = out + (((size_t)ks * 3 * n32 + tile) * 64 + l) * 8 + i;
         const size_t term = (size_t)n32 * 512;
         o[0] = t.t1;  o[term] = t.t2;  o[2 * term] = t.t3;
     }
+}
+
+// the pixel-unshuffled instances (no prologue): the split kernel's 128 x 128 tiles or the pipelined kernel's 64 x 64
+int launch_downsample(const PwArgs& a, hipStream_t st, bool split) {
+    const dim3 grid(a.total_wg), block(256);
+    if (split) {
+        static nd_device_once configured;
+        if (int e = nd_reserve_lds(configured, reinterpret_cast<const void*>(pointwise_split_kernel<ND_PRO_NONE, true>), SPLIT_LDS, "nd_pointwise_downsample")) return e;
+        hipLaunchKernelGGL((pointwise_split_kernel<ND_PRO_NONE, true>), grid, block, SPLIT_LDS, st, a);
+    } else {
+        hipLaunchKernelGGL((pointwise_pipe_kernel<1, 1, ND_PRO_NONE, true>), grid, block, 0, st, a);
+    }
+    return 0;
 }
 
 int launch_split(const PwArgs& a, hipStream_t st) {
@@ -1365,6 +1442,18 @@ extern "C" int nd_pointwise_narrow_fold_takes(int c0, int c1, int c2, int cout) 
     return c0 > 0 && c1 >= 0 && c2 > 0 && c0 % 4 == 0 && c1 % 4 == 0 && c2 % 4 == 0 && (cout == 4 || cout == 8) && (long)(c0 + c1 + c2) * cout <= 8192;   // weights <= 32 KB of LDS
 }
 
+// ---- the wide AttnBlock's tail as one GEMM: the fold of ff.net.2 and proj_out (pack_attn_tail_fold_kernel above); the GEMM itself is the split entry's
+extern "C" int64_t nd_pack_attn_tail_fold_floats(int C) { return C > 0 ? (int64_t)C * 3 * C : 0; }
+
+extern "C" int nd_pack_attn_tail_fold(const float* w2, const float* b2, const float* wp, const float* bp, float* w_out, float* b_out, int C, void* stream) {
+    ND_REQUIRE(w2 && wp && w_out && b_out, ND_E_BADARG, "nd_pack_attn_tail_fold: null pointer");
+    ND_REQUIRE(C > 0 && C <= 16384, ND_E_SHAPE, "nd_pack_attn_tail_fold: C = %d", C);
+    const size_t total = (size_t)C * 3 * C + C;
+    const int blocks = (int)((total + 255) / 256 < 4096 ? (total + 255) / 256 : 4096);
+    hipLaunchKernelGGL(pack_attn_tail_fold_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, w2, b2, wp, bp, w_out, b_out, C);
+    return nd_launch_status("nd_pack_attn_tail_fold");
+}
+
 extern "C" int64_t nd_pack_narrow_fold_floats(int cin, int cout) { return (int64_t)nd_round_up(cin, 4) * nd_round_up(cout, 4); }
 
 extern "C" int nd_pack_narrow_fold(const float* wf, const float* bf, const float* wr, const float* br, float* w_out, float* b_out, int cin_r, int mid, int cout,
@@ -1407,6 +1496,56 @@ extern "C" int nd_pack_pointwise_weight_split(const float* w, float* packed, int
     const int cinP = nd_round_up(cin, 32), coutP = nd_round_up(cout, 128);
     const size_t total = (size_t)cinP * coutP;
     const int blocks = (int)((total + 255) / 256 < 2048 ? (total + 255) / 256 : 2048);
-    hipLaunchKernelGGL(pack_pointwise_split_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, w, reinterpret_cast<unsigned short*>(packed), cin, cout, cinP, coutP);
+    hipLaunchKernelGGL(pack_pointwise_split_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, w, reinterpret_cast<unsigned short*>(packed), cin, cout, cinP, coutP, 0);
     return nd_launch_status("nd_pack_pointwise_weight_split");
+}
+
+// The same packing behind a pixel-unshuffle (unshuffle_c = cin / 4): K in the order (p1 p2 c) nd_pointwise_downsample_nhwc_f32 stages, as nd_pack_pointwise_weight's
+extern "C" int nd_pack_pointwise_weight_split_unshuffle(const float* w, float* packed, int cin, int cout, int unshuffle_c, void* stream) {
+    ND_REQUIRE(w && packed && nd_aligned16(packed), ND_E_BADARG, "nd_pack_pointwise_weight_split_unshuffle: null or unaligned pointer");
+    ND_REQUIRE(cin > 0 && cout > 0, ND_E_BADARG, "nd_pack_pointwise_weight_split_unshuffle: non-positive size");
+    ND_REQUIRE(unshuffle_c > 0 && unshuffle_c * 4 == cin && unshuffle_c % 4 == 0, ND_E_SHAPE,
+               "nd_pack_pointwise_weight_split_unshuffle: unshuffle_c=%d must be cin/4 and a multiple of 4", unshuffle_c);
+    const int cinP = nd_round_up(cin, 32), coutP = nd_round_up(cout, 128);
+    const size_t total = (size_t)cinP * coutP;
+    const int blocks = (int)((total + 255) / 256 < 2048 ? (total + 255) / 256 : 2048);
+    hipLaunchKernelGGL(pack_pointwise_split_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, w, reinterpret_cast<unsigned short*>(packed), cin, cout, cinP, coutP,
+                       unshuffle_c);
+    return nd_launch_status("nd_pack_pointwise_weight_split_unshuffle");
+}
+
+// ---- Downsample (pixel-unshuffle + 1x1) on the streaming kernels.  The conditions, written once (shape part: no address is read but WHETHER the epilogue's
+// residual operands are given): one pixel-unshuffled source whose sub-pixels are whole 32-channel chunks, no prologue, no residual operands, no output shuffle,
+// cout in whole 64-column tiles.
+namespace {
+int pw_downsample_shape(const nd_pointwise* d, const char* who) {
+    const nd_src& s = d->src;
+    if (int e = pw_shape(d, who ? "nd_pointwise" : nullptr)) return e;
+    ND_DESC_REQUIRE(s.unshuffle == 1 && s.c1 == 0 && (s.c0 / 4) % 32 == 0 && s.mode == ND_PRO_NONE && d->shuffle_c == 0 && d->cout % 64 == 0 &&
+                    !d->res0 && !d->res1 && !d->gn_t && !d->vec, ND_E_SHAPE, "%d -> %d is not a layer of the downsample kernels (one pixel-unshuffled source, "
+                    "(c0 / 4) %% 32 == 0, cout %% 64 == 0, no prologue, no residual operands, no output shuffle: nd_pointwise_downsample_takes)", d->cin, d->cout);
+    return 0;
+}
+}  // namespace
+
+extern "C" int nd_pointwise_downsample_takes(const nd_pointwise* d) { return d && pw_downsample_shape(d, nullptr) == 0; }
+
+// cout % 128 == 0: pointwise_split_kernel's unshuffled instance (`weight`: nd_pack_pointwise_weight_split_unshuffle); otherwise pointwise_pipe_kernel's
+// (`weight`: nd_pack_pointwise_weight with unshuffle_c = cin / 4).  A function of the layer's widths alone.
+extern "C" int nd_pointwise_downsample_nhwc_f32(const nd_pointwise* d, void* stream) {
+    ND_REQUIRE(d, ND_E_BADARG, "nd_pointwise_downsample: null descriptor");
+    if (int e = pw_downsample_shape(d, "nd_pointwise_downsample")) return e;
+    if (int e = pw_ptrs(d, "nd_pointwise_downsample")) return e;
+    const bool split = d->cout % 128 == 0;
+    PwArgs a;
+    a.d = *d;
+    a.uns_h = a.uns_w = 0;
+    a.cinP = d->cin;  a.coutP = d->cout;                       // cin % 128 == 0, cout % 64 == 0: neither packing pads
+    a.m_tiles = nd_cdiv(d->HW, split ? 128 : 64);
+    a.n_tiles = d->cout / (split ? 128 : 64);
+    const long wgs = (long)d->B * a.m_tiles * a.n_tiles;
+    ND_REQUIRE(wgs < (1L << 31), ND_E_SHAPE, "nd_pointwise_downsample: grid too large");
+    a.total_wg = (int)wgs;
+    if (int e = launch_downsample(a, (hipStream_t)stream, split)) return e;
+    return nd_launch_status("nd_pointwise_downsample_nhwc_f32");
 }

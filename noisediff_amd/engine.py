@@ -70,6 +70,9 @@ SPLIT_CHAIN, SPLIT_PW = _SPLIT in ("1", "chain"), _SPLIT in ("1", "pw")
 # The step's two full-resolution block tails folded into their per-pixel consumers.  ND_FOLD_FINAL=0 / ND_SHOT_TAIL=0: A/B knobs (tools/ only).
 FOLD_FINAL = os.environ.get("ND_FOLD_FINAL", "1") != "0"     # final_res_block.res_conv + final_conv: one narrow streaming dot product over [xp; x0; silu(GN(c2))]
 SHOT_TAIL = os.environ.get("ND_SHOT_TAIL", "1") != "0"       # shot_time's tail as the prologue of the shot_mlp3 chain
+# 1x1 work the result does not need.  ND_FOLD_ATTN=0 / ND_DOWN_FAST=0: A/B knobs (tools/ only), read once here.
+FOLD_ATTN = os.environ.get("ND_FOLD_ATTN", "1") != "0"       # wide AttnBlocks: ff.net.2 + proj_out as ONE split GEMM over [h1; x] with the weight [Wp W2 | Wp + I]
+DOWN_FAST = os.environ.get("ND_DOWN_FAST", "1") != "0"       # Downsample's unshuffle + 1x1 on the split / pipelined kernels (nd_pointwise_downsample_nhwc_f32)
 TIME_TABLE = True        # the time embedding's head looked up per timestep (r3; was ND_TIME_TABLE)
 PROJ_TABLE = True        # ... and the stacked ResnetBlock.mlp projection (r4e; was ND_PROJ_TABLE)
 TIME_TABLE_ROWS = 1000                                      # timesteps the table covers (the reference's --timesteps; larger t: computed)
@@ -166,6 +169,21 @@ _CHAIN_SPLIT_LIMIT = (1 << 32) - (1 << 17)    # bytes of one tensor a launch of 
 def _split_layer(cin: int, cout: int) -> bool:
     """1x1 / Linear layers whose weights are also packed as three bf16 terms for nd_pointwise_gemm_split_nhwc_f32: the widths it takes of a plain layer."""
     return SPLIT_PW and pointwise_takes(cin, cout, split=True)
+
+
+def _attn_fold_layer(C_: int) -> bool:
+    """AttnBlocks whose tail (ff.net.2, proj_out) is also packed as ONE folded 3C -> C layer for nd_pointwise_gemm_split_nhwc_f32 over [h1; x]: the wide blocks
+    (C % 128 == 0, where the per-pixel chain does not take the block) of the widths the split entry takes with the second source on its own chunk boundary, up
+    to C = 512.  The fold saves bytes, not products (3 C C per pixel either way): measured, a block's saving falls from 34 % at C = 128 to 8 % at C = 512
+    (DESIGN 8.13); at C = 1024 (d = 128) both GEMMs run at the matrix rate and the two launches stay."""
+    return SPLIT_PW and 0 < C_ <= 512 and C_ % 128 == 0 and pointwise_takes(3 * C_, C_, c1=C_, split=True)
+
+
+def _down_split_layer(cin: int, cout: int) -> bool:
+    """Downsample layers (unshuffle + 1x1, ``cin`` = 4 x the source's channels) whose weights are also packed as three bf16 terms in the unshuffled K order: the
+    ones nd_pointwise_downsample_nhwc_f32 takes and routes to the split kernel (cout % 128 == 0)."""
+    d = L.pointwise(L.src(None, None, L.PRO_NONE, cin, cin // 4, unshuffle=1), None, None, None, 1, 1, 1, cin, cout)
+    return SPLIT_PW and cout % 128 == 0 and bool(L.load().nd_pointwise_downsample_takes(C.byref(d)))
 
 
 def _classify(name: str, shape: Sequence[int]) -> str:
@@ -271,6 +289,8 @@ class Engine:
                         add(p.name + ".chain_s", self.lib.nd_pack_chain_weight_split_floats(p.shape[1], p.shape[0], first), "derived", p.shape)
                 if kind == "pw" and _split_layer(p.shape[1], p.shape[0]):
                     add(p.name + ".split", self.lib.nd_pack_pointwise_weight_split_floats(p.shape[1], p.shape[0]), "derived", p.shape)
+                if kind == "pw_unshuffle" and _down_split_layer(p.shape[1], p.shape[0]):
+                    add(p.name + ".split_uns", self.lib.nd_pack_pointwise_weight_split_floats(p.shape[1], p.shape[0]), "derived", p.shape)
             elif kind == "conv7":
                 n = 196 * p.shape[0]
                 if SPLIT_PW and p.name == "init_conv.weight":      # the per-step stem on the split-product kernel (cond_init_conv runs once per condition)
@@ -293,6 +313,16 @@ class Engine:
                 self.lib.nd_pointwise_narrow_fold_takes(wr.shape[0], wr.shape[0], wr.shape[0], wf.shape[0]):
             add("final_fold.weight", self.lib.nd_pack_narrow_fold_floats(wr.shape[1] + wr.shape[0], wf.shape[0]), "derived", (wf.shape[0], wr.shape[1] + wr.shape[0]))
             add("final_fold.bias", wf.shape[0], "derived", (wf.shape[0],))
+        # wide AttnBlocks: proj_out . ff.net.2 folded into one 3C -> C weight over [h1; x] (nd_pack_attn_tail_fold; a function of the widths alone) and its
+        # constant bias: the per-sample vector Wp cb + bias is formed with the condition (Plan._record_condition, on proj_out's own fp32 packing)
+        for n in [p.name[:-len(".attn.to_v.weight")] for p in self.spec if p.name.endswith(".attn.to_v.weight")]:
+            w2, wp = self.slots.get(n + ".ff.net.2.weight"), self.slots.get(n + ".proj_out.weight")
+            if w2 is None or wp is None:
+                continue
+            Cc = wp.shape[0]
+            if tuple(w2.shape) == (Cc, 2 * Cc) and wp.shape[1] == Cc and _attn_fold_layer(Cc):
+                add(n + ".tail_fold.weight.split", self.lib.nd_pack_pointwise_weight_split_floats(3 * Cc, Cc), "derived", (Cc, 3 * Cc))
+                add(n + ".tail_fold.bias", Cc, "derived", (Cc,))
         # time_mlp's result for every timestep 0 .. TIME_TABLE_ROWS - 1 (st = SiLU(time_mlp(emb(t))), Diffusion_arch.py:100-107,502-507,149): the
         # step kernel looks the head up instead of running two dependent small Linears at the start of every diffusion step
         # (only where the table's builder runs: its head batch of 16 timesteps needs 16 * dim * 36 bytes of LDS and 4 * dim <= 2048 -- dim <= 280;
@@ -364,6 +394,8 @@ class Engine:
                         L.call("nd_pack_pointwise_weight_split", t.data_ptr(), self.p(p.name + ".split"), p.shape[1], p.shape[0], st)
                 elif kind == "pw_unshuffle":
                     L.call("nd_pack_pointwise_weight", t.data_ptr(), dst, p.shape[1], p.shape[0], p.shape[1] // 4, st)
+                    if p.name + ".split_uns" in self.slots:
+                        L.call("nd_pack_pointwise_weight_split_unshuffle", t.data_ptr(), self.p(p.name + ".split_uns"), p.shape[1], p.shape[0], p.shape[1] // 4, st)
                 elif kind == "conv7":
                     L.call("nd_pack_conv7x7_weight", t.data_ptr(), dst, p.shape[0], st)
                     if p.name + ".split" in self.slots:
@@ -373,6 +405,17 @@ class Engine:
                 wr, wf = raw["final_res_block.res_conv.weight"], raw["final_conv.weight"]
                 L.call("nd_pack_narrow_fold", wf.data_ptr(), raw["final_conv.bias"].data_ptr(), wr.data_ptr(), raw["final_res_block.res_conv.bias"].data_ptr(),
                        self.p("final_fold.weight"), self.p("final_fold.bias"), wr.shape[1], wr.shape[0], wf.shape[0], st)
+            folds = [n[:-len(".tail_fold.bias")] for n in self.slots if n.endswith(".tail_fold.bias")]
+            if folds:      # W = [Wp W2 | Wp + I], bias = Wp b2 + bp: the C-term sums in fp64 on the device, rounded once; then the split kernel's packing of W
+                raw = {p.name: t for p, t in zip([q for q in self.spec if q.name in self.slots], keep)}
+                for n in folds:
+                    w2, wp = raw[n + ".ff.net.2.weight"], raw[n + ".proj_out.weight"]
+                    Cc = wp.shape[0]
+                    wfold = torch.empty(self.lib.nd_pack_attn_tail_fold_floats(Cc), dtype=torch.float32, device=self.device)
+                    keep.append(wfold)
+                    L.call("nd_pack_attn_tail_fold", w2.data_ptr(), raw[n + ".ff.net.2.bias"].data_ptr(), wp.data_ptr(), raw[n + ".proj_out.bias"].data_ptr(),
+                           wfold.data_ptr(), self.p(n + ".tail_fold.bias"), Cc, st)
+                    L.call("nd_pack_pointwise_weight_split", wfold.data_ptr(), self.p(n + ".tail_fold.weight.split"), 3 * Cc, Cc, st)
             L.call("nd_stream_sync", st)
             tw = torch.cat([self.view(r + ".mlp.1.weight") for r in self.resnet_names])
             tb = torch.cat([self.view(r + ".mlp.1.bias") for r in self.resnet_names])
@@ -561,6 +604,8 @@ class Plan:
             self.iso_emb = f(B, ISO_DIM)
             self.attn_names = [p.name[:-len(".attn.to_v.weight")] for p in eng.spec if p.name.endswith(".attn.to_v.weight")]
             self.cb = {n: f(B, eng.slots[n + ".proj_out.bias"].shape[0]) for n in self.attn_names}
+            # folded wide blocks: Wp cb + (Wp b2 + bp) per sample, the folded GEMM's epilogue vector
+            self.cbf = {n: f(B, self.cb[n].shape[-1]) for n in self.attn_names if FOLD_ATTN and n + ".tail_fold.bias" in eng.slots}
             self.emb = f(B, d)
             self.t1 = f(B, 4 * d)
             self.st = f(B, 4 * d)
@@ -779,12 +824,42 @@ class Plan:
             kw["rowstats"] = rs
         ln = L.src(x, None, L.PRO_LAYERNORM, vec=cb, gamma=self.e.p(name + ".norm2.weight"), beta=self.e.p(name + ".norm2.bias"), **kw)
         h1 = self.pw(name + ".ff.net.0.0", ln, Cc, 2 * Cc, HW, W, act=L.ACT_GELU)
-        x2 = self.pw(name + ".ff.net.2", L.src(h1), 2 * Cc, Cc, HW, W, res0=x, vec=cb)
-        y = self.pw(name + ".proj_out", L.src(x2), Cc, Cc, HW, W, res0=x)
-        self._release(h1, x2)
+        if self._attn_tail_folds(name, Cc, HW, W):
+            # proj_out(ff.net.2(h1) + x + cb) + x is linear in [h1; x]: one split GEMM with [Wp W2 | Wp + I]; the biases and Wp cb arrive as the per-sample vector
+            y = self.pw(name + ".tail_fold", L.src(h1, x), 3 * Cc, Cc, HW, W, bias=False, vec=self.cbf[name])
+            self._release(h1)
+        else:
+            x2 = self.pw(name + ".ff.net.2", L.src(h1), 2 * Cc, Cc, HW, W, res0=x, vec=cb)
+            y = self.pw(name + ".proj_out", L.src(x2), Cc, Cc, HW, W, res0=x)
+            self._release(h1, x2)
         if rs is not None:
             self._release(rs)
         return y.view(self.B, H, W, Cc)
+
+    def _attn_tail_folds(self, name: str, Cc: int, HW: int, W: int) -> bool:
+        """Does the block's tail run as the folded GEMM?  The knob, the slots, and the split entry's answer to the folded descriptor.  (Debug plans too: they tap
+        the block's output, not x2, and record what the plain plans record.)"""
+        if name not in self.cbf or (name + ".tail_fold.weight.split") not in self.e.slots:
+            return False
+        d = L.pointwise(L.src(None, None, L.PRO_NONE, 2 * Cc, 2 * Cc, 0, Cc, Cc), None, None, None, self.B, HW, W, 3 * Cc, Cc)
+        return bool(self.e.lib.nd_pointwise_gemm_split_takes(C.byref(d)))
+
+    def downsample(self, name: str, x: torch.Tensor, cin: int, cout: int, h: int, w: int) -> torch.Tensor:
+        """Downsample (Diffusion_arch.py:80-81): pixel-unshuffle of ``x`` (2h x 2w x cin) + 1x1 to ``cout`` at h x w -- on the streaming kernels where
+        nd_pointwise_downsample_nhwc_f32 takes the layer (a function of its widths alone), else the generic kernel."""
+        e = self.e
+        src = L.src(x, None, L.PRO_NONE, 4 * cin, cin, unshuffle=1)
+        if DOWN_FAST:
+            split = cout % 128 == 0
+            d = L.pointwise(src, None, e.p(name + ".bias"), None, self.B, h * w, w, 4 * cin, cout)
+            if e.lib.nd_pointwise_downsample_takes(C.byref(d)) and (not split or (name + ".weight.split_uns") in e.slots):
+                out = self._alloc(self.B, h * w, cout)
+                d.out, d.weight = out.data_ptr(), e.p(name + (".weight.split_uns" if split else ".weight"))
+                self._add("nd_pointwise_downsample_nhwc_f32", C.byref(d), e.stream,
+                          meta={"layer": name, "B": self.B, "HW": h * w, "cin": 4 * cin, "cout": cout, "split": int(split)})
+                self._keep.append((d, out))
+                return out
+        return self.pw(name, src, 4 * cin, cout, h * w, w)
 
     def mlp(self, name: str, src: L.Src, cin: int, hid: int, cout: int, H: int, W: int, res0=None) -> torch.Tensor:
         if res0 is None and src.mode == L.PRO_NONE and self._chain_ok(H * W, (cin, hid, cout)):
@@ -822,6 +897,10 @@ class Plan:
                 Cc = self.cb[n].shape[-1]
                 self.linear_rows(self.iso_emb, e.p(n + ".attn.to_v.weight"), None, v, ISO_DIM, inner)
                 self.linear_rows(v, e.p(n + ".attn.to_out.0.weight"), e.p(n + ".attn.to_out.0.bias"), self.cb[n], inner, Cc)
+                if n in self.cbf:                  # the folded tail's vector Wp cb + (Wp b2 + bp): proj_out itself over the B rows of cb, with the folded bias
+                    d = L.pointwise(L.src(self.cb[n]), e.p(n + ".proj_out.weight"), e.p(n + ".tail_fold.bias"), self.cbf[n], 1, B, B, Cc, Cc)
+                    self._add("nd_pointwise_gemm_nhwc_f32", C.byref(d), st, meta={"layer": n + ".tail_fold.vec", "B": 1, "HW": B, "cin": Cc, "cout": Cc, "split": 0})
+                    self._keep.append(d)
             self._release(v)
         self.clean_emb = None
         if tr.cond_branch:
@@ -908,8 +987,7 @@ class Plan:
                 x, *_ = self.conv3(f"{p}.{rs}", L.src(xa), cin, cout, h, w, stats=False)
             else:
                 h, w = h // 2, w // 2
-                x = self.pw(f"{p}.{rs}.1", L.src(xa, None, L.PRO_NONE, 4 * cin, cin, unshuffle=1), 4 * cin, cout,
-                            h * w, w).view(B, h, w, cout)
+                x = self.downsample(f"{p}.{rs}.1", xa, cin, cout, h, w).view(B, h, w, cout)
             if xa is not x2:
                 self._release(xa)
             self._tap(f"down{i}", x)
