@@ -564,6 +564,38 @@ int nd_raw_to_bayer_u16(const float* img, uint16_t* out, const int32_t* bl, int 
  * A thread takes 4, 2 or 1 packed columns: the widest that w and the given outputs' alignment allow. */
 int nd_raw_diffusion_batch_f32(const uint16_t* frames, int N, int H2, int W2, const nd_raw_sample* table, float black, float white, float* noise,
                                float* noisy, float* clean, float* coord, int B, int h, int w, void* stream);
+/* Whole synthetic noisy frames from sampled patches (frame.hip): one launch scatters the OWNED rectangle of each patch of a batch into
+ * frame-sized outputs.  patches: fp32 NCHW [B][4][c][c], what the sampler returns for c x c patches of io.patch_grid; frames: the long exposures,
+ * uint16 [N][H2][W2] as above, or NULL for dark frames; H = H2 / 2, W = W2 / 2.  Row b of `table` (DEVICE memory, rewritten between replays of a
+ * captured launch) places patch b: its origin (x0, y0) in packed pixels of frame `frame_clean`, and the rectangle [ax0, ax1) x [ay0, ay1) of
+ * output frame `frame_out`, in frame coordinates, that it owns.  Packed pixel (Y, X) of the rectangle takes n = patches[b][ch][Y - y0][X - x0]:
+ *   noise: fp32 [F][4][H][W] = n, bits unchanged (a NaN stays a NaN);
+ *   noisy: fp32 [F][4][H][W] = io.compose_noisy against the long exposure, one IEEE fp32 operation per step, no fused multiply-add:
+ *     g = (float)x' - black; g = g < 0 ? 0 : g; clean = g / wb  (nd_raw_diffusion_batch_f32's clean, not clipped; 0 with frames NULL);
+ *     nc = clip(n, -1, 1); noisy = clip(nc + clean, 0, 1), both by comparisons (a NaN passes through);
+ *   short_out: uint16 [F][2H][2W], the frame as the sensor would have recorded it at the short exposure, channel ch at the Bayer site
+ *     nd_raw_to_bayer_u16 uses: p = noisy, NaN -> 0; t = (double)p * (double)wb; t = t / (double)ratio; t = t + (double)black; t = t + 0.5;
+ *     code = min(trunc(t), white): rounded to nearest, so that packing the frame back is unbiased.
+ * Each output may be NULL and is then neither computed nor written; one at least is given.  An empty rectangle is valid and writes nothing.
+ * A row writes nothing either when it is invalid: frame_out outside [0, F), frame_clean outside [0, N) where the frames are read, a patch
+ * window that leaves the frame, a rectangle that leaves its patch window, or, with short_out, a ratio that is not positive and finite.
+ * Rectangles of one launch that share pixels of one output frame give an undefined result there (no atomics; the host side refuses them).
+ * A thread takes an aligned run of 4, 2 or 1 packed columns of the FRAME (the widest that W and the given outputs' alignment allow); a run cut by
+ * a rectangle's edge is done column by column, with the same arithmetic.  All offsets are 64-bit.  No allocation, no synchronisation.
+ * Every refusal is ND_E_BADARG, before any device call: odd or non-positive sides, c, B or F <= 0, B > 65535, c > H or c > W, a NULL table or
+ * NULL patches, no output, frames given with noisy or short_out requested and N <= 0, levels outside 0 <= black < white <= 65535, a pointer
+ * that is not 4-byte aligned. */
+typedef struct nd_frame_patch {
+    int32_t frame_out;      /* index of the output frame, [0, F)                                                           */
+    int32_t frame_clean;    /* index of the long exposure in `frames`, [0, N); not read with frames NULL                    */
+    int32_t x0, y0;         /* patch origin in packed pixels                                                               */
+    int32_t ax0, ay0;       /* the owned rectangle, frame coordinates: first column and row                                */
+    int32_t ax1, ay1;       /* one past its last column and row                                                            */
+    float ratio;            /* exposure ratio of the short frame; read for short_out only                                  */
+    int32_t reserved[3];
+} nd_frame_patch;
+int nd_frame_assemble(const float* patches, const uint16_t* frames, int N, int H2, int W2, const nd_frame_patch* table, float black, float white,
+                      float* noise, float* noisy, uint16_t* short_out, int B, int c, int F, void* stream);
 /* A packed RAW frame developed to an sRGB picture (develop.hip): what test_denoising.py's postprocess_bayer gets from
  * rawpy.postprocess(use_camera_wb=True, half_size=True, no_auto_bright=True, output_bps=8, bright=1), LibRaw's develop steps restated; also
  * half_size=False with the bilinear demosaic and output_bps=16.  NOT checked against LibRaw bit for bit: the yardstick is tests/render_ref.py.

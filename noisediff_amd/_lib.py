@@ -83,6 +83,11 @@ class RawSample(C.Structure):
                 ("k", C.c_double), ("sd", C.c_double), ("ratio64", C.c_double)]
 
 
+class FramePatch(C.Structure):
+    _fields_ = [("frame_out", C.c_int32), ("frame_clean", C.c_int32), ("x0", C.c_int32), ("y0", C.c_int32), ("ax0", C.c_int32), ("ay0", C.c_int32),
+                ("ax1", C.c_int32), ("ay1", C.c_int32), ("ratio", C.c_float), ("reserved", C.c_int32 * 3)]
+
+
 class DevelopParams(C.Structure):
     _fields_ = [("black", C.c_int32 * 4), ("white", C.c_int32), ("scale_mul", C.c_float * 4), ("rgb_cam", C.c_float * 9),
                 ("x0", C.c_int32), ("y0", C.c_int32), ("bps", C.c_int32), ("full", C.c_int32)]
@@ -298,6 +303,7 @@ SIGNATURES = {
     "nd_raw_to_bayer_u16": (i32, [vp, vp, C.POINTER(C.c_int32), i32, i32, i32, i32, vp]),
     "nd_raw_diffusion_batch_f32": (i32, [vp, i32, i32, i32, vp, f32, f32, vp, vp, vp, vp, i32, i32, i32, vp]),
     "nd_raw_develop": (i32, [vp, vp, i32, i32, i32, C.POINTER(DevelopParams), vp, vp, i32, i32, vp]),
+    "nd_frame_assemble": (i32, [vp, vp, i32, i32, i32, vp, f32, f32, vp, vp, vp, i32, i32, i32, vp]),
 }
 
 _UNCHECKED = {"nd_conv3x3_takes", "nd_pointwise_gemm_takes", "nd_pointwise_gemm_split_takes", "nd_pointwise_chain_supported", "nd_pointwise_chain_takes",

@@ -18,7 +18,6 @@
 // on the host) and reads 2V codes = 4V bytes from each Bayer row with the widest load the address allows: a window origin is any integer,
 // so a 16-byte row start is the common case and not a promise.  No LDS; grid (tiles, B).
 #include "nd_common.h"
-#include <type_traits>
 
 #pragma clang fp contract(off)
 
@@ -33,23 +32,11 @@ static_assert(RW_NORMAL_BLOCK == PO_MAX_ATTEMPTS / 2, "the normal draw takes the
 
 
 template <int V>
-__device__ __forceinline__ void rw_store_pairs(uint16_t* p, const uint32_t (&r)[V]) {      // p is 4 V-byte aligned: checked on the host
-    if constexpr (V == 4) *reinterpret_cast<uint4*>(p) = uint4{r[0], r[1], r[2], r[3]};
-    else if constexpr (V == 2) *reinterpret_cast<uint2*>(p) = uint2{r[0], r[1]};
-    else *reinterpret_cast<uint32_t*>(p) = r[0];
-}
-template <int V>
 __device__ __forceinline__ void rw_store_nan(float* p) {
     float nanv[V];
 #pragma unroll
     for (int i = 0; i < V; ++i) nanv[i] = __builtin_nanf("");
     nd_store_v<V>(p, nanv);
-}
-
-// channel c of a Bayer cell given its two words (row 2Y, row 2Y+1)
-__device__ __forceinline__ float rw_code(uint32_t top, uint32_t bottom, int c) {
-    const uint32_t wd = c < 2 ? top : bottom;
-    return (float)((c == 1 || c == 2) ? (wd >> 16) : (wd & 0xFFFFu));
 }
 
 struct RawArgs {
@@ -281,21 +268,6 @@ __global__ __launch_bounds__(RW_THREADS) void raw_bayer_kernel(BayerArgs A) {
     uint16_t* dst = A.out + ((size_t)b * 2 * h + 2 * (size_t)y) * W2 + 2 * (size_t)x;
     rw_store_pairs<V>(dst, top);
     rw_store_pairs<V>(dst + W2, bottom);
-}
-
-// the widest V with w % V == 0 and every pointer of `bits` 4 V-byte aligned
-int rw_width(int w, uintptr_t bits) {
-    if (w % 4 == 0 && (bits & 15u) == 0) return 4;
-    if (w % 2 == 0 && (bits & 7u) == 0) return 2;
-    return 1;
-}
-
-// launch(std::integral_constant<int, V>) for V = 4, 2 or 1: the one place a width chosen at run time becomes a kernel's template argument
-template <class F>
-void rw_dispatch(int V, F launch) {
-    if (V == 4) launch(std::integral_constant<int, 4>());
-    else if (V == 2) launch(std::integral_constant<int, 2>());
-    else launch(std::integral_constant<int, 1>());
 }
 
 dim3 rw_grid(size_t threads, int B) { return dim3((unsigned)((threads + RW_THREADS - 1) / RW_THREADS), (unsigned)B); }
