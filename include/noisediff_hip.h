@@ -564,6 +564,58 @@ int nd_raw_to_bayer_u16(const float* img, uint16_t* out, const int32_t* bl, int 
  * A thread takes 4, 2 or 1 packed columns: the widest that w and the given outputs' alignment allow. */
 int nd_raw_diffusion_batch_f32(const uint16_t* frames, int N, int H2, int W2, const nd_raw_sample* table, float black, float white, float* noise,
                                float* noisy, float* clean, float* coord, int B, int h, int w, void* stream);
+/* The calibrated physics-based noise model of ELD / PMN on windows of resident frames (physics_noise.hip): Poisson shot noise, Gaussian or
+ * Tukey-lambda read noise, row noise, quantisation noise and a bias, the baseline a learned synthesizer is scored against.  Units are codes
+ * above black at the short exposure (DN); wb = white - black in fp32.  Output element (c, y, x) of sample b reads packed row
+ * Y = y0 + (flip ? h-1-y : y) and column X = x0 + x of frame `frame`.  Every line is one IEEE operation (a product and the sum that takes it
+ * are two, no fused multiply-add), in this order:
+ *   c0 = max((float)code - black, 0) (fp32); clean_out = c0 / wb (fp32); latent = c0 / (float)ratio (fp32); lamP = (double)latent / K;
+ *   n ~ Poisson(lamP): nd_philox_poisson_f32's generator, key = seed, counter {e, first_sample + b, draw, blocks 0..31}, e = c h w + y w + x
+ *     of the OUTPUT position (as nd_raw_poisson_gaussian_f32); a lamP that is negative, NaN or infinite gives NaN; K > 0;
+ *   r = the unit read variate, rounded to fp32, from block 32 of the same counter, uniforms u = (word + 0.5) 2^-32 in fp64:
+ *     read_kind 0: sqrt(-2 log(u0)) cos((2 pi) u1) on words 0 and 1, nd_raw_poisson_gaussian_f32's normal exactly;
+ *     read_kind 1: the Tukey-lambda quantile of u2 (word 2): a = log(u2); b = log1p(-u2); lam != 0: p = lam a; q = lam b;
+ *       Q = (expm1(p) - expm1(q)) / lam; lam == 0: Q = a - b.  s_read is then the SCALE of the unit variate (scipy.stats.tukeylambda's
+ *       scale=, PMN's sigTL), not a standard deviation: the unit variance is 2.06 at lam = 0.149 and 4.61 at lam = -0.091, infinite for
+ *       lam <= -0.5.  The expm1 form and not pow: the calibrated |lam| go down to 0.0026.  Any other read_kind gives NaN;
+ *   g = the unit row variate, rounded to fp32: the same Box-Muller on words 0 and 1 of counter {4 Y + c, row_stream, draw, block 33}.  One
+ *     variate per (absolute row Y, channel c) (PMN's randn(C, H, 1)), keyed by the SOURCE row: a flipped window carries the row noise with
+ *     its rows, and windows of one frame that are given one row_stream agree on every row they share;
+ *   uq = (float)(u3 - 0.5), word 3 of block 32;
+ *   t = K n; t = t + s_read r; t = t + s_row g; t = t + qstep uq; t = t + bias (fp64; a zero scale is still multiplied and added);
+ *   t = clip(t, -black, wb) by comparisons, a NaN passes (the sensor's range at the short exposure);
+ *   v = t ratio; v = v / wb; with ND_PHYS_CLIP01: v = clip(v, 0, 1); noisy = fl32(v); noise_out = noisy - clean_out (fp32).
+ * With read_kind 0, s_row = qstep = bias = 0 and ND_PHYS_CLIP01, noisy has the values of nd_raw_poisson_gaussian_f32 for the same key with
+ * k = K and sd = s_read.  `table`: DEVICE memory, rewritten between replays of a captured launch; a row that points outside the frame gives
+ * NaN for its sample and reads nothing.  rng ({seed, first_sample, draw} as int64 in device memory, or NULL) overrides the three arguments;
+ * row_stream comes from the table alone.  counts, reads, quants: fp32 [B][4][h][w]; rows: fp32 [B][4][h], indexed by the OUTPUT row.  An
+ * *_in array replaces its draw, an *_out array returns what was used; each may be NULL, and so may noise_out.  h and w are independent: a
+ * whole frame is one window with h = H2 / 2, w = W2 / 2.  A thread takes 4, 2 or 1 packed columns (the widest that w and the alignment of
+ * noisy, clean_out, noise_out, counts_out, reads_out and quants_out allow) for all four channels.  One launch, no allocation, no
+ * synchronisation.  Every refusal is ND_E_BADARG, before any device call: what nd_raw_poisson_gaussian_f32 refuses (a NULL frames, table,
+ * noisy or clean_out, a negative draw, levels outside 0 <= black < white <= 65535, a size that is not positive, B > 65535, odd sides, a
+ * window larger than the packed frame, 4 h w >= 2^32, frames or an array not 4-byte aligned, table or rng not 8-byte aligned), and a flag
+ * other than ND_PHYS_CLIP01. */
+typedef struct nd_physics_sample {          /* 8-byte aligned, 88 bytes */
+    int32_t frame;          /* index of the frame the window is read from                                                  */
+    int32_t x0, y0;         /* window origin in packed pixels                                                              */
+    int32_t flip;           /* != 0: rows reversed                                                                         */
+    int32_t read_kind;      /* 0: Gaussian read noise, 1: Tukey-lambda                                                     */
+    uint32_t row_stream;    /* counter word 1 of the row variates; the host's default is first_sample + b                  */
+    int32_t reserved[2];
+    double ratio;           /* exposure ratio                                                                              */
+    double K;               /* system gain, DN per electron                                                                */
+    double s_read;          /* scale of the read variate, DN                                                               */
+    double lam;             /* the Tukey-lambda shape; read with read_kind 1 only                                          */
+    double s_row;           /* scale of the row variate, DN                                                                */
+    double qstep;           /* quantisation step q * wb, DN                                                                */
+    double bias;            /* DN                                                                                          */
+} nd_physics_sample;
+#define ND_PHYS_CLIP01 1
+int nd_raw_physics_noise_f32(const uint16_t* frames, int N, int H2, int W2, const nd_physics_sample* table, const int64_t* rng, uint64_t seed,
+                             int64_t first_sample, int32_t draw, const float* counts_in, const float* reads_in, const float* rows_in,
+                             const float* quants_in, float* counts_out, float* reads_out, float* rows_out, float* quants_out, float black,
+                             float white, int flags, float* noisy, float* clean_out, float* noise_out, int B, int h, int w, void* stream);
 /* Whole synthetic noisy frames from sampled patches (frame.hip): one launch scatters the OWNED rectangle of each patch of a batch into
  * frame-sized outputs.  patches: fp32 NCHW [B][4][c][c], what the sampler returns for c x c patches of io.patch_grid; frames: the long exposures,
  * uint16 [N][H2][W2] as above, or NULL for dark frames; H = H2 / 2, W = W2 / 2.  Row b of `table` (DEVICE memory, rewritten between replays of a

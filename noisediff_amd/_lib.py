@@ -83,6 +83,12 @@ class RawSample(C.Structure):
                 ("k", C.c_double), ("sd", C.c_double), ("ratio64", C.c_double)]
 
 
+class PhysicsSample(C.Structure):
+    _fields_ = [("frame", C.c_int32), ("x0", C.c_int32), ("y0", C.c_int32), ("flip", C.c_int32), ("read_kind", C.c_int32),
+                ("row_stream", C.c_uint32), ("reserved", C.c_int32 * 2), ("ratio", C.c_double), ("K", C.c_double), ("s_read", C.c_double),
+                ("lam", C.c_double), ("s_row", C.c_double), ("qstep", C.c_double), ("bias", C.c_double)]
+
+
 class FramePatch(C.Structure):
     _fields_ = [("frame_out", C.c_int32), ("frame_clean", C.c_int32), ("x0", C.c_int32), ("y0", C.c_int32), ("ax0", C.c_int32), ("ay0", C.c_int32),
                 ("ax1", C.c_int32), ("ay1", C.c_int32), ("ratio", C.c_float), ("reserved", C.c_int32 * 3)]
@@ -95,6 +101,7 @@ class DevelopParams(C.Structure):
 
 RAW_PACK, RAW_PACK_SHADED, RAW_TRAIN_REAL = 0, 1, 2       # enum nd_raw_mode
 RAW_RESCALE, RAW_CLIP = 1, 2
+PHYS_CLIP01 = 1
 CHAIN_RES_NONE, CHAIN_RES_INPUT, CHAIN_RES_INPUT_RAW = 0, 1, 2
 
 
@@ -302,6 +309,8 @@ SIGNATURES = {
     "nd_raw_poisson_gaussian_f32": (i32, [vp, i32, i32, i32, vp, vp, u64, i64, i32, vp, vp, vp, vp, f32, f32, vp, vp, i32, i32, i32, vp]),
     "nd_raw_to_bayer_u16": (i32, [vp, vp, C.POINTER(C.c_int32), i32, i32, i32, i32, vp]),
     "nd_raw_diffusion_batch_f32": (i32, [vp, i32, i32, i32, vp, f32, f32, vp, vp, vp, vp, i32, i32, i32, vp]),
+    "nd_raw_physics_noise_f32": (i32, [vp, i32, i32, i32, vp, vp, u64, i64, i32, vp, vp, vp, vp, vp, vp, vp, vp, f32, f32, i32, vp, vp, vp, i32, i32, i32,
+                                       vp]),
     "nd_raw_develop": (i32, [vp, vp, i32, i32, i32, C.POINTER(DevelopParams), vp, vp, i32, i32, vp]),
     "nd_frame_assemble": (i32, [vp, vp, i32, i32, i32, vp, f32, f32, vp, vp, vp, i32, i32, i32, vp]),
 }

@@ -193,6 +193,7 @@ class RawInputs(ParamBlock):
 class _WindowBuilder(BlockBuilder):
     """What the builders of crop windows share: resident frames, one table row per sample."""
     Inputs = RawInputs
+    ROW = ROW                            # the table's row type: a subclass with another table names its own (and its Inputs)
 
     def __init__(self, crop: int, black: float = BLACK, white: float = WHITE):
         crop = int(crop)
@@ -230,8 +231,8 @@ class _WindowBuilder(BlockBuilder):
         check_frames(frame, N)
         if (xy < 0).any() or (xy[:, 0] > W2 // 2 - c).any() or (xy[:, 1] > H2 // 2 - c).any():
             raise ValueError(f"a {c} x {c} window at {xy.tolist()} leaves the packed frame {H2 // 2} x {W2 // 2}")
-        rows = host[_RNG_BYTES:].view(ROW)
-        rows[:] = np.zeros(B, ROW)
+        rows = host[_RNG_BYTES:].view(self.ROW)
+        rows[:] = np.zeros(B, self.ROW)
         rows["frame"], rows["x0"], rows["y0"], rows["flip"] = frame, xy[:, 0], xy[:, 1], flip != 0
         return rows
 
