@@ -616,6 +616,58 @@ int nd_raw_physics_noise_f32(const uint16_t* frames, int N, int H2, int W2, cons
                              int64_t first_sample, int32_t draw, const float* counts_in, const float* reads_in, const float* rows_in,
                              const float* quants_in, float* counts_out, float* reads_out, float* rows_out, float* quants_out, float black,
                              float white, int flags, float* noisy, float* clean_out, float* noise_out, int B, int h, int w, void* stream);
+/* ------------------------------------------------------------------ calibrating the physics-based model from dark frames (calibrate.hip)
+ * What ELD / PMN do on the host with numpy and scipy.stats (row means, ppcc_max, probplot), on uint16 dark frames [N][H2][W2] that stay on the
+ * device.  Units are codes (DN).  h = H2 / 2, w = W2 / 2, a frame's n = 4 h w values are ordered (channel, packed row, packed column) with the
+ * channels and the Bayer cell of nd_raw_pack_u16_f32.  2 <= h, w <= 32768, 1 <= N <= 32767.  Every entry is plain launches on `stream`: no
+ * allocation, no synchronisation, no host read, no floating-point atomics; every fp64 sum has a fixed order (a workgroup's partial in its own
+ * workspace slot, the slots summed in slot order, a constant grid per frame), so the bits of a frame depend on that frame alone.  Argument
+ * errors are ND_E_BADARG before any device call.
+ *
+ * nd_dark_stack_add_u16: sums[y][x] += sum over the N frames of their code at (y, x); sums: int32 [H2][W2], 8-byte aligned, zeroed by the
+ * caller before the first call.  Integer adds: exact, and the split of the frames over calls does not matter.  The caller counts the frames
+ * and stops at 32767 (32767 * 65535 < 2^31).  nd_dark_stack_mean_f64: mean[y][x] = (double)sums[y][x] / (double)count, one IEEE division.
+ *
+ * The integer pixel value: t = D code - P, with D = 1 and P = black when T is NULL, and D = N and P = T[y][x] (the sums of a dark stack over
+ * these N frames) otherwise: N times the deviation from the mean dark frame, the fixed pattern gone exactly.  0 <= black <= 65535.
+ * nd_calib_row_sums_i64: R[n][c][Y] = sum over X of t, int64 [N][4][h], exact.  One wave per (frame, packed row).
+ * nd_calib_residual_f64: x[n][c][Y][X] = (double)(t w - R[n][c][Y]) / (double)(w D), fp64 [N][4 h w], 16-byte aligned: the numerator is an
+ *   exact integer below 2^53 and the denominator is exact, so x is the correctly rounded deviation of a pixel from its row's mean.
+ * Both read V = 4, 2 or 1 packed columns per thread (the widest w allows), as the raw entries do.
+ * nd_calib_row_stats_f64: out fp64 [N][8] = { sigR_pmn, sigR, bias[0..3], V_x, 0 } per frame.  With S_c = sum_Y R[c][Y] and Q_c = sum_Y R[c][Y]^2
+ *   as integers: bias[c] = (double)S_c / (double)(h w D); v = fl(sum_c (h Q_c - S_c^2)) / (double)(4 h h) / (double)(w D) / (double)(w D), the
+ *   integer formed exactly in 128 bits and converted once: the ddof-0 variance of the 4 h row means about their channel's mean;
+ *   sigR_pmn = sqrt(v); V_x = var_x[n * var_stride] (fp64, DEVICE memory: the ddof-0 variance of the frame's x, nd_probplot_f64's out[4]);
+ *   sigR = sqrt(max(v - V_x / (double)(w - 1), 0)), a NaN passing.
+ *
+ * Probability plots of SORTED values xs: fp64 [N][n], ascending per frame, 3 <= n.  The order-statistic medians are scipy's: m[n-1] = 0.5^(1/n)
+ * (pow on the host), m[0] = 1 - m[n-1], m[i-1] = ((double)i - 0.3175) / ((double)n + 0.365).  The theoretical quantile q of m: kind 1, the unit
+ * Tukey-lambda one in nd_raw_physics_noise_f32's form, a = log m; b = log1p(-m); lam != 0: (expm1(lam a) - expm1(lam b)) / lam; lam == 0: a - b;
+ * kind 0, the standard normal one (normcdfinv).  Every element is evaluated: the twin -q of m[n-1-i] is NOT used, because 1 - m[i] is not
+ * m[n-1-i] in fp64.  nd_calib_quantiles_f64 writes q[0..n) for one shape (what the sums below are made of).
+ * One evaluation forms, with xc = x - xs[n / 2] (a shift, so that the one-pass sums do not cancel), S = { sum xc, sum q, sum xc^2, sum q^2,
+ * sum xc q } and from them cxx = S2 - S0 S0 / n, cqq = S3 - S1 S1 / n, cxq = S4 - S0 S1 / n; slope = cxq / cqq; mean = xs[n / 2] + S0 / n;
+ * intercept = mean - slope (S1 / n); r = cxq / (sqrt(cxx) sqrt(cqq)) clipped to [-1, 1] by comparisons: scipy.stats.probplot's
+ * (slope, intercept, r).  A constant frame gives r = NaN.
+ * nd_probplot_f64: one evaluation per frame; out fp64 [N][6] = { slope, intercept, r, mean, cxx / n, 0 }.  lam: fp64 [N] in DEVICE memory
+ *   (kind 1), NULL with kind 0.
+ * nd_ppcc_max_f64: scipy.stats.ppcc_max with a bounded bracket: Brent's bounded minimisation (golden section and parabolic steps, the
+ *   algorithm of scipy.optimize.minimize_scalar(method="bounded") statement by statement) of 1 - r(lam) on (lo, hi), per frame, the state in
+ *   the workspace.  2 max_eval + 1 launches: an evaluation over grid (slots, N) and a one-workgroup-per-frame step that sums the slots,
+ *   updates the bracket and writes the next lam; once a frame's done flag is set its workgroups return at once.  out fp64 [N][3] = { lam,
+ *   r, evaluations }.  The search of a frame ends when |xf - xm| <= 2 tol1 - (b - a) / 2 with tol1 = sqrt(2.2e-16) |xf| + xtol / 3, after
+ *   max_eval evaluations, or at a NaN objective (then lam = r = NaN).  -0.5 < lo < hi, xtol > 0, 3 <= max_eval <= 64.
+ * Workspace of both: nd_ppcc_workspace_bytes(N) bytes, 8-byte aligned, needs no zeroing. */
+int nd_dark_stack_add_u16(const uint16_t* frames, int N, int H2, int W2, int32_t* sums, void* stream);
+int nd_dark_stack_mean_f64(const int32_t* sums, int H2, int W2, int count, double* mean, void* stream);
+int nd_calib_row_sums_i64(const uint16_t* frames, int N, int H2, int W2, const int32_t* T, int black, int64_t* R, void* stream);
+int nd_calib_residual_f64(const uint16_t* frames, int N, int H2, int W2, const int32_t* T, int black, const int64_t* R, double* x, void* stream);
+int nd_calib_row_stats_f64(const int64_t* R, int N, int h, int w, int D, const double* var_x, int var_stride, double* out, void* stream);
+int nd_calib_quantiles_f64(int64_t n, int kind, double lam, double* q, void* stream);
+int64_t nd_ppcc_workspace_bytes(int N);
+int nd_probplot_f64(const double* xs, int N, int64_t n, int kind, const double* lam, double* out, void* workspace, void* stream);
+int nd_ppcc_max_f64(const double* xs, int N, int64_t n, double lo, double hi, double xtol, int max_eval, double* out, void* workspace,
+                    void* stream);
 /* Whole synthetic noisy frames from sampled patches (frame.hip): one launch scatters the OWNED rectangle of each patch of a batch into
  * frame-sized outputs.  patches: fp32 NCHW [B][4][c][c], what the sampler returns for c x c patches of io.patch_grid; frames: the long exposures,
  * uint16 [N][H2][W2] as above, or NULL for dark frames; H = H2 / 2, W = W2 / 2.  Row b of `table` (DEVICE memory, rewritten between replays of a

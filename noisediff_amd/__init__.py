@@ -7,7 +7,8 @@ __all__ = ["GaussianDiffusion", "NoiseDiffNet", "UNet_PosEmbV2", "UNet_PosEmbV2_
            "histogram_counts", "kl_div_forward", "kl_div_inverse", "kl_div_sym", "kl_div_3", "noise_kld", "patch_std_mean", "poisson_lambda_by_patch",
            "LevelMoments", "level_curve", "theil_sen", "get_poisson_lambda", "get_poisson_lambda_all_images", "get_regression_result_all_images",
            "Develop", "gamma_curve", "postprocess_bayer", "FrameLayout", "FrameAssembler", "FrameSynthesizer",
-           "PhysicsNoiseBatchBuilder", "CameraNoiseModel", "physics_frames", "tukey_lambda_quantile", "__version__"]
+           "PhysicsNoiseBatchBuilder", "CameraNoiseModel", "physics_frames", "tukey_lambda_quantile",
+           "DarkStack", "calibrate_dark_frames", "table_row", "ppcc_max", "probplot", "__version__"]
 
 
 def __getattr__(name):
@@ -50,4 +51,7 @@ def __getattr__(name):
     if name in ("PhysicsNoiseBatchBuilder", "CameraNoiseModel", "physics_frames", "tukey_lambda_quantile"):
         from . import physics_noise
         return getattr(physics_noise, name)
+    if name in ("DarkStack", "calibrate_dark_frames", "table_row", "ppcc_max", "probplot"):
+        from . import calibrate
+        return getattr(calibrate, name)
     raise AttributeError(name)

@@ -313,6 +313,15 @@ SIGNATURES = {
                                        vp]),
     "nd_raw_develop": (i32, [vp, vp, i32, i32, i32, C.POINTER(DevelopParams), vp, vp, i32, i32, vp]),
     "nd_frame_assemble": (i32, [vp, vp, i32, i32, i32, vp, f32, f32, vp, vp, vp, i32, i32, i32, vp]),
+    "nd_dark_stack_add_u16": (i32, [vp, i32, i32, i32, vp, vp]),
+    "nd_dark_stack_mean_f64": (i32, [vp, i32, i32, i32, vp, vp]),
+    "nd_calib_row_sums_i64": (i32, [vp, i32, i32, i32, vp, i32, vp, vp]),
+    "nd_calib_residual_f64": (i32, [vp, i32, i32, i32, vp, i32, vp, vp, vp]),
+    "nd_calib_row_stats_f64": (i32, [vp, i32, i32, i32, i32, vp, i32, vp, vp]),
+    "nd_calib_quantiles_f64": (i32, [i64, i32, f64, vp, vp]),
+    "nd_ppcc_workspace_bytes": (i64, [i32]),
+    "nd_probplot_f64": (i32, [vp, i32, i64, i32, vp, vp, vp, vp]),
+    "nd_ppcc_max_f64": (i32, [vp, i32, i64, f64, f64, f64, i32, vp, vp, vp]),
 }
 
 _UNCHECKED = {"nd_conv3x3_takes", "nd_pointwise_gemm_takes", "nd_pointwise_gemm_split_takes", "nd_pointwise_chain_supported", "nd_pointwise_chain_takes",
@@ -323,7 +332,7 @@ _UNCHECKED = {"nd_conv3x3_takes", "nd_pointwise_gemm_takes", "nd_pointwise_gemm_
               "nd_groupnorm_train_workspace_floats", "nd_linear_wgrad_workspace_floats",
               "nd_layernorm_train_workspace_floats", "nd_groupnorm_silu_train_workspace_floats", "nd_conv3x3_wgrad_cat_workspace_floats",
               "nd_convt2x2_wgrad_workspace_floats", "nd_image_quality_workspace_bytes", "nd_illum_scale_workspace_bytes",
-              "nd_histogram_chunk_elements", "nd_histogram_workspace_bytes", "nd_patch_std_mean_workspace_bytes", "nd_level_table_bytes",
+              "nd_histogram_chunk_elements", "nd_histogram_workspace_bytes", "nd_patch_std_mean_workspace_bytes", "nd_level_table_bytes", "nd_ppcc_workspace_bytes",
               "nd_theil_sen_workspace_bytes", "nd_attention_backward_workspace_floats", "nd_linear_attention_backward_workspace_floats",
               "nd_rmsnorm_backward_workspace_floats", "nd_diffusion_loss_slice_elements", "nd_diffusion_loss_workspace_bytes",
               "nd_denoise_loss_slice_pixels", "nd_denoise_loss_workspace_bytes"}

@@ -15,6 +15,7 @@
 // No floating-point atomics, no cooperative launch, no kernel that waits for another workgroup, no host read.
 #include "nd_common.h"
 #include "block_sum.h"
+#include "u128.h"
 #include <float.h>
 
 // The fit mirrors numpy operation by operation (the order of the long sums apart): a product and a sum stay two roundings.
@@ -136,17 +137,6 @@ __global__ __launch_bounds__(256) void level_reset_kernel(u64* __restrict__ tabl
     if (i < 2) counters[i] = 0;
 }
 
-// Round to nearest even, once: the top 64 bits with everything below them folded into the last one, which lies under the rounding position.
-__device__ __forceinline__ double ls_u128_to_double(u128 v) {
-    const u64 hi = (u64)(v >> 64);
-    if (hi == 0) return (double)(u64)v;
-    const int sh = 64 - __builtin_clzll(hi);                                   // 1 .. 64
-    u64 top = (u64)(v >> sh);
-    const u128 below = sh == 64 ? (u128)(u64)v : (v & (((u128)1 << sh) - 1));
-    top |= (u64)(below != 0);
-    return ldexp((double)top, sh);
-}
-
 __global__ __launch_bounds__(256) void level_stats_kernel(const u64* __restrict__ table, int n_levels, int64_t* __restrict__ count,
                                                           double* __restrict__ mean, double* __restrict__ std) {
     const int l = blockIdx.x * 256 + threadIdx.x;
@@ -160,7 +150,7 @@ __global__ __launch_bounds__(256) void level_stats_kernel(const u64* __restrict_
     if (n >= 1) m = (double)(int64_t)(s1 - (n << 32)) / (double)n * 0x1p-30;   // |sum q - n 2^32| < n 2^32 <= 2^63
     if (n >= 2) {
         const u128 num = (u128)n * s2 - (u128)s1 * s1;                         // >= 0 (Cauchy-Schwarz), < 2^128 while n < 2^31
-        s = sqrt(ls_u128_to_double(num) / (double)n / (double)(n - 1)) * 0x1p-30;
+        s = sqrt(nd_u128_to_double(num) / (double)n / (double)(n - 1)) * 0x1p-30;
     }
     mean[l] = m;
     std[l] = s;
